@@ -1,7 +1,17 @@
 """Benchmark: batched Kalman log-likelihood evals/s on MI355X (BASELINE.json configs 2-5).
 
-    python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5]
+    python bench.py [--gpus N --steps K --warmup W] [--config 2|3|4|5] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, settles the clock, warms up, times the K steps and prints the result line (the
+headline `value` / `ms_per_step` and the roofline of the timed launches, which needs no run of its
+own).  `--dump-outputs DIR` also writes what the last timed step computed (`DIR/loglik.npy`: this
+rank's logliks, float64, a non-finite one written as 0.0 with its kind in `DIR/loglik_class.npy`: 0 finite,
+1 −Inf, 2 +Inf, 3 NaN; N > 1 adds `DIR/best_candidate.npy`: [loglik, global index]); the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.  `--full` adds
+every other leg after the timed steps: the full-recursion comparison (`steady_state`), the FP64 mode of
+TVλ (`fp64_mode`), the host-pointer rates (`host_pointer_rate`) and the CPU baselines with the
+binary128-adjudicated parity (`cpu_baseline`); `--no-cpu-baseline` / `--no-host-rate` drop one of them.
 
 `--gpus N > 1` without a launcher (WORLD_SIZE unset) starts the N ranks itself
 (yfm_amd.distributed.spawn_local_ranks: one fresh process per GPU, 127.0.0.1 rendezvous), so
@@ -21,10 +31,10 @@ Other configs (same JSON contract, `config.workload` names them):
 
 Prints ONE JSON line on rank 0 with a `roofline` object (FP64 VALU bound: the algorithmic flops
 of the formulation the dominant kernel runs ÷ HIP-event time of its launches on the library's
-stream) and a `cpu_baseline` object (the faithful dense-LU C restatement, oracle/yfm_oracle.c, on
+stream) and, with `--full`, a `cpu_baseline` object (the faithful dense-LU C restatement, oracle/yfm_oracle.c, on
 a bounded sample of the same workload, OpenMP over the host cores; plus the optimised CPU variant
 and the binary128-adjudicated parity of the sample).  TVλ runs in the library's default certified
-(double-double) precision; `fp64_mode` reports the FP64 mode beside it.
+(double-double) precision; with `--full`, `fp64_mode` reports the FP64 mode beside it.
 """
 from __future__ import annotations
 
@@ -477,6 +487,34 @@ def emulate_world(args) -> dict:
                     "integer leaves a partial last round of waves"}
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> dict:
+    """Write each array as two float64 files of finite numbers: <out_dir>/<name>.npy holds its values with every
+    non-finite one written as 0.0, and <out_dir>/<name>_class.npy says what each element was (0 finite, 1 −Inf,
+    2 +Inf, 3 NaN) — an invalid θ's loglik is −Inf by contract (include/yfm.h), and a comparison of two dumps that
+    subtracts them must not meet Inf − Inf.  When the files together would exceed DUMP_MAX_BYTES every array longer
+    than its share is cut to a fixed, seeded sample of its elements (sorted indices from PCG64(0)), so two runs
+    with the same arguments write the same elements.  Returns {name: elements written}."""
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for k, v in arrays.items()}
+    budget = DUMP_MAX_BYTES // 16 - 128 * len(arrays)  # elements (two files each); 1 KiB per file for the .npy header
+    share = budget // max(1, len(arrays))
+    written = {}
+    if sum(a.size for a in arrays.values()) > budget:
+        rng = np.random.Generator(np.random.PCG64(0))
+        arrays = {k: a if a.size <= share else a[np.sort(rng.choice(a.size, share, replace=False))]
+                  for k, a in arrays.items()}
+    for k, a in arrays.items():
+        cls = np.select([np.isfinite(a), np.isneginf(a), np.isposinf(a)], [0.0, 1.0, 2.0], default=3.0)
+        np.save(d / f"{k}.npy", np.where(cls == 0.0, a, 0.0))
+        np.save(d / f"{k}_class.npy", cls)
+        written[k] = int(a.size)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -490,10 +528,16 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--settle-seconds", type=float, default=0.5,
                     help="untimed load before the warmup steps so the timed steps run at the card's steady clock")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float64, a non-finite "
+                         "value as 0.0 with its kind in DIR/<name>_class.npy): loglik (this rank's logliks) and, "
+                         "with --gpus N > 1, best_candidate")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the full-recursion comparison (steady_state), the FP64 mode "
+                         "of TVλ (fp64_mode), the host-pointer rates and the CPU baselines with their parity table")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-host-rate", action="store_true",
-                    help="skip the host-pointer (PCIe-inclusive) timing, e.g. for PMC passes: its chunked "
-                         "dispatches would mix into the per-dispatch counter averages")
+                    help="with --full: skip the host-pointer (PCIe-inclusive) timing")
     ap.add_argument("--dist-backend", choices=["nccl", "gloo"], default="nccl",
                     help="nccl = RCCL over xGMI (one GPU per rank); gloo = host collectives, ranks may share a GPU "
                          "(multi-rank rehearsal on a one-GPU box)")
@@ -675,13 +719,19 @@ def main():
     roof["kernel_ms_source"] = (f"HIP event pairs on the launch stream around every {EVENT_EVERY}th launch of the "
                                   f"timed region ({len(k_times)} of {args.steps}); each pair brackets the whole "
                                   f"loglik call (filter kernel + deferral launch)")
-    out_host = d_out.cpu().numpy()
+    out_host = outs[(it[0] - 1) % len(outs)].cpu().numpy()  # the buffer the last timed step wrote
     if os.environ.get("YFM_BENCH_DUMP") and rank == 0:  # A/B runs (tools/ab_run.sh): the logliks, for a bitwise compare
         np.save(os.environ["YFM_BENCH_DUMP"], out_host)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = {"loglik": out_host}
+        if best_main is not None:
+            arrays["best_candidate"] = best_main.cpu().numpy()
+        dumped = {"dir": args.dump_outputs, "elements": dump_outputs(args.dump_outputs, arrays)}
     # DNS, GNS5: the same workload with the full covariance recursion every step (YFM_DNS_STEADY=0), beside the
     # default — the steady state must not change a loglik by more than rounding (tests/test_gpu_steady.py)
     steady = None
-    if kind in (KIND_DNS, KIND_GNS):
+    if args.full and kind in (KIND_DNS, KIND_GNS):
         Tb = w.T_use if w.T_use is not None else np.full(B, T)
         os.environ["YFM_DNS_STEADY"] = "0"
         try:
@@ -718,7 +768,7 @@ def main():
 
     # TVλ: the FP64 mode of the same workload beside the certified default (not the metric's value)
     fp64_mode = None
-    if kind == KIND_TVL and args.precision == "certified":
+    if args.full and kind == KIND_TVL and args.precision == "certified":
         eng.precision = _lib.PREC_FP64
         wall64, kms64 = timed(args.steps, max(1, args.warmup // 2))
         f64_host = d_out.cpu().numpy()
@@ -733,7 +783,7 @@ def main():
     # host-pointer boundary (yfm_loglik_batch: θ in over PCIe, logliks back, synchronous) —
     # reported beside the metric, never as `value` (inputs are not HBM-resident there)
     host_rate = None
-    if rank == 0 and world == 1 and not args.no_host_rate:
+    if args.full and rank == 0 and world == 1 and not args.no_host_rate:
         Th_host = np.asfortranarray(w.Theta)
         tu_host = w.T_use
         eng.loglik(kind, Th_host, space=0, T_use=tu_host)
@@ -757,7 +807,7 @@ def main():
                              "pinned_* with both in yfm_alloc_host memory"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, args.cpu_seconds, out_host)
         ro1 = cpu["optimised"].get("evals_per_s_1_thread")
         cpu["gpu_over_cpu"] = {"dense_port": value / cpu["value"],
@@ -780,6 +830,7 @@ def main():
             "clock_settle": {"seconds": round(settle["seconds"], 3), "steps": settle["steps"],
                              "note": "untimed steps before the warmup (--settle-seconds)"},
             "ms_per_step": ms_per_step,
+            "full": args.full,
             "higher_is_better": True,
             "scaling": w.scaling,
             "vs_baseline": None,
@@ -797,6 +848,8 @@ def main():
             "host_pointer_rate": host_rate,
             "outputs": {"neg_inf": n_neginf, "nan": n_nan, "deferred_double_double": n_deferred},
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         if per_rank:
             line.update(per_rank)
         if fp64_mode:

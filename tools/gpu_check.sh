@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout
 echo "pytest ok"
 timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 echo "smoke ok"
-timeout -k 10 200 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout -k 10 200 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cat "$OUT/bench.json"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- python3 bench.py --no-cpu-baseline > "$OUT/bench_traced.json" 2> "$OUT/prof.err"
 echo "rocprof ok"

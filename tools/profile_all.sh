@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=${1:-gpurun_out/prof_all}
 mkdir -p "$OUT"
 for c in 2 3 4 5; do
-  timeout -k 10 300 python -u bench.py --config $c --steps 10 --warmup 2 > "$OUT/bench_c$c.json" 2> "$OUT/bench_c$c.err"
+  timeout -k 10 300 python -u bench.py --full --config $c --steps 10 --warmup 2 > "$OUT/bench_c$c.json" 2> "$OUT/bench_c$c.err"
   echo "bench c$c ok"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace_c$c" -o run --output-format csv -- \
     python3 bench.py --config $c --steps 10 --warmup 2 --no-cpu-baseline > "$OUT/traced_c$c.json" 2> "$OUT/trace_c$c.err"

@@ -48,24 +48,7 @@ int param_count(int kind) {
   return n_lead(kind) + 1 + M * (M + 1) / 2 + M + M * M;
 }
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
+using yfm::DevBuf;
 
 }  // namespace
 
@@ -80,12 +63,18 @@ struct yfm::Workspace {
   DevBuf scratch_dd;  // TVλ double-double records (YFM_PREC_CERTIFIED)
   DevBuf defer;       // candidates handed from the FP64 fixed-loading kernels to the dd kernel
   DevBuf scratch_fd;  // their double-double records (yfm_fixedz_dd.hip)
+  // allocate and zero the two counter banks
+  hipError_t init() {
+    const size_t nb = 2 * yfm::kFlagsPerBank * sizeof(unsigned int);
+    const hipError_t e = flags.ensure(nb);
+    return e == hipSuccess ? hipMemset(flags.p, 0, nb) : e;
+  }
+  unsigned int* bank_ptr(int b) const { return static_cast<unsigned int*>(flags.p) + yfm::kFlagsPerBank * b; }
 };
 
 struct yfm_ctx {
   int device = 0;
   int precision = YFM_PREC_CERTIFIED;  // TVλ arithmetic (yfm_set_precision)
-  int lane_share = 1;                  // concurrent launches in flight (yfm::set_lane_share)
   hipStream_t stream = nullptr;
   hipStream_t copy_stream = nullptr;  // θ uploads of pipelined host-pointer batches (created lazily)
   // panel
@@ -94,24 +83,19 @@ struct yfm_ctx {
   DevBuf colsum;  // the panel's dd column statistics (certified TVλ), made by yfm_set_panel
   // staging for host-pointer calls
   DevBuf theta, out, tuse, rec_beta, rec_P;
-  DevBuf flags;  // 2 banks × kFlagsPerBank unsigned int: n_init_throw, n_neg_inf, deferral list length, n_deferred, steady wave-steps
-  int bank = 0;  // the bank of the last launch (the other one is zeroed by that launch's first kernel)
-  bool bank_dirty = false;            // as Workspace::bank_dirty
-  hipStream_t last_stream = nullptr;  // as Workspace::last_stream
-  DevBuf scratch;  // per-candidate work records (TVλ init)
-  DevBuf scratch_dd;  // TVλ double-double records (YFM_PREC_CERTIFIED)
+  yfm::Workspace own;          // the work buffers of every launch that brings no workspace of its own
   DevBuf traj, init_bad;       // trajectory-mode state records, per-candidate init-throw marks
-  DevBuf defer;                // candidates handed from the FP64 fixed-loading kernels to the dd kernel
-  DevBuf scratch_fd;           // their double-double records (yfm_fixedz_dd.hip)
   DevBuf tiled_raw, tiled_panel;  // get_loss_array with K > 1 passes: the panel tiled K times
-  // TVλ maturity-jump tables, one per lane count L = 2^l (built lazily, reset by set_panel)
+  // TVλ maturity tables, one per lane count L = 2^l (built lazily, reset by set_panel)
   std::vector<double> mats_host;
-  int gap_K[7] = {-1, -1, -1, -1, -1, -1, -1};
-  bool gap_exact[7] = {};
-  DevBuf gap_buf[7];
-  int pow_K[7] = {};       // power-mode tables (TvlGaps::Kp), built with the jump tables
-  double pow_step = 0.0;   // Δ (0: the maturities are not integer multiples of one step)
-  DevBuf pow_buf[7];
+  double pow_step = 0.0;  // Δ (0: the maturities are not integer multiples of one step)
+  struct TvlTab {
+    int K = -1;          // jump table (TvlGaps::K; −1: not built yet)
+    bool exact = false;
+    DevBuf buf;
+    int Kp = 0;          // power-mode table (TvlGaps::Kp), built with the jump table
+    DevBuf pow;
+  } tvl_tab[7];
 };
 
 namespace {
@@ -146,99 +130,111 @@ int check_batch(yfm_ctx* ctx, int kind, int space, int P, int B) {
   return YFM_OK;
 }
 
+// Index of v among the distinct values seen so far (exact equality); a new value is appended, and −1
+// says that it would be one more than `max`.
+int distinct_index(std::vector<double>& seen, double v, int max) {
+  int k = 0;
+  while (k < (int)seen.size() && seen[k] != v) ++k;
+  if (k < (int)seen.size()) return k;
+  if (k == max) return -1;
+  seen.push_back(v);
+  return k;
+}
+
+// A maturity table on the device: `slots` doubles (the distinct values, zero-padded), then one index per maturity.
+int upload_table(DevBuf& buf, std::vector<double>& vals, int slots, const std::vector<int>& idx) {
+  vals.resize(slots, 0.0);
+  const size_t vb = sizeof(double) * slots, ib = sizeof(int) * idx.size();
+  YFM_HIP_CHECK(buf.ensure(vb + ib));
+  char* base = static_cast<char*>(buf.p);
+  YFM_HIP_CHECK(hipMemcpy(base, vals.data(), vb, hipMemcpyHostToDevice));
+  YFM_HIP_CHECK(hipMemcpy(base + vb, idx.data(), ib, hipMemcpyHostToDevice));
+  return YFM_OK;
+}
+
 // Jump table of the TVλ exp recurrence for lane count L: distinct m_{i+L} − m_i (exact
 // equality) and each maturity's index; K = 0 when there are more than yfm::kTvlGaps.
+int build_jump_table(const std::vector<double>& m, int L, yfm_ctx::TvlTab& t) {
+  const int N = (int)m.size();
+  std::vector<double> d;
+  std::vector<int> idx(N, 0);
+  bool ok = true, exact = true;
+  for (int i = 0; i + L < N && ok; ++i) {
+    const double hi = m[i + L], lo = m[i];
+    const double gap = hi - lo;
+    // TwoSum error of the subtraction: the double-double filter needs the jumps exactly
+    const double bb = gap - hi;
+    exact = exact && ((hi - (gap - bb)) + (-lo - bb)) == 0.0;
+    idx[i] = distinct_index(d, gap, yfm::kTvlGaps);
+    ok = idx[i] >= 0;
+  }
+  if (ok && d.empty()) d.push_back(0.0);  // N ≤ L: every lane has at most one maturity
+  const int K = ok ? (int)d.size() : 0;
+  if (K > 0)
+    if (int r = upload_table(t.buf, d, yfm::kTvlGaps, idx)) return r;
+  t.exact = exact;
+  t.K = K;
+  return YFM_OK;
+}
+
+// Δ of the power mode: the gcd of the maturities when each is an integer (exactly, as a double: integer-valued
+// and < 2^31), 0 otherwise.
+double maturity_step(const std::vector<double>& m) {
+  long long gcd = 0;
+  for (const double v : m) {
+    if (!(v > 0.0 && v < 2147483648.0 && v == std::floor(v))) return 0.0;
+    long long a = (long long)v, b = gcd;
+    while (b) {
+      const long long t = a % b;
+      a = b;
+      b = t;
+    }
+    gcd = a;
+  }
+  return (double)gcd;
+}
+
+// Power-mode table for lane count L: the distinct jump exponents (m_{i+L} − m_i)/Δ and each maturity's index;
+// Kp = 0 when Δ = 0, an exponent is outside [1, 512) or there are more than yfm::kTvlPowGaps.
+int build_pow_table(const std::vector<double>& m, double step, int L, yfm_ctx::TvlTab& t) {
+  const int N = (int)m.size();
+  t.Kp = 0;
+  if (step == 0.0 || N <= L) return YFM_OK;
+  std::vector<double> e;
+  std::vector<int> pidx(N, 0);
+  for (int i = 0; i + L < N; ++i) {
+    const double q = (m[i + L] - m[i]) / step;  // exact: integers < 2^31
+    if (!(q >= 1.0 && q < 512.0)) return YFM_OK;
+    pidx[i] = distinct_index(e, q, yfm::kTvlPowGaps);
+    if (pidx[i] < 0) return YFM_OK;
+  }
+  const int Kp = (int)e.size();
+  if (int r = upload_table(t.pow, e, yfm::kTvlPowGaps, pidx)) return r;
+  t.Kp = Kp;
+  return YFM_OK;
+}
+
+// The context's tables for lane count L, built on first use after yfm_set_panel.
 int tvl_gaps(yfm_ctx* ctx, int L, yfm::TvlGaps& g) {
   int l = 0;
   while ((1 << l) < L) ++l;
-  if (ctx->gap_K[l] < 0) {
-    const int N = ctx->N;
-    std::vector<double> d;
-    std::vector<int> idx(N, 0);
-    bool ok = true;
-    bool exact = true;
-    for (int i = 0; i + L < N && ok; ++i) {
-      const double hi = ctx->mats_host[i + L], lo = ctx->mats_host[i];
-      const double gap = hi - lo;
-      // TwoSum error of the subtraction: the double-double filter needs the jumps exactly
-      const double bb = gap - hi;
-      exact = exact && ((hi - (gap - bb)) + (-lo - bb)) == 0.0;
-      int k = 0;
-      while (k < (int)d.size() && d[k] != gap) ++k;
-      if (k == (int)d.size()) {
-        if ((int)d.size() == yfm::kTvlGaps) ok = false;
-        else d.push_back(gap);
-      }
-      idx[i] = k;
-    }
-    int K = ok ? (int)d.size() : 0;
-    if (K == 0 && ok) K = 1, d.push_back(0.0);  // N ≤ L: every lane has at most one maturity
-    d.resize(yfm::kTvlGaps, 0.0);
-    if (K > 0) {
-      YFM_HIP_CHECK(ctx->gap_buf[l].ensure(sizeof(double) * yfm::kTvlGaps + sizeof(int) * N));
-      char* base = static_cast<char*>(ctx->gap_buf[l].p);
-      YFM_HIP_CHECK(hipMemcpy(base, d.data(), sizeof(double) * yfm::kTvlGaps, hipMemcpyHostToDevice));
-      YFM_HIP_CHECK(hipMemcpy(base + sizeof(double) * yfm::kTvlGaps, idx.data(), sizeof(int) * N,
-                              hipMemcpyHostToDevice));
-    }
-    ctx->gap_K[l] = K;
-    ctx->gap_exact[l] = exact;
-    // power mode: every maturity an integer multiple of Δ = gcd (exactly, as doubles: integer-valued and < 2^31)
-    ctx->pow_K[l] = 0;
-    long long gcd = 0;
-    bool integral = N > 0;
-    for (int i = 0; i < N && integral; ++i) {
-      const double m = ctx->mats_host[i];
-      integral = m > 0.0 && m < 2147483648.0 && m == std::floor(m);
-      long long a = integral ? (long long)m : 0, b = gcd;
-      while (b) {
-        const long long t = a % b;
-        a = b;
-        b = t;
-      }
-      gcd = a;
-    }
-    ctx->pow_step = integral ? (double)gcd : 0.0;
-    if (integral && N > L) {
-      std::vector<double> e;
-      std::vector<int> pidx(N, 0);
-      bool fits = true;
-      for (int i = 0; i + L < N && fits; ++i) {
-        const double q = (ctx->mats_host[i + L] - ctx->mats_host[i]) / (double)gcd;  // exact: integers < 2^31
-        int k = 0;
-        while (k < (int)e.size() && e[k] != q) ++k;
-        if (k == (int)e.size()) {
-          if ((int)e.size() == yfm::kTvlPowGaps || !(q >= 1.0 && q < 512.0)) fits = false;
-          else e.push_back(q);
-        }
-        pidx[i] = k;
-      }
-      if (fits) {
-        e.resize(yfm::kTvlPowGaps, 0.0);
-        YFM_HIP_CHECK(ctx->pow_buf[l].ensure(sizeof(double) * yfm::kTvlPowGaps + sizeof(int) * N));
-        char* base = static_cast<char*>(ctx->pow_buf[l].p);
-        YFM_HIP_CHECK(hipMemcpy(base, e.data(), sizeof(double) * yfm::kTvlPowGaps, hipMemcpyHostToDevice));
-        YFM_HIP_CHECK(hipMemcpy(base + sizeof(double) * yfm::kTvlPowGaps, pidx.data(), sizeof(int) * N,
-                                hipMemcpyHostToDevice));
-        int Kp = 0;
-        while (Kp < yfm::kTvlPowGaps && e[Kp] != 0.0) ++Kp;
-        ctx->pow_K[l] = Kp;
-      }
-    }
+  yfm_ctx::TvlTab& t = ctx->tvl_tab[l];
+  if (t.K < 0) {
+    if (int r = build_jump_table(ctx->mats_host, L, t)) return r;
+    ctx->pow_step = maturity_step(ctx->mats_host);
+    if (int r = build_pow_table(ctx->mats_host, ctx->pow_step, L, t)) return r;
   }
-  g.K = ctx->gap_K[l];
-  g.exact = ctx->gap_exact[l];
+  g.K = t.K;
+  g.exact = t.exact;
   if (g.K > 0) {
-    char* base = static_cast<char*>(ctx->gap_buf[l].p);
-    g.d = reinterpret_cast<const double*>(base);
-    g.idx = reinterpret_cast<const int*>(base + sizeof(double) * yfm::kTvlGaps);
+    g.d = static_cast<const double*>(t.buf.p);
+    g.idx = reinterpret_cast<const int*>(g.d + yfm::kTvlGaps);
   }
-  g.Kp = ctx->pow_K[l];
+  g.Kp = t.Kp;
   if (g.Kp > 0) {
-    char* base = static_cast<char*>(ctx->pow_buf[l].p);
     g.step = ctx->pow_step;
-    g.e = reinterpret_cast<const double*>(base);
-    g.pidx = reinterpret_cast<const int*>(base + sizeof(double) * yfm::kTvlPowGaps);
+    g.e = static_cast<const double*>(t.pow.p);
+    g.pidx = reinterpret_cast<const int*>(g.e + yfm::kTvlPowGaps);
   }
   if (const char* ov = std::getenv("YFM_TVL_EXP")) {  // diagnostic: force one exp per maturity
     if (std::atoi(ov) == 1) g.K = g.Kp = 0;
@@ -253,9 +249,131 @@ struct PanelView {
   int T;
 };
 
-int launch_impl(yfm_ctx* ctx, int kind, int space, const double* d_theta, int P, int B, const int* d_T_use,
-                double* d_out, double* d_rb, double* d_rP, hipStream_t s, int horizon, int rec_len,
-                const PanelView* pv, bool reset_flags, yfm::Workspace* ws);
+// One filter launch.  A call site sets the fields it means; the rest keep these defaults.
+struct Launch {
+  int kind = 0, space = 0;
+  const double* theta = nullptr;  // P×B device
+  int P = 0, B = 0;
+  const int* T_use = nullptr;     // B device or nullptr
+  double* out = nullptr;          // B device
+  double* rec_beta = nullptr;     // optional trajectories
+  double* rec_P = nullptr;
+  hipStream_t stream = nullptr;
+  int horizon = 0;                // as LaunchArgs::horizon
+  int rec_len = 0;                // recorded steps per candidate (0 with rec_beta: T − 1)
+  const PanelView* panel = nullptr;  // nullptr: the context's panel
+  bool continues = false;  // a later chunk of a pipelined batch: accumulates into the previous chunk's counters
+  int share = 1;           // launches of this size the caller keeps in flight at once (yfm::loglik_device_ws)
+};
+
+// The plain log-likelihood launch, in the argument order of yfm_loglik_batch_device.
+Launch loglik_launch(int kind, int space, const double* d_theta, int P, int B, const int* d_T_use, double* d_out,
+                     hipStream_t s) {
+  Launch q;
+  q.kind = kind;
+  q.space = space;
+  q.theta = d_theta;
+  q.P = P;
+  q.B = B;
+  q.T_use = d_T_use;
+  q.out = d_out;
+  q.stream = s;
+  return q;
+}
+
+// Enqueue the kernels of one launch on q.stream, with the work buffers of w.
+int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
+  const int B = q.B;
+  const hipStream_t s = q.stream;
+  const int bank = w.bank ^ (q.continues ? 0 : 1);  // the bank this launch uses
+  unsigned int* flags_next = nullptr;
+  if (!q.continues) {
+    flags_next = w.bank_ptr(bank ^ 1);
+  } else {
+    YFM_HIP_CHECK(hipMemsetAsync(w.bank_ptr(bank) + 2, 0, sizeof(unsigned int), s));
+  }
+  if (B == 0) {  // no kernel runs: zero both banks here
+    YFM_HIP_CHECK(hipMemsetAsync(w.flags.p, 0, 2 * yfm::kFlagsPerBank * sizeof(unsigned int), s));
+    return YFM_OK;
+  }
+  yfm::LaunchArgs a;
+  a.theta = q.theta;
+  a.P = q.P;
+  a.B = B;
+  a.space = q.space;
+  a.panel = static_cast<const double*>(ctx->panel.p);
+  a.raw = static_cast<const double*>(ctx->raw.p);
+  a.T = ctx->T;
+  a.N = ctx->N;
+  a.np = ctx->np;
+  a.ldp = ctx->ldp;
+  a.mats = static_cast<const double*>(ctx->mats.p);
+  a.T_use = q.T_use;
+  a.out = q.out;
+  a.flags = w.bank_ptr(bank);
+  a.flags_next = flags_next;
+  a.rec_beta = q.rec_beta;
+  a.rec_P = q.rec_P;
+  a.scratch = nullptr;
+  a.horizon = q.horizon;
+  a.rec_len = q.rec_beta ? (q.rec_len > 0 ? q.rec_len : ctx->T - 1) : 0;
+  if (q.panel) {
+    a.raw = q.panel->raw;
+    a.panel = q.panel->panel;
+    a.T = q.panel->T;
+  }
+  a.stream = s;
+  hipError_t e;
+  if (q.kind == YFM_MODEL_TVL) {
+    int lanes = yfm::tvl_lanes_for(B, ctx->N, q.share);
+    if (const char* ov = std::getenv("YFM_TVL_LANES")) {  // tuning override: 1, 2, 4, …, 64
+      const int l = std::atoi(ov);
+      if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) lanes = l;
+    }
+    yfm::TvlGaps g;
+    if (ctx->precision == YFM_PREC_CERTIFIED) {
+      lanes = yfm::tvl_dd_lanes_for(B, ctx->N, std::getenv("YFM_TVL_LANES") ? lanes : 0, q.share);
+      // the context's panel has its column statistics already; a panel of the launch's own gets them here
+      const bool own_panel = q.panel && q.panel->raw != static_cast<const double*>(ctx->raw.p);
+      const size_t rec_bytes = yfm::tvl_dd_scratch_bytes(B);
+      YFM_HIP_CHECK(w.scratch_dd.ensure(rec_bytes + (own_panel ? yfm::tvl_dd_colsum_bytes(a.T) : 0)));
+      double* rdd = static_cast<double*>(w.scratch_dd.p);
+      const double* colsum = static_cast<const double*>(ctx->colsum.p);
+      if (own_panel) {
+        double* cs = rdd + rec_bytes / sizeof(double);
+        YFM_HIP_CHECK(yfm::launch_tvl_dd_colsum(a.raw, a.N, a.T, cs, s));
+        colsum = cs;
+      }
+      if (int r = tvl_gaps(ctx, lanes, g)) return r;
+      e = yfm::launch_tvl_dd_init(a, rdd);
+      if (e == hipSuccess) e = yfm::launch_tvl_dd(a, rdd, colsum, g, lanes);
+    } else {
+      YFM_HIP_CHECK(w.scratch.ensure(yfm::tvl_scratch_bytes(B)));
+      a.scratch = static_cast<double*>(w.scratch.p);
+      if (int r = tvl_gaps(ctx, lanes, g)) return r;
+      e = yfm::launch_tvl(a, g, lanes);
+    }
+  } else {
+    // N ≤ 64: one filter per lane (MFMA Z'y); larger N: one filter per lane group.  Either defers
+    // the candidates with an ill-conditioned Z'Z, which the double-double kernel then evaluates
+    YFM_HIP_CHECK(w.defer.ensure(sizeof(int) * (size_t)B));
+    YFM_HIP_CHECK(w.scratch_fd.ensure(yfm::fixedz_dd_scratch_bytes(q.kind, B)));
+    a.defer_count = reinterpret_cast<int*>(a.flags + 2);  // zero (a fresh bank, or reset above)
+    a.defer_list = static_cast<int*>(w.defer.p);
+    if (yfm::fixedz_np_for(ctx->N) > 0) {
+      if (const size_t sb = yfm::fixedz_scratch_bytes(q.kind, B)) {
+        YFM_HIP_CHECK(w.scratch.ensure(sb));
+        a.scratch = static_cast<double*>(w.scratch.p);
+      }
+      e = yfm::launch_fixedz(q.kind, a);
+    } else {
+      e = yfm::launch_fixedz_group(q.kind, a);
+    }
+    if (e == hipSuccess) e = yfm::launch_fixedz_dd(q.kind, a, static_cast<double*>(w.scratch_fd.p));
+  }
+  if (e != hipSuccess) return set_error(YFM_EHIP, "kernel launch: %s", hipGetErrorString(e));
+  return YFM_OK;
+}
 
 // Counters [n_init_throw, n_neg_inf, defer_count, n_deferred, steady] in two banks: a launch uses the bank
 // its predecessor zeroed (its first kernel zeroes the other one), so no memset is enqueued per call.
@@ -267,188 +385,85 @@ int launch_impl(yfm_ctx* ctx, int kind, int space, const double* d_theta, int P,
 // touches the previous launch's stream (the estimator destroys its group streams).  The bank index flips
 // only once the launch succeeded.  A pipelined chunk continues its batch's counters and only resets the
 // deferral list length.
-int launch(yfm_ctx* ctx, int kind, int space, const double* d_theta, int P, int B, const int* d_T_use,
-           double* d_out, double* d_rb, double* d_rP, hipStream_t s, int horizon = 0, int rec_len = 0,
-           const PanelView* pv = nullptr, bool reset_flags = true, yfm::Workspace* ws = nullptr) {
-  DevBuf& w_flags = ws ? ws->flags : ctx->flags;
-  int& w_bank = ws ? ws->bank : ctx->bank;
-  bool& dirty = ws ? ws->bank_dirty : ctx->bank_dirty;
-  hipStream_t& last = ws ? ws->last_stream : ctx->last_stream;
-  unsigned int* fb = static_cast<unsigned int*>(w_flags.p);
+int launch(yfm_ctx* ctx, const Launch& q, yfm::Workspace* ws = nullptr) {
+  yfm::Workspace& w = ws ? *ws : ctx->own;
   // the context's own (synchronous) stream after a launch on a caller's stream: that launch may still run
-  if (!ws && s == ctx->stream) YFM_HIP_CHECK(yfm::settle_foreign_launch(ctx));
-  if (reset_flags && (dirty || s != last)) {
-    YFM_HIP_CHECK(hipMemsetAsync(fb + yfm::kFlagsPerBank * (w_bank ^ 1), 0, yfm::kFlagsPerBank * sizeof(unsigned int), s));
-    dirty = false;
+  if (!ws && q.stream == ctx->stream) YFM_HIP_CHECK(yfm::settle_foreign_launch(ctx));
+  if (!q.continues && (w.bank_dirty || q.stream != w.last_stream)) {
+    YFM_HIP_CHECK(hipMemsetAsync(w.bank_ptr(w.bank ^ 1), 0, yfm::kFlagsPerBank * sizeof(unsigned int), q.stream));
+    w.bank_dirty = false;
   }
-  const int r = launch_impl(ctx, kind, space, d_theta, P, B, d_T_use, d_out, d_rb, d_rP, s, horizon, rec_len, pv,
-                            reset_flags, ws);
+  const int r = enqueue(ctx, q, w);
   if (r != YFM_OK) {
-    dirty = true;
+    w.bank_dirty = true;
     return r;
   }
-  if (reset_flags) {
-    w_bank ^= 1;
-    last = s;
+  if (!q.continues) {
+    w.bank ^= 1;
+    w.last_stream = q.stream;
   }
   return YFM_OK;
 }
 
-int launch_impl(yfm_ctx* ctx, int kind, int space, const double* d_theta, int P, int B, const int* d_T_use,
-                double* d_out, double* d_rb, double* d_rP, hipStream_t s, int horizon, int rec_len,
-                const PanelView* pv, bool reset_flags, yfm::Workspace* ws) {
-  DevBuf& w_flags = ws ? ws->flags : ctx->flags;
-  const int w_bank = (ws ? ws->bank : ctx->bank) ^ (reset_flags ? 1 : 0);  // the bank this launch uses
-  DevBuf& w_scratch = ws ? ws->scratch : ctx->scratch;
-  DevBuf& w_scratch_dd = ws ? ws->scratch_dd : ctx->scratch_dd;
-  DevBuf& w_defer = ws ? ws->defer : ctx->defer;
-  DevBuf& w_scratch_fd = ws ? ws->scratch_fd : ctx->scratch_fd;
-  unsigned int* fb = static_cast<unsigned int*>(w_flags.p);
-  unsigned int* flags_next = nullptr;
-  if (reset_flags) {
-    flags_next = fb + yfm::kFlagsPerBank * (w_bank ^ 1);
-  } else {
-    YFM_HIP_CHECK(hipMemsetAsync(fb + yfm::kFlagsPerBank * w_bank + 2, 0, sizeof(unsigned int), s));
-  }
-  if (B == 0) {  // no kernel runs: zero both banks here
-    YFM_HIP_CHECK(hipMemsetAsync(fb, 0, 2 * yfm::kFlagsPerBank * sizeof(unsigned int), s));
-    return YFM_OK;
-  }
-  yfm::LaunchArgs a;
-  a.theta = d_theta;
-  a.P = P;
-  a.B = B;
-  a.space = space;
-  a.panel = static_cast<const double*>(ctx->panel.p);
-  a.raw = static_cast<const double*>(ctx->raw.p);
-  a.T = ctx->T;
-  a.N = ctx->N;
-  a.np = ctx->np;
-  a.ldp = ctx->ldp;
-  a.mats = static_cast<const double*>(ctx->mats.p);
-  a.T_use = d_T_use;
-  a.out = d_out;
-  a.flags = fb + yfm::kFlagsPerBank * w_bank;
-  a.flags_next = flags_next;
-  a.rec_beta = d_rb;
-  a.rec_P = d_rP;
-  a.scratch = nullptr;
-  a.horizon = horizon;
-  a.rec_len = d_rb ? (rec_len > 0 ? rec_len : ctx->T - 1) : 0;
-  if (pv) {
-    a.raw = pv->raw;
-    a.panel = pv->panel;
-    a.T = pv->T;
-  }
-  a.stream = s;
-  hipError_t e;
-  if (kind == YFM_MODEL_TVL) {
-    int lanes = yfm::tvl_lanes_for(B, ctx->N, ctx->lane_share);
-    if (const char* ov = std::getenv("YFM_TVL_LANES")) {  // tuning override: 1, 2, 4, …, 64
-      const int l = std::atoi(ov);
-      if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) lanes = l;
-    }
-    yfm::TvlGaps g;
-    if (ctx->precision == YFM_PREC_CERTIFIED) {
-      lanes = yfm::tvl_dd_lanes_for(B, ctx->N, std::getenv("YFM_TVL_LANES") ? lanes : 0, ctx->lane_share);
-      // the context's panel has its column statistics already; a panel of the launch's own gets them here
-      const bool own_panel = pv && pv->raw != static_cast<const double*>(ctx->raw.p);
-      const size_t rec_bytes = yfm::tvl_dd_scratch_bytes(B);
-      YFM_HIP_CHECK(w_scratch_dd.ensure(rec_bytes + (own_panel ? yfm::tvl_dd_colsum_bytes(a.T) : 0)));
-      double* rdd = static_cast<double*>(w_scratch_dd.p);
-      const double* colsum = static_cast<const double*>(ctx->colsum.p);
-      if (own_panel) {
-        double* cs = rdd + rec_bytes / sizeof(double);
-        YFM_HIP_CHECK(yfm::launch_tvl_dd_colsum(a.raw, a.N, a.T, cs, s));
-        colsum = cs;
-      }
-      if (int r = tvl_gaps(ctx, lanes, g)) return r;
-      e = yfm::launch_tvl_dd_init(a, rdd);
-      if (e == hipSuccess) e = yfm::launch_tvl_dd(a, rdd, colsum, g, lanes);
-    } else {
-      YFM_HIP_CHECK(w_scratch.ensure(yfm::tvl_scratch_bytes(B)));
-      a.scratch = static_cast<double*>(w_scratch.p);
-      if (int r = tvl_gaps(ctx, lanes, g)) return r;
-      e = yfm::launch_tvl(a, g, lanes);
-    }
-  } else {
-    // N ≤ 64: one filter per lane (MFMA Z'y); larger N: one filter per lane group.  Either defers
-    // the candidates with an ill-conditioned Z'Z, which the double-double kernel then evaluates
-    YFM_HIP_CHECK(w_defer.ensure(sizeof(int) * (size_t)B));
-    YFM_HIP_CHECK(w_scratch_fd.ensure(yfm::fixedz_dd_scratch_bytes(kind, B)));
-    a.defer_count = reinterpret_cast<int*>(a.flags + 2);  // zero (a fresh bank, or reset above)
-    a.defer_list = static_cast<int*>(w_defer.p);
-    if (yfm::fixedz_np_for(ctx->N) > 0) {
-      if (const size_t sb = yfm::fixedz_scratch_bytes(kind, B)) {
-        YFM_HIP_CHECK(w_scratch.ensure(sb));
-        a.scratch = static_cast<double*>(w_scratch.p);
-      }
-      e = yfm::launch_fixedz(kind, a);
-    } else {
-      e = yfm::launch_fixedz_group(kind, a);
-    }
-    if (e == hipSuccess) e = yfm::launch_fixedz_dd(kind, a, static_cast<double*>(w_scratch_fd.p));
-  }
-  if (e != hipSuccess) return set_error(YFM_EHIP, "kernel launch: %s", hipGetErrorString(e));
-  return YFM_OK;
-}
-
-// Upload θ (and T_use) for a host-pointer call; returns the device pointers.
-int stage_inputs(yfm_ctx* ctx, const double* theta, int P, int B, const int* T_use, const double** d_th,
-                 const int** d_tu) {
+// The launch of a host-pointer call: θ (and T_use) uploaded into the context's staging buffers on its stream,
+// the logliks to go to ctx->out.
+int stage_inputs(yfm_ctx* ctx, int kind, int space, const double* theta, int P, int B, const int* T_use, Launch& q) {
   const size_t nb = (size_t)(B > 0 ? B : 1);
   YFM_HIP_CHECK(ctx->theta.ensure(sizeof(double) * (size_t)P * nb));
   YFM_HIP_CHECK(ctx->out.ensure(sizeof(double) * nb));
   if (B > 0)
     YFM_HIP_CHECK(hipMemcpyAsync(ctx->theta.p, theta, sizeof(double) * (size_t)P * B, hipMemcpyHostToDevice,
                                  ctx->stream));
-  *d_th = static_cast<const double*>(ctx->theta.p);
-  *d_tu = nullptr;
+  q = loglik_launch(kind, space, static_cast<const double*>(ctx->theta.p), P, B, nullptr,
+                    static_cast<double*>(ctx->out.p), ctx->stream);
   if (T_use && B > 0) {
     YFM_HIP_CHECK(ctx->tuse.ensure(sizeof(int) * nb));
     YFM_HIP_CHECK(hipMemcpyAsync(ctx->tuse.p, T_use, sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream));
-    *d_tu = static_cast<const int*>(ctx->tuse.p);
+    q.T_use = static_cast<const int*>(ctx->tuse.p);
   }
   return YFM_OK;
 }
 
-// Trajectory mode: run the filter kernel recording the last rec_len states of every
+// Trajectory mode: run the staged launch q recording the last q.rec_len states of every
 // candidate into ctx->traj and mark the candidates whose initialize_filter threw.
-int run_trajectory(yfm_ctx* ctx, int kind, int space, const double* d_th, int P, int B, const int* d_tu,
-                   int horizon, int rec_len, const PanelView* pv = nullptr) {
-  const int M = state_dim(kind);
-  const size_t n = (size_t)B * rec_len * M;
+int run_trajectory(yfm_ctx* ctx, Launch q) {
+  const size_t n = (size_t)q.B * q.rec_len * state_dim(q.kind);
   YFM_HIP_CHECK(ctx->traj.ensure(sizeof(double) * (n > 0 ? n : 1)));
-  YFM_HIP_CHECK(ctx->init_bad.ensure((size_t)(B > 0 ? B : 1)));
+  YFM_HIP_CHECK(ctx->init_bad.ensure((size_t)(q.B > 0 ? q.B : 1)));
   YFM_HIP_CHECK(hipMemsetAsync(ctx->traj.p, 0xff, sizeof(double) * n, ctx->stream));  // NaN fill
-  if (int r = launch(ctx, kind, space, d_th, P, B, d_tu, static_cast<double*>(ctx->out.p),
-                     static_cast<double*>(ctx->traj.p), nullptr, ctx->stream, horizon, rec_len, pv))
-    return r;
-  YFM_HIP_CHECK(yfm::launch_init_bad(static_cast<const double*>(ctx->out.p), B,
-                                     static_cast<unsigned char*>(ctx->init_bad.p), ctx->stream));
+  q.rec_beta = static_cast<double*>(ctx->traj.p);
+  if (int r = launch(ctx, q)) return r;
+  YFM_HIP_CHECK(yfm::launch_init_bad(q.out, q.B, static_cast<unsigned char*>(ctx->init_bad.p), ctx->stream));
   return YFM_OK;
 }
 
-yfm::PredictArgs predict_args(yfm_ctx* ctx, int kind, const double* d_th, int P, int B, const int* d_tu,
-                              int horizon, int rec_len) {
+// The emit kernels' view of the trajectory that run_trajectory(ctx, q) recorded.
+yfm::PredictArgs predict_args(yfm_ctx* ctx, const Launch& q, int horizon) {
   yfm::PredictArgs a{};
-  a.kind = kind;
-  a.M = state_dim(kind);
-  a.L = gamma_dim(kind);
+  a.kind = q.kind;
+  a.M = state_dim(q.kind);
+  a.L = gamma_dim(q.kind);
   a.N = ctx->N;
-  a.P = P;
-  a.B = B;
+  a.P = q.P;
+  a.B = q.B;
   a.T = ctx->T;
   a.horizon = horizon;
   a.ncol = ctx->T + horizon - 1;
-  a.theta = d_th;
+  a.theta = q.theta;
   a.mats = static_cast<const double*>(ctx->mats.p);
-  a.T_use = d_tu;
+  a.T_use = q.T_use;
   a.rec = static_cast<const double*>(ctx->traj.p);
-  a.rec_len = rec_len;
+  a.rec_len = q.rec_len;
   a.init_bad = static_cast<const unsigned char*>(ctx->init_bad.p);
   a.stream = ctx->stream;
   return a;
+}
+
+// The counters of the context's last launch (layout: yfm_flags.hpp).
+int read_flags(yfm_ctx* ctx, unsigned int (&h)[yfm::kFlagsPerBank]) {
+  if (int r = check_ctx(ctx)) return r;
+  YFM_HIP_CHECK(hipMemcpy(h, ctx->own.bank_ptr(ctx->own.bank), sizeof(h), hipMemcpyDeviceToHost));
+  return YFM_OK;
 }
 
 int validate_tuse(const int* T_use, int B, int T) {
@@ -466,9 +481,9 @@ int api_error(int code, const char* msg) { return set_error(code, "%s", msg); }
 int panel_T(const yfm_ctx* ctx) { return ctx ? ctx->T : 0; }
 
 hipError_t settle_foreign_launch(yfm_ctx* ctx) {
-  if (!ctx || !ctx->last_stream || ctx->last_stream == ctx->stream) return hipSuccess;
+  if (!ctx || !ctx->own.last_stream || ctx->own.last_stream == ctx->stream) return hipSuccess;
   const hipError_t e = hipDeviceSynchronize();
-  if (e == hipSuccess) ctx->last_stream = nullptr;  // nothing of the context is in flight any more
+  if (e == hipSuccess) ctx->own.last_stream = nullptr;  // nothing of the context is in flight any more
   return e;
 }
 }  // namespace yfm
@@ -498,30 +513,23 @@ yfm_ctx* yfm_create(int hip_device) {
   yfm_ctx* ctx = new yfm_ctx();
   ctx->device = hip_device;
   if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess ||
-      ctx->flags.ensure(2 * yfm::kFlagsPerBank * sizeof(unsigned int)) != hipSuccess) {
+      ctx->own.init() != hipSuccess) {
     set_error(YFM_EHIP, "context allocation failed on device %d", hip_device);
     yfm_destroy(ctx);
     return nullptr;
   }
-  (void)hipMemset(ctx->flags.p, 0, 2 * yfm::kFlagsPerBank * sizeof(unsigned int));
   return ctx;
 }
 
 void yfm_destroy(yfm_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
-  if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  for (DevBuf* b : {&ctx->panel, &ctx->mats, &ctx->raw, &ctx->theta, &ctx->out, &ctx->tuse, &ctx->rec_beta,
-                    &ctx->rec_P, &ctx->flags, &ctx->scratch})
-    b->release();
-  for (DevBuf* b : {&ctx->traj, &ctx->init_bad, &ctx->tiled_raw, &ctx->tiled_panel, &ctx->defer, &ctx->scratch_fd})
-    b->release();
-  ctx->scratch_dd.release();
-  for (DevBuf& b : ctx->gap_buf) b.release();
-  for (DevBuf& b : ctx->pow_buf) b.release();
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  if (ctx->copy_stream) (void)hipStreamDestroy(ctx->copy_stream);
-  delete ctx;
+  for (hipStream_t s : {ctx->stream, ctx->copy_stream}) {
+    if (!s) continue;
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+  }
+  delete ctx;  // every buffer frees itself
 }
 
 void* yfm_alloc_host(size_t bytes) {
@@ -575,7 +583,7 @@ int yfm_set_panel(yfm_ctx* ctx, const double* Y, int N, int T, const double* mat
   ctx->N = N;
   ctx->T = T;
   ctx->mats_host.assign(maturities, maturities + N);
-  for (int& k : ctx->gap_K) k = -1;
+  for (auto& t : ctx->tvl_tab) t.K = -1;
   ctx->np = npad;
   ctx->ldp = ldp;
   return YFM_OK;
@@ -587,13 +595,6 @@ int yfm_loglik_batch(yfm_ctx* ctx, int model_kind, int param_space, const double
   if (int r = check_batch(ctx, model_kind, param_space, P, B)) return r;
   if (B > 0 && (!theta || !loglik_out)) return set_error(YFM_EINVAL, "null theta or loglik_out");
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
-  const size_t nb = (size_t)(B > 0 ? B : 1);
-  YFM_HIP_CHECK(ctx->theta.ensure(sizeof(double) * (size_t)P * nb));
-  YFM_HIP_CHECK(ctx->out.ensure(sizeof(double) * nb));
-  if (T_use && B > 0) YFM_HIP_CHECK(ctx->tuse.ensure(sizeof(int) * nb));
-  double* d_th = static_cast<double*>(ctx->theta.p);
-  double* d_out = static_cast<double*>(ctx->out.p);
-  int* d_tu = T_use ? static_cast<int*>(ctx->tuse.p) : nullptr;
   // Batches that fill the chip several times over are pipelined: chunk k+1's θ is uploaded on
   // the copy stream while chunk k's filter runs on the context stream (each chunk still holds
   // ≥ 2 waves per SIMD of candidates).  Evaluations are independent, so the logliks are the
@@ -604,6 +605,12 @@ int yfm_loglik_batch(yfm_ctx* ctx, int model_kind, int param_space, const double
     if (!ctx->copy_stream) YFM_HIP_CHECK(hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking));
   }
   if (chunk < B) {
+    YFM_HIP_CHECK(ctx->theta.ensure(sizeof(double) * (size_t)P * B));
+    YFM_HIP_CHECK(ctx->out.ensure(sizeof(double) * B));
+    if (T_use) YFM_HIP_CHECK(ctx->tuse.ensure(sizeof(int) * B));
+    double* d_th = static_cast<double*>(ctx->theta.p);
+    double* d_out = static_cast<double*>(ctx->out.p);
+    int* d_tu = T_use ? static_cast<int*>(ctx->tuse.p) : nullptr;
     const int nchunks = (B + chunk - 1) / chunk;
     std::vector<hipEvent_t> ev(nchunks, nullptr);
     int rc = YFM_OK;
@@ -621,8 +628,10 @@ int yfm_loglik_batch(yfm_ctx* ctx, int model_kind, int param_space, const double
         rc = set_error(YFM_EHIP, "pipelined upload: %s", hipGetErrorString(e));
         break;
       }
-      rc = launch(ctx, model_kind, param_space, d_th + (size_t)P * b0, P, nbk, d_tu ? d_tu + b0 : nullptr,
-                  d_out + b0, nullptr, nullptr, ctx->stream, 0, 0, nullptr, k == 0);
+      Launch q = loglik_launch(model_kind, param_space, d_th + (size_t)P * b0, P, nbk, d_tu ? d_tu + b0 : nullptr,
+                               d_out + b0, ctx->stream);
+      q.continues = k > 0;
+      rc = launch(ctx, q);
     }
     if (rc == YFM_OK) {
       hipError_t e = hipMemcpyAsync(loglik_out, d_out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream);
@@ -635,26 +644,22 @@ int yfm_loglik_batch(yfm_ctx* ctx, int model_kind, int param_space, const double
     if (rc == YFM_OK && e != hipSuccess) rc = set_error(YFM_EHIP, "hipStreamSynchronize: %s", hipGetErrorString(e));
     return rc;
   }
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  if (int r = launch(ctx, q)) return r;
   if (B > 0)
-    YFM_HIP_CHECK(hipMemcpyAsync(d_th, theta, sizeof(double) * (size_t)P * B, hipMemcpyHostToDevice, ctx->stream));
-  if (d_tu && B > 0)
-    YFM_HIP_CHECK(hipMemcpyAsync(d_tu, T_use, sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream));
-  if (int r = launch(ctx, model_kind, param_space, d_th, P, B, d_tu, d_out, nullptr, nullptr, ctx->stream))
-    return r;
-  if (B > 0)
-    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, d_out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
   YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return YFM_OK;
 }
-
 
 int yfm_loglik_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
                             const int* d_T_use, double* d_loglik_out, void* hip_stream) {
   if (int r = check_ctx(ctx)) return r;
   if (int r = check_batch(ctx, model_kind, param_space, P, B)) return r;
   if (B > 0 && (!d_theta || !d_loglik_out)) return set_error(YFM_EINVAL, "null d_theta or d_loglik_out");
-  return launch(ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out, nullptr, nullptr,
-                static_cast<hipStream_t>(hip_stream));
+  return launch(ctx, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
+                                   static_cast<hipStream_t>(hip_stream)));
 }
 
 int yfm_filter_states(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
@@ -668,25 +673,17 @@ int yfm_filter_states(yfm_ctx* ctx, int model_kind, int param_space, const doubl
   }
   const int M = state_dim(model_kind);
   const size_t steps = (size_t)(ctx->T - 1) * B;
-  YFM_HIP_CHECK(ctx->theta.ensure(sizeof(double) * (size_t)P * B));
-  YFM_HIP_CHECK(ctx->out.ensure(sizeof(double) * B));
   YFM_HIP_CHECK(ctx->rec_beta.ensure(sizeof(double) * steps * M));
   YFM_HIP_CHECK(ctx->rec_P.ensure(sizeof(double) * steps * M * M));
   YFM_HIP_CHECK(hipMemsetAsync(ctx->rec_beta.p, 0xff, sizeof(double) * steps * M, ctx->stream));  // NaN fill
   YFM_HIP_CHECK(hipMemsetAsync(ctx->rec_P.p, 0xff, sizeof(double) * steps * M * M, ctx->stream));
-  YFM_HIP_CHECK(hipMemcpyAsync(ctx->theta.p, theta, sizeof(double) * (size_t)P * B, hipMemcpyHostToDevice,
-                               ctx->stream));
-  const int* d_tuse = nullptr;
-  if (T_use) {
-    YFM_HIP_CHECK(ctx->tuse.ensure(sizeof(int) * B));
-    YFM_HIP_CHECK(hipMemcpyAsync(ctx->tuse.p, T_use, sizeof(int) * B, hipMemcpyHostToDevice, ctx->stream));
-    d_tuse = static_cast<const int*>(ctx->tuse.p);
-  }
-  if (int r = launch(ctx, model_kind, param_space, static_cast<const double*>(ctx->theta.p), P, B, d_tuse,
-                     static_cast<double*>(ctx->out.p), static_cast<double*>(ctx->rec_beta.p),
-                     static_cast<double*>(ctx->rec_P.p), ctx->stream, 0, ctx->T - 1))
-    return r;
-  YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, ctx->out.p, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  q.rec_beta = static_cast<double*>(ctx->rec_beta.p);
+  q.rec_P = static_cast<double*>(ctx->rec_P.p);
+  q.rec_len = ctx->T - 1;
+  if (int r = launch(ctx, q)) return r;
+  YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
   YFM_HIP_CHECK(hipMemcpyAsync(beta_out, ctx->rec_beta.p, sizeof(double) * steps * M, hipMemcpyDeviceToHost,
                                ctx->stream));
   YFM_HIP_CHECK(hipMemcpyAsync(P_out, ctx->rec_P.p, sizeof(double) * steps * M * M, hipMemcpyDeviceToHost,
@@ -696,27 +693,23 @@ int yfm_filter_states(yfm_ctx* ctx, int model_kind, int param_space, const doubl
 }
 
 int yfm_last_batch_flags(yfm_ctx* ctx, long long* n_init_throw, long long* n_neg_inf) {
-  if (int r = check_ctx(ctx)) return r;
-  unsigned int h[2] = {0, 0};
-  YFM_HIP_CHECK(hipMemcpy(h, static_cast<unsigned int*>(ctx->flags.p) + yfm::kFlagsPerBank * ctx->bank, sizeof(h), hipMemcpyDeviceToHost));
+  unsigned int h[yfm::kFlagsPerBank];
+  if (int r = read_flags(ctx, h)) return r;
   if (n_init_throw) *n_init_throw = h[0];
   if (n_neg_inf) *n_neg_inf = h[1];
   return YFM_OK;
 }
 
 int yfm_last_batch_deferred(yfm_ctx* ctx, long long* n_deferred) {
-  if (int r = check_ctx(ctx)) return r;
-  unsigned int h[4] = {0, 0, 0, 0};
-  YFM_HIP_CHECK(hipMemcpy(h, static_cast<unsigned int*>(ctx->flags.p) + yfm::kFlagsPerBank * ctx->bank, sizeof(h), hipMemcpyDeviceToHost));
+  unsigned int h[yfm::kFlagsPerBank];
+  if (int r = read_flags(ctx, h)) return r;
   if (n_deferred) *n_deferred = h[3];
   return YFM_OK;
 }
 
 int yfm_last_batch_steady(yfm_ctx* ctx, long long* steady_wave_steps) {
-  if (int r = check_ctx(ctx)) return r;
-  unsigned int h[5] = {0, 0, 0, 0, 0};
-  YFM_HIP_CHECK(hipMemcpy(h, static_cast<unsigned int*>(ctx->flags.p) + yfm::kFlagsPerBank * ctx->bank, sizeof(h),
-                          hipMemcpyDeviceToHost));
+  unsigned int h[yfm::kFlagsPerBank];
+  if (int r = read_flags(ctx, h)) return r;
   if (steady_wave_steps) *steady_wave_steps = h[4];
   return YFM_OK;
 }
@@ -733,17 +726,17 @@ int yfm_predict(yfm_ctx* ctx, int model_kind, int param_space, const double* the
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
   if (B == 0) return YFM_OK;
   const int M = state_dim(model_kind), L = gamma_dim(model_kind), N = ctx->N;
-  const int rec_len = ctx->T + horizon;  // every step of the longest candidate
   const size_t ncol = (size_t)ctx->T + horizon - 1;
-  const double* d_th;
-  const int* d_tu;
-  if (int r = stage_inputs(ctx, theta, P, B, T_use, &d_th, &d_tu)) return r;
-  if (int r = run_trajectory(ctx, model_kind, param_space, d_th, P, B, d_tu, horizon, rec_len)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  q.horizon = horizon;
+  q.rec_len = ctx->T + horizon;  // every step of the longest candidate
+  if (int r = run_trajectory(ctx, q)) return r;
   // outputs: one device block [preds | load1 | load2 | factors | states]
   const size_t nN = (size_t)N * ncol * B, nM = (size_t)M * ncol * B, nL = (size_t)L * ncol * B;
   YFM_HIP_CHECK(ctx->rec_P.ensure(sizeof(double) * (3 * nN + nM + nL)));
   double* d = static_cast<double*>(ctx->rec_P.p);
-  yfm::PredictArgs a = predict_args(ctx, model_kind, d_th, P, B, d_tu, horizon, rec_len);
+  yfm::PredictArgs a = predict_args(ctx, q, horizon);
   a.preds = d;
   a.load1 = loadings_1 ? d + nN : nullptr;
   a.load2 = loadings_2 ? d + 2 * nN : nullptr;
@@ -770,13 +763,14 @@ int yfm_forecast(yfm_ctx* ctx, int model_kind, int param_space, const double* th
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
   if (B == 0) return YFM_OK;
   const int M = state_dim(model_kind), L = gamma_dim(model_kind), N = ctx->N;
-  const double* d_th;
-  const int* d_tu;
-  if (int r = stage_inputs(ctx, theta, P, B, T_use, &d_th, &d_tu)) return r;
-  if (int r = run_trajectory(ctx, model_kind, param_space, d_th, P, B, d_tu, horizon, horizon + 1)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  q.horizon = horizon;
+  q.rec_len = horizon + 1;
+  if (int r = run_trajectory(ctx, q)) return r;
   const size_t n = (size_t)(M + L + N) * horizon * B;
   YFM_HIP_CHECK(ctx->rec_P.ensure(sizeof(double) * n));
-  yfm::PredictArgs a = predict_args(ctx, model_kind, d_th, P, B, d_tu, horizon, horizon + 1);
+  yfm::PredictArgs a = predict_args(ctx, q, horizon);
   a.preds = static_cast<double*>(ctx->rec_P.p);
   YFM_HIP_CHECK(yfm::launch_forecast_emit(a));
   YFM_HIP_CHECK(hipMemcpyAsync(out, a.preds, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -794,9 +788,8 @@ int yfm_loss_array(yfm_ctx* ctx, int model_kind, int param_space, const double* 
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
   const int T1 = ctx->T - 1;
   if (B == 0 || T1 <= 0) return YFM_OK;
-  const double* d_th;
-  const int* d_tu;
-  if (int r = stage_inputs(ctx, theta, P, B, T_use, &d_th, &d_tu)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
   PanelView pv{static_cast<const double*>(ctx->raw.p), static_cast<const double*>(ctx->panel.p), ctx->T};
   if (K > 1) {
     // the K passes continue the filter state (filter.jl:221-242 never re-initialises):
@@ -814,15 +807,15 @@ int yfm_loss_array(yfm_ctx* ctx, int model_kind, int param_space, const double* 
                                          static_cast<double*>(ctx->tiled_panel.p), ctx->stream));
     pv = PanelView{static_cast<const double*>(ctx->tiled_raw.p), static_cast<const double*>(ctx->tiled_panel.p), Tk};
   }
-  const int rec_len = pv.T - 1;
-  if (int r = run_trajectory(ctx, model_kind, param_space, d_th, P, B, d_tu, 0, rec_len, &pv)) return r;
-  unsigned int* cur = static_cast<unsigned int*>(ctx->flags.p) + yfm::kFlagsPerBank * ctx->bank;
+  q.rec_len = pv.T - 1;
+  q.panel = &pv;
+  if (int r = run_trajectory(ctx, q)) return r;
+  unsigned int* cur = ctx->own.bank_ptr(ctx->own.bank);
   YFM_HIP_CHECK(hipMemsetAsync(cur, 0, 2 * sizeof(unsigned int), ctx->stream));
   YFM_HIP_CHECK(ctx->rec_P.ensure(sizeof(double) * (size_t)T1 * B));
-  yfm::PredictArgs a = predict_args(ctx, model_kind, d_th, P, B, d_tu, 1, rec_len);
+  yfm::PredictArgs a = predict_args(ctx, q, 1);
   a.preds = static_cast<double*>(ctx->rec_P.p);
-  YFM_HIP_CHECK(yfm::launch_loss_array(a, static_cast<const double*>(ctx->raw.p), T1, K,
-                                       cur));
+  YFM_HIP_CHECK(yfm::launch_loss_array(a, static_cast<const double*>(ctx->raw.p), T1, K, cur));
   YFM_HIP_CHECK(hipMemcpyAsync(mse_out, a.preds, sizeof(double) * (size_t)T1 * B, hipMemcpyDeviceToHost, ctx->stream));
   YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return YFM_OK;
@@ -834,29 +827,22 @@ namespace yfm {
 
 Workspace* workspace_create() {
   auto* w = new Workspace;
-  if (w->flags.ensure(2 * yfm::kFlagsPerBank * sizeof(unsigned int)) != hipSuccess ||
-      hipMemset(w->flags.p, 0, 2 * yfm::kFlagsPerBank * sizeof(unsigned int)) != hipSuccess) {
+  if (w->init() != hipSuccess) {
     delete w;
     return nullptr;
   }
   return w;
 }
 
-void workspace_destroy(Workspace* w) {
-  if (!w) return;
-  for (DevBuf* b : {&w->flags, &w->scratch, &w->scratch_dd, &w->defer, &w->scratch_fd}) b->release();
-  delete w;
-}
+void workspace_destroy(Workspace* w) { delete w; }
 
 int loglik_device_ws(yfm_ctx* ctx, Workspace* ws, int kind, int space, const double* d_theta, int P, int B,
-                     const int* d_T_use, double* d_out, hipStream_t s) {
+                     const int* d_T_use, double* d_out, hipStream_t s, int share) {
   if (int r = check_ctx(ctx)) return r;
   if (int r = check_batch(ctx, kind, space, P, B)) return r;
-  return launch(ctx, kind, space, d_theta, P, B, d_T_use, d_out, nullptr, nullptr, s, 0, 0, nullptr, true, ws);
-}
-
-void set_lane_share(yfm_ctx* ctx, int share) {
-  if (ctx) ctx->lane_share = share > 1 ? share : 1;
+  Launch q = loglik_launch(kind, space, d_theta, P, B, d_T_use, d_out, s);
+  q.share = share > 1 ? share : 1;
+  return launch(ctx, q, ws);
 }
 
 }  // namespace yfm

@@ -290,44 +290,35 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
   // so a round costs one filter latency instead of filter + host bookkeeping + transfers.
   int G = R >= 32 ? 2 : 1;
   if (const char* e = std::getenv("YFM_EST_GROUPS")) G = std::max(1, std::min(kMaxGroups, std::atoi(e)));
-  // device-side batch: θ uploaded per round on each group's own stream, T_use once
+  // device-side batch: θ uploaded per round on each group's own stream, T_use once.  The buffers are declared
+  // before the guard of the streams, so they are freed after it has waited for the streams' work
+  yfm::DevBuf buf_th, buf_out, buf_tu;
   hipStream_t sts[kMaxGroups] = {};
   yfm::Workspace* wss[kMaxGroups] = {};  // group 0 uses the context's own buffers
-  double *d_th = nullptr, *d_out = nullptr;
-  int* d_tu = nullptr;
   struct Release {
     hipStream_t (&s)[kMaxGroups];
     yfm::Workspace* (&w)[kMaxGroups];
-    double*& a;
-    double*& b;
-    int*& c;
     ~Release() {
       for (hipStream_t x : s)
         if (x) (void)hipStreamSynchronize(x);
-      if (a) (void)hipFree(a);
-      if (b) (void)hipFree(b);
-      if (c) (void)hipFree(c);
       for (hipStream_t x : s)
         if (x) (void)hipStreamDestroy(x);
       for (yfm::Workspace* x : w) yfm::workspace_destroy(x);
     }
-  } release{sts, wss, d_th, d_out, d_tu};
-  // the G groups' launches run side by side: each group's TVλ launch is sized for its share of the device
-  struct Share {
-    yfm_ctx* c;
-    ~Share() { yfm::set_lane_share(c, 1); }
-  } share_reset{ctx};
-  yfm::set_lane_share(ctx, G);
+  } release{sts, wss};
   for (int g = 0; g < G; ++g)
     if (hipStreamCreateWithFlags(&sts[g], hipStreamNonBlocking) != hipSuccess)
       return yfm::api_error(YFM_EHIP, "stream creation failed for the estimation batch");
   for (int g = 1; g < G; ++g)
     if (!(wss[g] = yfm::workspace_create()))
       return yfm::api_error(YFM_EHIP, "workspace allocation failed for the estimation batch");
-  if (hipMalloc(&d_th, sizeof(double) * (size_t)B * P) != hipSuccess ||
-      hipMalloc(&d_out, sizeof(double) * (size_t)B) != hipSuccess ||
-      (T_use && hipMalloc(&d_tu, sizeof(int) * (size_t)B) != hipSuccess))
+  if (buf_th.ensure(sizeof(double) * (size_t)B * P) != hipSuccess ||
+      buf_out.ensure(sizeof(double) * (size_t)B) != hipSuccess ||
+      (T_use && buf_tu.ensure(sizeof(int) * (size_t)B) != hipSuccess))
     return yfm::api_error(YFM_EHIP, "device allocation failed for the estimation batch");
+  double* const d_th = static_cast<double*>(buf_th.p);
+  double* const d_out = static_cast<double*>(buf_out.p);
+  int* const d_tu = static_cast<int*>(buf_tu.p);
   if (T_use && hipMemcpy(d_tu, pin_tu.p, sizeof(int) * (size_t)B, hipMemcpyHostToDevice) != hipSuccess)
     return yfm::api_error(YFM_EHIP, "T_use upload failed");
   int nthreads = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
@@ -382,12 +373,13 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
     r_end[g] = last_active.load() + 1;
     return active.load() > 0;
   };
+  // the G groups' launches run side by side: each is sized for its share G of the device
   auto submit = [&](int g) -> int {
     const size_t o = (size_t)r0[g] * SLOT;
     const int Bg = (r_end[g] - r0[g]) * SLOT;
     if (zero_copy) {
       const int rc = yfm::loglik_device_ws(ctx, wss[g], model_kind, YFM_THETA_UNCONSTRAINED, map_th + o * P, P, Bg,
-                                           d_tu ? d_tu + o : nullptr, map_out + o, sts[g]);
+                                           d_tu ? d_tu + o : nullptr, map_out + o, sts[g], G);
       if (rc != YFM_OK) return rc;
       device_evals += Bg;
       ++rounds;
@@ -397,7 +389,7 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
         hipSuccess)
       return yfm::api_error(YFM_EHIP, "θ upload failed");
     const int rc = yfm::loglik_device_ws(ctx, wss[g], model_kind, YFM_THETA_UNCONSTRAINED, d_th + o * P, P, Bg,
-                                         d_tu ? d_tu + o : nullptr, d_out + o, sts[g]);
+                                         d_tu ? d_tu + o : nullptr, d_out + o, sts[g], G);
     if (rc != YFM_OK) return rc;
     if (hipMemcpyAsync(out + o, d_out + o, sizeof(double) * (size_t)Bg, hipMemcpyDeviceToHost, sts[g]) != hipSuccess)
       return yfm::api_error(YFM_EHIP, "loglik download failed");

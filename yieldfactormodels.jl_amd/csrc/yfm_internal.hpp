@@ -7,6 +7,28 @@
 
 namespace yfm {
 
+// A device allocation that grows on demand and frees itself.  It is destroyed with the device it was
+// allocated on current (yfm_destroy sets the context's device before it deletes the context).
+struct DevBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    return e;
+  }
+};
+
 struct LaunchArgs {
   const double* theta;  // P×B device
   int P, B, space;
@@ -105,15 +127,15 @@ hipError_t launch_predict_emit(const PredictArgs& a);
 hipError_t launch_forecast_emit(const PredictArgs& a);
 hipError_t launch_loss_array(const PredictArgs& a, const double* Y, int T1, int passes, unsigned int* flags);
 // Extra per-launch work buffers (flags, deferral list, init records) so launches can be in flight
-// on several streams of one context at once (yfm_capi.hip; used by the estimation driver).
+// on several streams of one context at once (yfm_capi.hip; used by the estimation driver).  A null
+// workspace is the context's own.  `share`: launches of similar size the caller keeps in flight at once
+// (the TVλ lane choice sizes the device's share of this launch by it): the estimation driver passes its
+// chain-group count, every other caller 1.
 struct Workspace;
 Workspace* workspace_create();
 void workspace_destroy(Workspace* w);
 int loglik_device_ws(yfm_ctx* ctx, Workspace* ws, int kind, int space, const double* d_theta, int P, int B,
-                     const int* d_T_use, double* d_out, hipStream_t s);
-// concurrent launches of similar size the caller keeps in flight (the TVλ lane choice sizes the device's share of
-// each launch by it); the estimation driver sets its chain-group count and restores 1
-void set_lane_share(yfm_ctx* ctx, int share);
+                     const int* d_T_use, double* d_out, hipStream_t s, int share);
 // record `msg` as yfm_last_error() for this thread and return `code` (host helpers above the C ABI)
 int api_error(int code, const char* msg);
 // columns of the context's panel (0 before yfm_set_panel)

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YFM_ABI_VERSION 2
+#define YFM_ABI_VERSION 3
 
 typedef struct yfm_ctx yfm_ctx;
 
@@ -212,6 +212,33 @@ int yfm_last_batch_deferred(yfm_ctx* ctx, long long* n_deferred);
  * step that depends on its own θ only.  YFM_DNS_STEADY=0 in the environment disables it.  0 for the
  * other models, for trajectories and for panels shorter than 80 columns (full recursion there). */
 int yfm_last_batch_steady(yfm_ctx* ctx, long long* steady_wave_steps);
+
+/* Batched log-likelihood WITH its gradient — replaces, per candidate, the value and the ForwardDiff
+ * gradient that estimate! asks for (optimization.jl:367, TwiceDifferentiable(...; autodiff=:forward))
+ * of compute_loss (optimization.jl:10-23), with the sign of get_loss: loglik_out[b] is what
+ * yfm_loglik_batch returns and grad_out[:, b] (P×B column-major) = ∂(+loglik)/∂θ_i in the space the
+ * caller passed — the unconstrained space includes the derivatives of exp and of from_R_to_11
+ * (transformations.jl:2-4, :21-26); the constrained space is the derivative with respect to θ_c itself.
+ * The gradient is exact (forward-mode tangents of the full filter recursion, quirks of filter.jl:190-206
+ * included: t = 1 not accumulated, the last column unused, a NaN column a prediction-only step whose
+ * stale F/v term — and its tangent — is added again).  YFM_MODEL_DNS with N ≤ 64 only: TVλ, GNS5 and
+ * larger N return YFM_EUNSUPPORTED.  grad_out[:, b] is NaN in all P entries where loglik_out[b] is −Inf
+ * (n_neg_inf) or NaN (n_init_throw), and for the candidates of yfm_last_batch_deferred (their value comes
+ * from the double-double path, which carries no tangents): those are counted by
+ * yfm_last_batch_grad_unavailable.  yfm_last_batch_flags keeps its meaning.  Synchronous. */
+int yfm_loglik_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                          const int* T_use, double* loglik_out, double* grad_out);
+
+/* Same (optimization.jl:367, :10-23) with DEVICE pointers on the caller's HIP stream; asynchronous, with
+ * the ordering rules of yfm_loglik_batch_device. */
+int yfm_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
+                                 const int* d_T_use, double* d_loglik_out, double* d_grad_out, void* hip_stream);
+
+/* Candidates of the last gradient batch on this ctx with a finite-or-not loglik from the double-double
+ * path and therefore NaN gradients (optimization.jl:367 has no counterpart: ForwardDiff differentiates
+ * the dense path of optimization.jl:10-23 there).  0 after a batch that asked for no gradient.  For
+ * yfm_loglik_grad_batch_device, synchronise the stream first. */
+int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,88 @@
+"""CPU test of the DNS gradient's tangent algebra (csrc/yfm_grad.hpp): the functions the gfx950 kernel runs,
+compiled for the host (tests/grad_host_check.cpp, -ffp-contract=off) and run one candidate at a time on the
+fixture cases B (N = 10, one NaN entry) and E (N = 4), held to the GPU test's rule:
+
+    max_i |g − g_fd| ≤ 1e-9·‖g_fd‖∞ + e_fd[b]   for every compared candidate, at least 75% compared.
+"""
+from __future__ import annotations
+
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN, ROOT
+
+sys.path.insert(0, str(GOLDEN / "grad"))
+import make_grad as MG  # noqa: E402
+
+REL = 1e-9
+
+
+@pytest.fixture(scope="module")
+def harness(tmp_path_factory):
+    exe = tmp_path_factory.mktemp("grad") / "grad_host_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
+                    str(ROOT / "tests" / "grad_host_check.cpp"), "-o", str(exe)], check=True)
+    return exe
+
+
+def hexf(v) -> str:
+    return "nan" if v != v else float(v).hex()
+
+
+def run_host(exe, tmp_path, Y, m, Th, tu, space=0):
+    N, T = Y.shape
+    B = Th.shape[1]
+    words = [str(N), str(T), str(B), str(space)]
+    words += [hexf(v) for v in m]
+    words += [hexf(v) for v in np.asarray(Y).reshape(-1, order="F")]
+    for b in range(B):
+        words.append(str(int(tu[b])))
+        words += [hexf(v) for v in Th[:, b]]
+    path = tmp_path / "case.txt"
+    path.write_text(" ".join(words))
+    out = subprocess.run([str(exe), str(path)], check=True, capture_output=True, text=True).stdout.split("\n")
+    rows = np.array([[float.fromhex(v) if "0x" in v else float(v) for v in line.split()] for line in out[:B]])
+    return rows[:, 0], rows[:, 1:].T
+
+
+def check_case(c, ll, g):
+    cmp_ = c["compared"]
+    assert cmp_.mean() >= 0.75
+    gn = np.abs(c["g_fd"]).max(axis=0)
+    err = np.abs(g - c["g_fd"]).max(axis=0)
+    bound = REL * gn + c["e_fd"]
+    print("max err / bound over the compared:", np.max(err[cmp_] / np.maximum(bound[cmp_], 1e-300)),
+          "max err / |g|:", np.max(err[cmp_] / np.maximum(gn[cmp_], 1e-300)))
+    assert np.all(err[cmp_] <= bound[cmp_]), (err[cmp_] / gn[cmp_]).max()
+    zero = c["g_fd"] == 0.0
+    assert np.all(g[zero & cmp_[None, :]] == 0.0)
+    fin = np.isfinite(c["loglik_truth"])
+    den = np.maximum(np.abs(c["loglik_truth"][fin]), 1e-300)
+    assert np.all(np.abs(ll[fin] - c["loglik_truth"][fin]) / den <= REL)
+
+
+@pytest.mark.parametrize("name", ["B", "E"])
+def test_host_gradient_matches_truth_differences(harness, tmp_path, name):
+    c = MG.load_cases()[name]
+    ll, g = run_host(harness, tmp_path, c["Y"], c["maturities"], c["Theta"], c["T_use"])
+    check_case(c, ll, g)
+
+
+def test_host_chain_rule(harness, tmp_path):
+    """grad(space 0, θ) = grad(space 1, θ_c) · dθ_c/dθ: θ_c for the exp entries, (1 − θ_c²)/2 for the Φ diagonal."""
+    from yfm_amd import KIND_DNS
+    from yfm_amd.params import transform_params
+    c = MG.load_cases()["E"]
+    Th = c["Theta"]
+    Tc = np.stack([transform_params(KIND_DNS, Th[:, b]) for b in range(Th.shape[1])], axis=1)
+    _, g0 = run_host(harness, tmp_path, c["Y"], c["maturities"], Th, c["T_use"], 0)
+    _, g1 = run_host(harness, tmp_path, c["Y"], c["maturities"], Tc, c["T_use"], 1)
+    f = np.ones_like(Tc)
+    for i in (1, 2, 4, 7):
+        f[i] = Tc[i]
+    for i in (11, 15, 19):
+        f[i] = (1.0 - Tc[i] ** 2) / 2.0
+    assert np.all(np.abs(g0 - g1 * f).max(axis=0) <= REL * np.abs(g0).max(axis=0))

@@ -55,7 +55,7 @@ using yfm::DevBuf;
 // Per-launch device work buffers.  A context owns one; the estimation driver adds one per extra
 // concurrent stream (launches in flight on different streams must not share them).
 struct yfm::Workspace {
-  DevBuf flags;       // 2 banks × kFlagsPerBank unsigned int: n_init_throw, n_neg_inf, deferral list length, n_deferred, steady wave-steps
+  DevBuf flags;       // 2 banks × kFlagsPerBank unsigned int: n_init_throw, n_neg_inf, deferral list length, n_deferred, steady wave-steps, n_grad_unavailable
   int bank = 0;       // the bank of the last launch (the other one is zeroed by that launch's first kernel)
   bool bank_dirty = false;        // the last launch failed: its zeroing of the other bank may not have been enqueued
   hipStream_t last_stream = nullptr;  // the stream of the last launch (compared, never used: it may be gone)
@@ -63,6 +63,7 @@ struct yfm::Workspace {
   DevBuf scratch_dd;  // TVλ double-double records (YFM_PREC_CERTIFIED)
   DevBuf defer;       // candidates handed from the FP64 fixed-loading kernels to the dd kernel
   DevBuf scratch_fd;  // their double-double records (yfm_fixedz_dd.hip)
+  DevBuf grad;        // P×B gradient staging of the host-pointer gradient call (yfm_loglik_grad_batch)
   // allocate and zero the two counter banks
   hipError_t init() {
     const size_t nb = 2 * yfm::kFlagsPerBank * sizeof(unsigned int);
@@ -405,6 +406,45 @@ int launch(yfm_ctx* ctx, const Launch& q, yfm::Workspace* ws = nullptr) {
   return YFM_OK;
 }
 
+// The gradient entry points' model check: the tangent kernel is built for DNS with N ≤ grad_max_n() only.
+int check_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
+  if (state_dim(kind) >= 0 && kind != YFM_MODEL_DNS)
+    return set_error(YFM_EUNSUPPORTED, "log-likelihood gradients are built for YFM_MODEL_DNS only (model_kind %d)", kind);
+  if (int r = check_batch(ctx, kind, space, P, B)) return r;
+  if (ctx->N > yfm::grad_max_n())
+    return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the gradient kernel's %d", ctx->N, yfm::grad_max_n());
+  return YFM_OK;
+}
+
+// The loglik launch q on the context's own workspace, then the tangent kernel on the same stream: it reads the
+// logliks q.out and that launch's deferral list and adds n_grad_unavailable to its counter bank.
+int launch_grad(yfm_ctx* ctx, const Launch& q, double* d_grad) {
+  if (int r = launch(ctx, q)) return r;
+  if (q.B == 0) return YFM_OK;
+  yfm::Workspace& w = ctx->own;
+  yfm::LaunchArgs a{};
+  a.theta = q.theta;
+  a.P = q.P;
+  a.B = q.B;
+  a.space = q.space;
+  a.panel = static_cast<const double*>(ctx->panel.p);
+  a.T = ctx->T;
+  a.N = ctx->N;
+  a.np = ctx->np;
+  a.ldp = ctx->ldp;
+  a.mats = static_cast<const double*>(ctx->mats.p);
+  a.T_use = q.T_use;
+  a.flags = w.bank_ptr(w.bank);  // the bank of the loglik launch just enqueued
+  a.defer_list = static_cast<int*>(w.defer.p);
+  a.stream = q.stream;
+  const hipError_t e = yfm::launch_dns_grad(a, q.out, d_grad);
+  if (e != hipSuccess) {
+    w.bank_dirty = true;
+    return set_error(YFM_EHIP, "gradient kernel launch: %s", hipGetErrorString(e));
+  }
+  return YFM_OK;
+}
+
 // The launch of a host-pointer call: θ (and T_use) uploaded into the context's staging buffers on its stream,
 // the logliks to go to ctx->out.
 int stage_inputs(yfm_ctx* ctx, int kind, int space, const double* theta, int P, int B, const int* T_use, Launch& q) {
@@ -660,6 +700,43 @@ int yfm_loglik_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const
   if (B > 0 && (!d_theta || !d_loglik_out)) return set_error(YFM_EINVAL, "null d_theta or d_loglik_out");
   return launch(ctx, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
                                    static_cast<hipStream_t>(hip_stream)));
+}
+
+int yfm_loglik_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                          const int* T_use, double* loglik_out, double* grad_out) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_grad(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !loglik_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loglik_out or grad_out");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  const size_t gb = sizeof(double) * (size_t)P * (size_t)(B > 0 ? B : 1);
+  YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
+  if (int r = launch_grad(ctx, q, static_cast<double*>(ctx->own.grad.p))) return r;
+  if (B > 0) {
+    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, ctx->own.grad.p, sizeof(double) * (size_t)P * B, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+int yfm_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
+                                 const int* d_T_use, double* d_loglik_out, double* d_grad_out, void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_grad(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_loglik_out || !d_grad_out))
+    return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_grad_out");
+  return launch_grad(ctx, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
+                                        static_cast<hipStream_t>(hip_stream)), d_grad_out);
+}
+
+int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n) {
+  unsigned int h[yfm::kFlagsPerBank];
+  if (int r = read_flags(ctx, h)) return r;
+  if (n) *n = h[5];
+  return YFM_OK;
 }
 
 int yfm_filter_states(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,

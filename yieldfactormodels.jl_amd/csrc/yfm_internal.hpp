@@ -66,6 +66,11 @@ hipError_t launch_fixedz_group(int kind, const LaunchArgs& a);
 // (yfm_fixedz_dd.hip): per-candidate dd records of fixedz_dd_scratch_bytes(kind, B) bytes
 size_t fixedz_dd_scratch_bytes(int kind, int B);
 hipError_t launch_fixedz_dd(int kind, const LaunchArgs& a, double* rec);
+// DNS loglik gradient (yfm_grad.hip), enqueued after the loglik launch whose counters a.flags and deferral list
+// a.defer_list it reads: ∂loglik/∂θ into grad_out (P×B), NaN where ll[b] is not finite or b was deferred
+// (counted in a.flags[5]).  grad_max_n: the largest N of its lane mapping.
+int grad_max_n();
+hipError_t launch_dns_grad(const LaunchArgs& a, const double* ll, double* grad_out);
 // TVλ EKF kernel (yfm_tvl.hip): lanes per filter for a batch, largest N, launcher.  `share`: launches of this
 // size the caller runs concurrently on the device (the estimation driver's chain groups; 1 otherwise)
 int tvl_lanes_for(int B, int N, int share = 1);

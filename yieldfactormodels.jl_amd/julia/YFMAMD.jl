@@ -72,6 +72,20 @@ function loglik_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space =
     out                                        # +loglik per column; -Inf / NaN as documented in yfm.h
 end
 
+"Batched loglik and its gradient (DNS, N ≤ 64): (ll[B], grad[P, B]), grad[:, b] = ∂(+loglik)/∂Θ[:, b] in `space` —
+what estimate!'s TwiceDifferentiable(...; autodiff=:forward) evaluates (optimization.jl:367), with get_loss's sign.
+NaN gradient columns where ll is -Inf / NaN or the candidate ran on the double-double path (yfm.h)."
+function loglik_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,
+                           T_use::Union{Nothing,Vector{Cint}} = nothing)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    ll, grad = Vector{Float64}(undef, B), Matrix{Float64}(undef, P, B)
+    GC.@preserve Θ ll grad T_use check(@ccall LIB.yfm_loglik_grad_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, ll::Ptr{Cdouble},
+        grad::Ptr{Cdouble})::Cint)
+    ll, grad
+end
+
 "Batched predict (filter.jl:250-282) on hcat(data[:, 1:T_use[b]], NaN × (horizon−1)); arrays get a trailing batch axis."
 function predict_batch(model, data::Matrix{Float64}, Θc::Matrix{Float64}; horizon::Integer = 1,
                        T_use::Union{Nothing,Vector{Cint}} = nothing)

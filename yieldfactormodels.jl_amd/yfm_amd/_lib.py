@@ -48,9 +48,14 @@ SIGNATURES = {
     "yfm_get_precision": (ctypes.c_int, [_V]),
     "yfm_loss_array": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, ctypes.c_int,
                                       _D]),
+    "yfm_loglik_grad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D,
+                                             _D]),
+    "yfm_loglik_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int,
+                                                    _V, _V, _V, _V]),
+    "yfm_last_batch_grad_unavailable": (ctypes.c_int, [_V, _LL]),
 }
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 
 # precision modes (include/yfm.h: enum yfm_precision)
 PREC_CERTIFIED, PREC_FP64 = 0, 1

@@ -110,6 +110,27 @@ class Engine:
                                                     ctypes.c_void_p(d_out),
                                                     ctypes.c_void_p(stream) if stream else None))
 
+    def loglik_grad(self, kind: int, theta, space: int = 0, T_use=None):
+        """(ll[B], grad[P, B]): the logliks of :meth:`loglik` and ∂(+loglik)/∂θ in the space passed
+        (include/yfm.h yfm_loglik_grad_batch; DNS with N ≤ 64).  A candidate's gradient is NaN where its loglik
+        is −Inf or NaN, and where it was evaluated on the double-double path (:meth:`last_grad_unavailable`)."""
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        ll = np.empty(B, dtype=np.float64)
+        grad = np.empty((P, B), dtype=np.float64, order="F")
+        _lib.check(self.lib.yfm_loglik_grad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                                  _lib.iptr(self._tuse(T_use, B)), _lib.dptr(ll), _lib.dptr(grad)))
+        return ll, grad
+
+    def loglik_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int, space: int = 0,
+                           d_T_use: int | None = None, stream: int | None = None) -> None:
+        """Device-pointer variant of :meth:`loglik_grad` (raw addresses; d_grad: P×B column-major); asynchronous
+        on ``stream``."""
+        _lib.check(self.lib.yfm_loglik_grad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
+                                                         ctypes.c_void_p(d_T_use) if d_T_use else None,
+                                                         ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
+                                                         ctypes.c_void_p(stream) if stream else None))
+
     def filter_states(self, kind: int, theta, space: int = 0, T_use=None):
         """Returns (loglik[B], beta[M, T-1, B], P[M, M, T-1, B]) — a_{t+1|t}, P_{t+1|t} after each filter! call."""
         Th = np.asfortranarray(np.atleast_2d(np.asarray(theta, dtype=np.float64).T).T)
@@ -201,6 +222,13 @@ class Engine:
         n = ctypes.c_longlong(0)
         _lib.check(self.lib.yfm_last_batch_deferred(self.ctx, ctypes.byref(n)))
         return n.value
+
+    def last_grad_unavailable(self) -> int:
+        """Candidates of the last gradient batch whose loglik came from the double-double path and whose
+        gradient is therefore NaN (include/yfm.h yfm_last_batch_grad_unavailable)."""
+        n = ctypes.c_longlong(0)
+        _lib.check(self.lib.yfm_last_batch_grad_unavailable(self.ctx, ctypes.byref(n)))
+        return int(n.value)
 
     def last_steady(self) -> int:
         """Wave-steps (64 filter steps each) of the last batch that ran the DNS kernel's frozen-covariance

@@ -21,6 +21,9 @@ reference                                 here
 forecast blocks forecasting.jl:236-250      :func:`forecast_batch`
 ``estimate_steps!`` optimization.jl:137-312 :func:`estimate_steps_` (+ batched
                                             :func:`estimate_batch`)
+``estimate!`` optimization.jl:329-410       :func:`estimate_` (+ batched
+                                            :func:`estimate_lbfgs_batch`; gradient:
+                                            :func:`compute_loss_grad_batch`)
 =======================================  =================================================
 
 plus the batched forms the device boundary exists for: :func:`get_loss_batch` and
@@ -40,6 +43,11 @@ import numpy as np
 
 from . import params as _p
 from .engine import get_engine
+
+
+class EstimationError(RuntimeError):
+    """estimate_steps! rethrows from the first group iteration (optimization.jl:249-253); estimate! throws
+    where compute_loss does."""
 
 
 class SingularException(ArithmeticError):
@@ -234,10 +242,6 @@ def forecast_batch(model: AbstractKalmanModel, data, Theta, T_use, horizon: int,
     return eng.forecast(model.kind, Theta, space=space, T_use=T_use, horizon=horizon)
 
 
-class EstimationError(RuntimeError):
-    """estimate_steps! rethrows from the first group iteration (optimization.jl:249-253)."""
-
-
 def estimate_steps_(model: AbstractKalmanModel, data, all_params, param_groups=None, max_group_iters: int = 10,
                     tol: float = 1e-8, printing: bool = False, iterations: int = 500):
     """estimate_steps! (optimization.jl:137-312) for a Kalman model: all_params (P×n, constrained; Kalman
@@ -265,3 +269,51 @@ def estimate_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, space: 
     eng = _engine(model, data)
     return eng.estimate(model.kind, Theta0, space=space, T_use=T_use, iterations=iterations, g_tol=g_tol,
                         max_group_iters=max_group_iters, tol=tol)
+
+
+def compute_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
+    """Batched compute_loss with its gradient — what estimate!'s TwiceDifferentiable(...; autodiff=:forward)
+    evaluates (optimization.jl:367): (−loglik[B], −∂loglik/∂θ[P, B]) for every unconstrained θ_b, the
+    reference's loss sign.  DNS with N ≤ 64; NaN gradient columns as in :meth:`Engine.loglik_grad`."""
+    ll, g = _engine(model, data).loglik_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
+    return -ll, -g
+
+
+def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 1, **opts) -> dict:
+    """One L-BFGS chain of estimate! (optimization.jl:329-410) per column of Θ₀ (P×R; constrained by default, as
+    all_params), all chains advancing in lockstep with one gradient launch per round (:mod:`yfm_amd.lbfgs`;
+    `opts`: iterations, g_tol, f_abstol, allow_f_increases).  Returns the per-start arrays: theta_c (P×R),
+    p (P×R unconstrained optimum), init_c (P×R: the start, constrained), ll (R), ll0 (R: the loglik at the
+    start), status (R: lbfgs status; 0 = converged), iterations (R), n_evals, rounds."""
+    from . import lbfgs as _lbfgs
+    Th = np.asarray(Theta0, dtype=np.float64)
+    if Th.ndim == 1:
+        Th = Th[:, None]
+    X0 = Th if space == _p.SPACE_UNCONSTRAINED else _p.untransform_params(model.kind, Th)
+    ll0 = -compute_loss_grad_batch(model, data, X0)[0]
+    r = _lbfgs.minimize_batch(lambda X: compute_loss_grad_batch(model, data, X), X0, **opts)
+    return dict(theta_c=np.asfortranarray(_p.transform_params(model.kind, r["x"])), p=r["x"],
+                init_c=np.asfortranarray(_p.transform_params(model.kind, X0)), ll=-r["f"], ll0=ll0,
+                status=r["status"], iterations=r["iterations"], n_evals=r["n_evals"] + X0.shape[1],
+                rounds=r["rounds"] + 1)
+
+
+def estimate_(model: AbstractKalmanModel, data, all_params, printing: bool = False, **opts):
+    """estimate! (optimization.jl:329-410): multistart L-BFGS from the columns of all_params (P×n, constrained)
+    → (init_params, ll, best_params, ir) of the start with the largest ll, both parameter vectors constrained,
+    ir = 0 if that chain converged else 1.  Raises :class:`EstimationError` where the reference throws:
+    compute_loss throws at a start (singular initialize_filter), or no start ends with ll > −Inf (the
+    reference then indexes its results with best_j = 0)."""
+    A = np.asarray(all_params, dtype=np.float64)
+    if A.ndim == 1:
+        A = A[:, None]
+    r = estimate_lbfgs_batch(model, data, A, space=_p.SPACE_CONSTRAINED, **opts)
+    if np.isnan(r["ll0"]).any():
+        raise EstimationError("compute_loss threw at a starting point (singular initialize_filter)")
+    ll = np.where(np.isnan(r["ll"]), -np.inf, r["ll"])
+    if not (ll > -np.inf).any():
+        raise EstimationError("no starting point reached a finite log-likelihood")
+    j = int(np.argmax(ll))  # the first of equal maxima, as the reference's `ll > best_ll`
+    if printing:
+        print(f"✓ Best LL = {r['ll'][j]} from starting point {j + 1}")
+    return r["init_c"][:, j].copy(), float(r["ll"][j]), r["theta_c"][:, j].copy(), 0 if r["status"][j] == 0 else 1

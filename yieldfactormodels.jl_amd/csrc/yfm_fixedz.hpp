@@ -612,4 +612,29 @@ struct FixedZFilter {
   }
 };
 
+// ---- DNS Z'ỹ with the last maturity eliminated (NP = 30: 7 MFMA k-steps instead of 8) ----
+// The panel columns are centred, Σᵢ ỹᵢ = 0, so for every loading column
+//     Z'ỹ = Σ_{i<N−1} (Zᵢ − Z_{N−1}) ỹᵢ  +  Z_{N−1} Σᵢ ỹᵢ,
+// and the last term is Z_{N−1} times the centring's rounding residual: the same class of term the dropped
+// constant loading column already neglects.  N − 1 ≤ 29 differenced loadings: slots 0..27 are the 7 k-steps'
+// MFMA fragments, slot 28 (non-zero only at N = 30) is one fma per loading column and step on the VALU.
+// Shared by the per-lane kernel (yfm_kernels.hip) and the two-wave kernel (yfm_split.hip), which must agree
+// bit for bit.  YFM_DNS_KTRIM=0 selects the 8-k-step instantiations on the original loadings.
+constexpr int kTrimNP = 30;    // the panel width that gains a k-step
+constexpr int kTrimSlot = 28;  // the maturity slot left to the VALU (16-byte aligned in a staged column)
+constexpr bool ktrim_applies(int NP, int M) { return NP == kTrimNP && M == 3; }
+constexpr int ktrim_nk(int NP, bool trim) { return trim ? (kTrimSlot / 4) : (NP + 3) / 4; }
+
+// the differenced loading of maturity slot i (N is wave-uniform): zero from the eliminated maturity on
+__device__ __forceinline__ double ktrim_diff(double z, double z_last, int i, int N) {
+  return (i < N - 1) ? z - z_last : 0.0;
+}
+
+// z̃_c = (the MFMA's sum over slots 0..27) + Zd_c[slot 28] · ỹ₂₈; zx = (the NZ sums, ỹ₂₈), zd is zero unless N = 30
+template <int NZ>
+__device__ __forceinline__ void ktrim_leftover(const double (&zd)[NZ], const double (&zx)[NZ + 1], double (&z)[NZ]) {
+#pragma unroll
+  for (int c = 0; c < NZ; ++c) z[c] = fma(zd[c], zx[NZ], zx[c]);
+}
+
 }  // namespace yfm

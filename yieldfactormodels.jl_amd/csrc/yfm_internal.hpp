@@ -56,6 +56,8 @@ hipError_t launch_fixedz(int kind, const LaunchArgs& a);
 // DNS with N ≤ 32: each filter split over a covariance wave and a mean wave (yfm_split.hip)
 bool dns_split_supported(int np);
 hipError_t launch_dns_split(const LaunchArgs& a);
+// DNS at NP = 30 on 7 MFMA k-steps (both kernels above): 1 unless YFM_DNS_KTRIM=0
+int ktrim_enabled();
 // per-candidate initial-state records of the per-lane kernel (GNS5: fixedz_init_kernel), bytes
 size_t fixedz_scratch_bytes(int kind, int B);
 // fixed-loading models with N beyond the per-lane kernel (yfm_group.hip): filter per lane group

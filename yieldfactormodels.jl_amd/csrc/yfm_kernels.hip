@@ -289,8 +289,16 @@ typedef double yfm_double4 __attribute__((ext_vector_type(4)));
 // computed one step ahead, inside the same basic block as the update.
 // A wave-uniform fast path (no NaN column, every lane active, every lane collapsed,
 // t ≥ 1) carries no per-lane masking; everything else takes the general path.
-template <int NP, int M, int LEAD, bool RECORD, bool STEADY_ = false, bool SPLIT_FORM = false>
-__global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
+//
+// DNS at NP = 30 (KTRIM_, the default; ktrim_* in yfm_fixedz.hpp): Z'ỹ runs 7 k-steps on the loadings
+// differenced against the last maturity, Σ_{i<N−1} (Zᵢ − Z_{N−1}) ỹᵢ — slots 0..27 on the MFMA, slot 28 (non-zero
+// only at N = 30) as one fma per loading column in the step.  What is neglected is Z_{N−1}·Σᵢỹᵢ, with Σᵢỹᵢ the
+// centring's rounding residual: the same class of term the dropped constant column neglects.  Zc, G = Z'Z, R,
+// log det G and the deferral decision come from the original loadings.  One body for every N ≤ 30 (N = 25..29
+// simply have zero in slot 28); the 8-k-step code is the KTRIM_ = false instantiation (YFM_DNS_KTRIM=0), which
+// carries a seventh template argument so that the default keeps its kernel name.
+template <int NP, int M, int LEAD, bool RECORD, bool STEADY_, bool SPLIT_FORM, bool KTRIM_>
+__device__ __forceinline__ void fixedz_loglik_body(
     const double* __restrict__ theta, int P, int B, int space, const double* __restrict__ panel, int T, int N,
     const double* __restrict__ mats, const int* __restrict__ T_use, double* __restrict__ out,
     unsigned int* __restrict__ flags, double* __restrict__ rec_beta, double* __restrict__ rec_P, int horizon,
@@ -310,7 +318,8 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
   constexpr int PER = (CH + kBlock - 1) / kBlock;
   constexpr int NZ = M - 1;                   // non-constant loading columns
   constexpr bool USE_MFMA = (NZ == 2 || NZ == 4) && (NP <= 32);  // fragments + LDS scratch budget
-  constexpr int NK = (NP + 3) / 4;            // MFMA k-steps (4 maturities each)
+  constexpr bool KTRIM = KTRIM_ && USE_MFMA && ktrim_applies(NP, M);  // the last maturity eliminated (header)
+  constexpr int NK = ktrim_nk(NP, KTRIM);     // MFMA k-steps (4 maturities each)
   constexpr int NRT = 64 * NZ / 16;           // MFMA row tiles per wave (16 (cand, col) pairs each)
   // row tiles accumulated at once (bounds live accumulators).  DNS: two groups of 4, so the first group's
   // z̃ stores overlap the second group's MFMAs (8: 0.2173 → 4: 0.2165 ms at config 2, 2: 0.2197 ms — two
@@ -456,11 +465,24 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
   // instead of four 8-byte ones, and still one candidate's z̃ in consecutive doubles for the step reads
   constexpr bool SIGMA = USE_MFMA && !ZB && !(kMfma4 && NZ == 4);
   // IL: the row tiles in three groups (4, 2, 2), each group's stores interleaved with the next group's MFMAs
-  // (NP 29–32: one store per k-step)
-  constexpr bool IL = SIGMA && NRT == 2 * RGN && NK == 2 * RGN;
+  // (NP 29–32: one store per k-step; with 7 k-steps the last k-step takes the store left over)
+  constexpr bool IL = SIGMA && NRT == 2 * RGN && (NK == 2 * RGN || NK == 2 * RGN - 1);
   constexpr bool IL5 = ZB && NK == NRTA;  // GNS5: the same across step pairs
   auto sigma = [](int i) { return SIGMA ? 4 * (i & 3) + (i >> 2) : i; };
   double Af[USE_MFMA ? NRTA : 1][USE_MFMA ? NK : 1];
+  // KTRIM: the loadings of the last maturity (N is a runtime value: a select chain, no indexed register array)
+  // and this lane's two differenced loadings of slot 28, which the step adds on the VALU
+  double z_last[KTRIM ? NZ : 1], zd28[KTRIM ? NZ : 1];
+  if constexpr (KTRIM) {
+#pragma unroll
+    for (int c = 0; c < NZ; ++c) {
+      double zl = 0.0;
+#pragma unroll
+      for (int i = 0; i < NP; ++i) zl = (i == N - 1) ? Zc[c][i] : zl;
+      z_last[c] = zl;
+      zd28[c] = ktrim_diff(Zc[c][kTrimSlot], zl, kTrimSlot, N);
+    }
+  }
   double rlam[LEAD];  // 1/λ_l (z-basis fragments)
 #pragma unroll
   for (int l = 0; l < LEAD; ++l) rlam[l] = 1.0 / (1e-2 + exp(p.gam[l]));
@@ -489,7 +511,12 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
 #pragma unroll
           for (int c = 0; c < NZ; ++c)
 #pragma unroll
-            for (int m = 0; m < ZS; ++m) st[(cl * NZ + c) * ZS + m] = (m < NP) ? Zc[c][m] : 0.0;
+            for (int m = 0; m < ZS; ++m) {
+              if constexpr (KTRIM)  // (ZS − 1 = 28 slots are read; m < NP throughout)
+                st[(cl * NZ + c) * ZS + m] = ktrim_diff(Zc[c][m], z_last[c], m, N);
+              else
+                st[(cl * NZ + c) * ZS + m] = (m < NP) ? Zc[c][m] : 0.0;
+            }
         }
       }
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0)
@@ -732,8 +759,14 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
         }
         if constexpr (IL) {
           // three groups of 4, 2, 2 tiles: the first group's 8 stores during the second group's MFMAs, the
-          // second's 4 during the third's, so only the last 2 tiles' 4 stores trail the block
+          // second's 4 during the third's, so only the last 2 tiles' 4 stores trail the block.  Store s of a group
+          // (tile s >> 1, half s & 1) goes after a k-step of the next group: the first group's store s after
+          // k-step s, the second's after k-step 2s + 1 — with 7 k-steps the last k-step takes the store that
+          // would have followed the eighth (two of the first group's, the second group's fourth)
           constexpr int H = RGN / 2;
+          constexpr int NS1 = 2 * RGN, NS2 = 2 * H;  // 16-byte stores of the first and the second group
+          auto last1 = [](int kk) { return kk == NK - 1 ? NS1 : kk + 1; };  // first-group stores issued by k-step kk
+          auto at2 = [](int s) { return 2 * s + 1 < NK - 1 ? 2 * s + 1 : NK - 1; };  // k-step of second-group store s
           yfm_double4 a1[RGN], a2[H], a3[H];
 #pragma unroll
           for (int r = 0; r < RGN; ++r) a1[r] = yfm_double4{0.0, 0.0, 0.0, 0.0};
@@ -749,31 +782,40 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
 #pragma unroll
             for (int r = 0; r < H; ++r)
               a2[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[RGN + r][kk], bvk[kk], a2[r], 0, 0, 0);
-            const int r1 = kk >> 1, h = kk & 1;
-            double* d = scr + (lane & 15) * SS + 16 * r1 + 4 * (lane >> 4) + 2 * h;
-            *reinterpret_cast<double2*>(d) = make_double2(a1[r1][2 * h], a1[r1][2 * h + 1]);
+#pragma unroll
+            for (int s = kk; s < last1(kk); ++s) {
+              const int r1 = s >> 1, h = s & 1;
+              double* d = scr + (lane & 15) * SS + 16 * r1 + 4 * (lane >> 4) + 2 * h;
+              *reinterpret_cast<double2*>(d) = make_double2(a1[r1][2 * h], a1[r1][2 * h + 1]);
+            }
           }
 #pragma unroll
           for (int kk = 0; kk < NK; ++kk) {
 #pragma unroll
             for (int r = 0; r < H; ++r)
               a3[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[RGN + H + r][kk], bvk[kk], a3[r], 0, 0, 0);
-            if (kk & 1) {
-              const int r2 = kk >> 2, h = (kk >> 1) & 1;
-              double* d = scr + (lane & 15) * SS + 16 * (RGN + r2) + 4 * (lane >> 4) + 2 * h;
-              *reinterpret_cast<double2*>(d) = make_double2(a2[r2][2 * h], a2[r2][2 * h + 1]);
+#pragma unroll
+            for (int s = 0; s < NS2; ++s) {
+              if (at2(s) == kk) {
+                const int r2 = s >> 1, h = s & 1;
+                double* d = scr + (lane & 15) * SS + 16 * (RGN + r2) + 4 * (lane >> 4) + 2 * h;
+                *reinterpret_cast<double2*>(d) = make_double2(a2[r2][2 * h], a2[r2][2 * h + 1]);
+              }
             }
           }
           __builtin_amdgcn_sched_group_barrier(0x008, RGN * NK, 0);  // the first group's MFMAs
 #pragma unroll
           for (int kk = 0; kk < NK; ++kk) {
             __builtin_amdgcn_sched_group_barrier(0x008, H, 0);  // a k-step of the second group
-            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // one store of the first
+#pragma unroll
+            for (int s = kk; s < last1(kk); ++s) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // one store of the first
           }
 #pragma unroll
           for (int kk = 0; kk < NK; ++kk) {
             __builtin_amdgcn_sched_group_barrier(0x008, H, 0);  // a k-step of the third group
-            if (kk & 1) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // one store of the second
+#pragma unroll
+            for (int s = 0; s < NS2; ++s)
+              if (at2(s) == kk) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // one store of the second
           }
 #pragma unroll
           for (int r = 0; r < H; ++r) store_tile(scr, RGN + H + r, a3[r]);
@@ -811,7 +853,19 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
         }
       }
       // step operands for tt are read one step ahead (hides the LDS latency at 1 wave/SIMD)
-      auto read_z = [&](int tt, double (&z)[NZ]) {  // this lane's pairs NZ·lane .. NZ·lane + NZ − 1
+      // (KTRIM: the operands carry ỹ₂₈ of the step's column in element NZ — a wave-uniform 16-byte read — and
+      // z_of adds the leftover term when the step consumes them)
+      constexpr int NZX = NZ + (KTRIM ? 1 : 0);
+      auto z_of = [&](const double (&zx)[NZX], double (&z)[NZ]) {
+        if constexpr (KTRIM) {
+          ktrim_leftover<NZ>(zd28, zx, z);
+        } else {
+#pragma unroll
+          for (int j = 0; j < NZ; ++j) z[j] = zx[j];
+        }
+      };
+      auto read_z = [&](int tt, double (&z)[NZX]) {  // this lane's pairs NZ·lane .. NZ·lane + NZ − 1
+        if constexpr (KTRIM) z[NZ] = reinterpret_cast<const double2*>(cb + tt * LDP + kTrimSlot)->x;
         const double* sp = scr + tt * SS + NZ * lane;
 #pragma unroll
         for (int j = 0; j < NZ; j += 2) {
@@ -825,31 +879,35 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
           }
         }
       };
-      double zc[NZ];
+      double zc[NZX];
       read_z(0, zc);
       double2 yb = *reinterpret_cast<const double2*>(cb + NP);
       double2 meta = *reinterpret_cast<const double2*>(cb + NP + 2);
       // two steps per trip with the operand buffers swapped by name (no register copies)
-      double zn[NZ];
+      double zn[NZX];
       double2 ybn, metan;
-      auto half = [&](int tt, const double (&zc_)[NZ], double2 yb_, double2 meta_, double (&zn_)[NZ], double2& ybn_,
+      auto half = [&](int tt, const double (&zc_)[NZX], double2 yb_, double2 meta_, double (&zn_)[NZX], double2& ybn_,
                       double2& metan_) {
         const int t = t0 + tt;
         const int tn = min(tt + 1, TB - 1);
         read_z(tn, zn_);
         ybn_ = *reinterpret_cast<const double2*>(cb + tn * LDP + NP);
         metan_ = *reinterpret_cast<const double2*>(cb + tn * LDP + NP + 2);
-        do_step(t, zc_, yb_, meta_);
+        double z[NZ];
+        z_of(zc_, z);
+        do_step(t, z, yb_, meta_);
         record(t);
         if ((t + 1) % TC == 0) rot_t = t;  // the chunk rotation, deferred to the next block's start
       };
       // the mean update only, with the cached factors of S (bitwise the full step's values for a frozen lane);
       // operands read one step ahead as in `half`
-      auto shalf = [&](int tt, const double (&zc_)[NZ], double2 yb_, double (&zn_)[NZ], double2& ybn_) {
+      auto shalf = [&](int tt, const double (&zc_)[NZX], double2 yb_, double (&zn_)[NZX], double2& ybn_) {
         const int tn = min(tt + 1, TB - 1);
         read_z(tn, zn_);
         ybn_ = *reinterpret_cast<const double2*>(cb + tn * LDP + NP);
-        f.steady_step(zc_, yb_);
+        double z[NZ];
+        z_of(zc_, z);
+        f.steady_step(z, yb_);
         if ((t0 + tt + 1) % TC == 0) rot_t = t0 + tt;
       };
       if constexpr (STEADY) {
@@ -858,10 +916,10 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
             // a whole block: the 16 steps unrolled into one basic block (no loop control or operand copies;
             // the chunk rotation, which only the block's last step can trigger, after it): 0.2114 → 0.2042 ms
             // at config 2, bitwise the same logliks (profiles/r4/ab16/)
-            double zq[2][NZ];
+            double zq[2][NZX];
             double2 ybq[2];
 #pragma unroll
-            for (int j = 0; j < NZ; ++j) zq[0][j] = zc[j];
+            for (int j = 0; j < NZX; ++j) zq[0][j] = zc[j];
             ybq[0] = yb;
 #pragma unroll
             for (int u = 0; u < TB; ++u) {
@@ -869,7 +927,9 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
               const int tn = min(u + 1, TB - 1);
               read_z(tn, zq[nx]);
               ybq[nx] = *reinterpret_cast<const double2*>(cb + tn * LDP + NP);
-              f.steady_step(zq[cur], ybq[cur]);
+              double z[NZ];
+              z_of(zq[cur], z);
+              f.steady_step(z, ybq[cur]);
             }
             rot_t = ((t0 + TB) % TC == 0) ? t0 + TB - 1 : -1;  // at the next block's start
           } else {
@@ -975,6 +1035,32 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
   out[b] = ll;
 }
 
+// The kernels: the default (KTRIM where it applies) under the six-argument name that committed profiles and
+// bench.py know, and the untrimmed DNS NP = 30 variant with the seventh argument spelled out.
+template <int NP, int M, int LEAD, bool RECORD, bool STEADY_ = false, bool SPLIT_FORM = false>
+__global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
+    const double* __restrict__ theta, int P, int B, int space, const double* __restrict__ panel, int T, int N,
+    const double* __restrict__ mats, const int* __restrict__ T_use, double* __restrict__ out,
+    unsigned int* __restrict__ flags, double* __restrict__ rec_beta, double* __restrict__ rec_P, int horizon,
+    int rec_len, int* __restrict__ defer_list, int* __restrict__ defer_count, const double* __restrict__ init_rec,
+    unsigned int* __restrict__ flags_next, int steady) {
+  fixedz_loglik_body<NP, M, LEAD, RECORD, STEADY_, SPLIT_FORM, true>(
+      theta, P, B, space, panel, T, N, mats, T_use, out, flags, rec_beta, rec_P, horizon, rec_len, defer_list,
+      defer_count, init_rec, flags_next, steady);
+}
+
+template <int NP, int M, int LEAD, bool RECORD, bool STEADY_, bool SPLIT_FORM, bool KTRIM_>
+__global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
+    const double* __restrict__ theta, int P, int B, int space, const double* __restrict__ panel, int T, int N,
+    const double* __restrict__ mats, const int* __restrict__ T_use, double* __restrict__ out,
+    unsigned int* __restrict__ flags, double* __restrict__ rec_beta, double* __restrict__ rec_P, int horizon,
+    int rec_len, int* __restrict__ defer_list, int* __restrict__ defer_count, const double* __restrict__ init_rec,
+    unsigned int* __restrict__ flags_next, int steady) {
+  fixedz_loglik_body<NP, M, LEAD, RECORD, STEADY_, SPLIT_FORM, KTRIM_>(
+      theta, P, B, space, panel, T, N, mats, T_use, out, flags, rec_beta, rec_P, horizon, rec_len, defer_list,
+      defer_count, init_rec, flags_next, steady);
+}
+
 }  // namespace yfm
 
 // ------------------------------------------------------------------------------------
@@ -989,6 +1075,13 @@ namespace yfm {
 // the frozen-covariance steady state of the DNS loglik kernel (FixedZFilter): on unless YFM_DNS_STEADY=0
 static int steady_enabled() {
   const char* e = std::getenv("YFM_DNS_STEADY");
+  return (e && e[0] == '0') ? 0 : 1;
+}
+
+// DNS at NP = 30 with the last maturity eliminated (7 MFMA k-steps; ktrim_* in yfm_fixedz.hpp): on unless
+// YFM_DNS_KTRIM=0 (declared in yfm_internal.hpp: the two-wave kernel obeys it too)
+int ktrim_enabled() {
+  const char* e = std::getenv("YFM_DNS_KTRIM");
   return (e && e[0] == '0') ? 0 : 1;
 }
 
@@ -1028,8 +1121,16 @@ static hipError_t launch_fixedz_np(const LaunchArgs& a) {
                          a.space, a.scratch, a.flags_next);
     }
   }
+  // YFM_DNS_KTRIM=0: the 8-k-step instantiations of DNS at NP = 30 (the seven-argument kernels)
+  constexpr bool kTrimmable = ktrim_applies(NP, M) && (NP <= 32);
+  bool untrimmed = false;
+  if constexpr (kTrimmable) untrimmed = !ktrim_enabled();
   if (a.rec_beta) {
-    hipLaunchKernelGGL((fixedz_loglik_kernel<NP, M, LEAD, true>), dim3(grid), dim3(kBlock), 0, a.stream, a.theta, a.P,
+    auto* k = &fixedz_loglik_kernel<NP, M, LEAD, true, false, false>;
+    if constexpr (kTrimmable) {
+      if (untrimmed) k = &fixedz_loglik_kernel<NP, M, LEAD, true, false, false, false>;
+    }
+    hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, a.stream, a.theta, a.P,
                        a.B, a.space, a.panel, a.T, a.N, a.mats, a.T_use, a.out, a.flags, a.rec_beta, a.rec_P,
                        a.horizon, a.rec_len, a.defer_list, a.defer_count, a.scratch, M == 5 ? nullptr : a.flags_next, 0);
   } else {
@@ -1047,6 +1148,11 @@ static hipError_t launch_fixedz_np(const LaunchArgs& a) {
     constexpr bool kSplitForm = (M == 5) && (NP == 30 || NP == 48);
     if constexpr (kSplitForm) {
       if (split_form_enabled()) k = &fixedz_loglik_kernel<NP, M, LEAD, false, false, true>;
+    }
+    if constexpr (kTrimmable) {
+      if (untrimmed)
+        k = (kSteady && on) ? &fixedz_loglik_kernel<NP, M, LEAD, false, kSteady, false, false>
+                            : &fixedz_loglik_kernel<NP, M, LEAD, false, false, false, false>;
     }
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, a.stream, a.theta, a.P, a.B, a.space, a.panel, a.T, a.N,
                        a.mats, a.T_use, a.out, a.flags, nullptr, nullptr, 0, 0, a.defer_list, a.defer_count,

@@ -41,7 +41,9 @@ constexpr int kRec = 13;          // L10 L20 L21, 1/d0..2, P00 P01 P02 P11 P12 P
 
 }  // namespace
 
-template <int NP, bool RECORD>
+// KTRIM_ (NP = 30, the default): the per-lane kernel's 7-k-step Z'ỹ on the differenced loadings, with the same
+// fragments, k-step count and VALU term (ktrim_* in yfm_fixedz.hpp), so the two kernels still agree bit for bit.
+template <int NP, bool RECORD, bool KTRIM_>
 __global__ __launch_bounds__(kSplitBlock, 1) void dns_split_kernel(
     const double* __restrict__ theta, int P, int B, int space, const double* __restrict__ panel, int T, int N,
     const double* __restrict__ mats, const int* __restrict__ T_use, double* __restrict__ out,
@@ -53,7 +55,8 @@ __global__ __launch_bounds__(kSplitBlock, 1) void dns_split_kernel(
   constexpr int LDP = NP + 4;
   constexpr int CH = kSTC * LDP;
   constexpr int PER = (CH + kSplitBlock - 1) / kSplitBlock;
-  constexpr int NK = (NP + 3) / 4;     // MFMA k-steps
+  constexpr bool KTRIM = KTRIM_ && ktrim_applies(NP, M);
+  constexpr int NK = ktrim_nk(NP, KTRIM);  // MFMA k-steps
   constexpr int NRT = 64 * NZ / 16;    // MFMA row tiles per wave
   constexpr int SS = 64 * NZ + 2;      // scratch row stride (doubles)
   constexpr int SCR = kSTB * SS;
@@ -131,7 +134,16 @@ __global__ __launch_bounds__(kSplitBlock, 1) void dns_split_kernel(
   // (candidate p >> 1 of this wave, column p & 1) at maturity 4kk + (l >> 4); staged through the
   // wave's scratch one quarter (16 candidates) at a time, each lane writing its own loadings
   double Af[COV ? 1 : NRT][COV ? 1 : NK];
+  double zd28[NZ] = {0.0, 0.0};  // KTRIM: the differenced loadings of slot 28, added in the step
   if constexpr (!COV) {
+    double zl_s = 0.0, zl_c = 0.0;  // KTRIM: the loadings of the last maturity
+    if constexpr (KTRIM) {
+      loading(max(N - 1, 0), zl_s, zl_c);
+      double zs, zc;
+      loading(kTrimSlot, zs, zc);
+      zd28[0] = ktrim_diff(zs, zl_s, kTrimSlot, N);
+      zd28[1] = ktrim_diff(zc, zl_c, kTrimSlot, N);
+    }
     constexpr int ZS = 4 * NK + 1;
     constexpr int QT = NRT / 4;
     static_assert(16 * NZ * ZS <= SCR, "staging fits the scratch");
@@ -144,6 +156,10 @@ __global__ __launch_bounds__(kSplitBlock, 1) void dns_split_kernel(
         for (int m = 0; m < ZS; ++m) {
           double zs, zc;
           loading(m < NP ? m : NP, zs, zc);
+          if constexpr (KTRIM) {
+            zs = ktrim_diff(zs, zl_s, m, N);
+            zc = ktrim_diff(zc, zl_c, m, N);
+          }
           st[(cl * NZ + 0) * ZS + m] = zs;
           st[(cl * NZ + 1) * ZS + m] = zc;
         }
@@ -306,7 +322,11 @@ __global__ __launch_bounds__(kSplitBlock, 1) void dns_split_kernel(
       }
       const double* cb = col_of(t);
       const double2 z2 = *reinterpret_cast<const double2*>(scr + tt * SS + NZ * lane);
-      const double zc[NZ] = {z2.x, z2.y};
+      double zc[NZ] = {z2.x, z2.y};
+      if constexpr (KTRIM) {
+        const double zx[NZ + 1] = {z2.x, z2.y, reinterpret_cast<const double2*>(cb + kTrimSlot)->x};
+        ktrim_leftover<NZ>(zd28, zx, zc);
+      }
       const double2 yb = *reinterpret_cast<const double2*>(cb + NP);
       const double2 meta = *reinterpret_cast<const double2*>(cb + NP + 2);
       const bool fast = (t >= 1) && (meta.x == 0.0) && (t < wave_min_data);
@@ -389,16 +409,16 @@ __global__ __launch_bounds__(kSplitBlock, 1) void dns_split_kernel(
 
 namespace {
 
-template <int NP>
+template <int NP, bool KTRIM = true>
 hipError_t launch_split_np(const LaunchArgs& a) {
   const int interleave = 0;  // wave-to-role layout: covariance waves 0-3, mean waves 4-7 (1: alternating)
   const int grid = (a.B + kSplitPairs * 64 - 1) / (kSplitPairs * 64);
   if (a.rec_beta) {
-    hipLaunchKernelGGL((dns_split_kernel<NP, true>), dim3(grid), dim3(kSplitBlock), 0, a.stream, a.theta, a.P, a.B,
+    hipLaunchKernelGGL((dns_split_kernel<NP, true, KTRIM>), dim3(grid), dim3(kSplitBlock), 0, a.stream, a.theta, a.P, a.B,
                        a.space, a.panel, a.T, a.N, a.mats, a.T_use, a.out, a.flags, a.rec_beta, a.rec_P, a.horizon,
                        a.rec_len, a.defer_list, a.defer_count, interleave, a.flags_next);
   } else {
-    hipLaunchKernelGGL((dns_split_kernel<NP, false>), dim3(grid), dim3(kSplitBlock), 0, a.stream, a.theta, a.P, a.B,
+    hipLaunchKernelGGL((dns_split_kernel<NP, false, KTRIM>), dim3(grid), dim3(kSplitBlock), 0, a.stream, a.theta, a.P, a.B,
                        a.space, a.panel, a.T, a.N, a.mats, a.T_use, a.out, a.flags, nullptr, nullptr, 0, 0,
                        a.defer_list, a.defer_count, interleave, a.flags_next);
   }
@@ -414,7 +434,7 @@ hipError_t launch_dns_split(const LaunchArgs& a) {
     case 8: return launch_split_np<8>(a);
     case 16: return launch_split_np<16>(a);
     case 24: return launch_split_np<24>(a);
-    case 30: return launch_split_np<30>(a);
+    case 30: return ktrim_enabled() ? launch_split_np<30>(a) : launch_split_np<30, false>(a);
     case 32: return launch_split_np<32>(a);
   }
   return hipErrorInvalidValue;

@@ -237,9 +237,7 @@ int tvl_gaps(yfm_ctx* ctx, int L, yfm::TvlGaps& g) {
     g.e = static_cast<const double*>(t.pow.p);
     g.pidx = reinterpret_cast<const int*>(g.e + yfm::kTvlPowGaps);
   }
-  if (const char* ov = std::getenv("YFM_TVL_EXP")) {  // diagnostic: force one exp per maturity
-    if (std::atoi(ov) == 1) g.K = g.Kp = 0;
-  }
+  if (std::atoi(yfm::env_or("YFM_TVL_EXP", "0")) == 1) g.K = g.Kp = 0;  // diagnostic: force one exp per maturity
   return YFM_OK;
 }
 
@@ -327,13 +325,14 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
   hipError_t e;
   if (q.kind == YFM_MODEL_TVL) {
     int lanes = yfm::tvl_lanes_for(B, ctx->N, q.share);
-    if (const char* ov = std::getenv("YFM_TVL_LANES")) {  // tuning override: 1, 2, 4, …, 64
+    const char* const ov = yfm::env_or("YFM_TVL_LANES", nullptr);  // tuning override: 1, 2, 4, …, 64
+    if (ov) {
       const int l = std::atoi(ov);
       if (l >= 1 && l <= 64 && (l & (l - 1)) == 0) lanes = l;
     }
     yfm::TvlGaps g;
     if (ctx->precision == YFM_PREC_CERTIFIED) {
-      lanes = yfm::tvl_dd_lanes_for(B, ctx->N, std::getenv("YFM_TVL_LANES") ? lanes : 0, q.share);
+      lanes = yfm::tvl_dd_lanes_for(B, ctx->N, ov ? lanes : 0, q.share);
       // the context's panel has its column statistics already; a panel of the launch's own gets them here
       const bool own_panel = q.panel && q.panel->raw != static_cast<const double*>(ctx->raw.p);
       const size_t rec_bytes = yfm::tvl_dd_scratch_bytes(B);

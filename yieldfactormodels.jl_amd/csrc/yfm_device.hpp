@@ -211,9 +211,7 @@ __device__ __forceinline__ bool init_state(const Params<M, LEAD>& p, double (&be
 //   W = B̃⁻¹ P = P B⁻¹ (symmetric),  K v = W Z'v,  P_{t|t} = σ² W,
 //   v'F⁻¹v = (v'v − u'Wu)/σ²,  det F = σ^{2(N−M)} det B̃.
 // Outputs the upper triangle of W and det B̃ (its sign is the sign of det F).
-// SYM: return the symmetric part of the computed W (used by the fixed-loading models, whose
-// capacitance lanes are exactly those with near-singular Z'Z); otherwise its upper triangle.
-template <int M, bool SYM = false>
+template <int M>
 struct Capacitance {
   __device__ __forceinline__ static void solve(const double (&P)[M][M], const double (&G)[M][M], double sigma2,
                                                double (&W)[M][M], double& det) {
@@ -285,25 +283,14 @@ struct Capacitance {
     }
     // W = B̃⁻¹P is symmetric in exact arithmetic; the computed one is not (its asymmetry grows
     // with B̃'s conditioning — measured 7e-9 on the loglik from using one triangle when Z'Z is
-    // near-singular).  Use the symmetric part.
+    // near-singular, which is why those candidates go to the double-double kernel instead).
 #pragma unroll
     for (int i = 0; i < M; ++i)
 #pragma unroll
-      for (int j = i; j < M; ++j) W[i][j] = SYM ? 0.5 * (X[i][j] + X[j][i]) : X[i][j];
+      for (int j = i; j < M; ++j) W[i][j] = X[i][j];
     det = sgn * prod;
   }
 };
-
-// 1/d to ~1 ulp: v_rcp_f64 plus two Newton steps (no IEEE special-casing needed:
-// a zero or non-finite d yields a non-finite result, which the callers treat
-// exactly like the reference's singular / non-finite cases).
-__device__ __forceinline__ double rcp_nr(double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  double e = fma(-d, r, 1.0);
-  r = fma(r, e, r);
-  e = fma(-d, r, 1.0);
-  return fma(r, e, r);
-}
 
 // 1/d from v_rcp_f64 and ONE Newton step (the seed's error squared: ≈ 1 ulp), for the per-step
 // LDLᵀ pivots of the fixed-loading filter, where the reciprocal sits on the serial chain
@@ -312,57 +299,9 @@ __device__ __forceinline__ double rcp_nr1(double d) {
   return fma(r, fma(-d, r, 1.0), r);
 }
 
-// Symmetric LDLᵀ (no pivoting) of an M×M matrix S, solving S X = Rhs in place for
-// R right-hand sides; returns det S = ∏ d_i (its sign is exact in the factorised
-// arithmetic).  Used on S = P + σ²(Z'Z)⁻¹, which is SPD whenever P is PSD.
-template <int M, int R>
-__device__ __forceinline__ double ldlt_solve(const double (&S)[M][M], double (&X)[M][R]) {
-  double L[M][M];  // strictly lower part used
-  double a[M][M];  // a[i][k] = L[i][k] * d[k]
-  double d[M], rd[M];
-#pragma unroll
-  for (int j = 0; j < M; ++j) {
-    double dj = S[j][j];
-#pragma unroll
-    for (int k = 0; k < j; ++k) dj = fma(-a[j][k], L[j][k], dj);
-    d[j] = dj;
-    rd[j] = rcp_nr(dj);
-#pragma unroll
-    for (int i = j + 1; i < M; ++i) {
-      double s = S[i][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) s = fma(-a[i][k], L[j][k], s);
-      a[i][j] = s;
-      L[i][j] = s * rd[j];
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < R; ++c) {
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      double s = X[i][c];
-#pragma unroll
-      for (int k = 0; k < i; ++k) s = fma(-L[i][k], X[k][c], s);
-      X[i][c] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < M; ++i) X[i][c] *= rd[i];
-#pragma unroll
-    for (int i = M - 1; i >= 0; --i) {
-      double s = X[i][c];
-#pragma unroll
-      for (int k = i + 1; k < M; ++k) s = fma(-L[k][i], X[k][c], s);
-      X[i][c] = s;
-    }
-  }
-  double det = d[0];
-#pragma unroll
-  for (int i = 1; i < M; ++i) det *= d[i];
-  return det;
-}
-
-// The same LDLᵀ split in two, so callers can stream the right-hand sides one at a time
-// (fewer live registers; per-element arithmetic identical to ldlt_solve).
+// Symmetric LDLᵀ (no pivoting) of an M×M matrix S; factor returns det S = ∏ d_i (its sign is exact in the
+// factorised arithmetic).  Used on S = P + σ²(Z'Z)⁻¹, which is SPD whenever P is PSD.  Factor and solve are
+// separate so callers can stream the right-hand sides one at a time (fewer live registers).
 template <int M>
 struct LDLT {
   double L[M][M];  // strictly lower part used

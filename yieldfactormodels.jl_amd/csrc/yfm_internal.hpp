@@ -3,9 +3,18 @@
 #include "yfm_flags.hpp"
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "../../include/yfm.h"
 
 namespace yfm {
+
+// An environment switch, read at the launch it steers: the variable's text, or `dflt` (which may be null) where
+// it is unset.
+inline const char* env_or(const char* name, const char* dflt) {
+  const char* e = std::getenv(name);
+  return e ? e : dflt;
+}
 
 // A device allocation that grows on demand and frees itself.  It is destroyed with the device it was
 // allocated on current (yfm_destroy sets the context's device before it deletes the context).

@@ -28,7 +28,7 @@
 // Panel layout in HBM (built by prep_panel_kernel from the caller's N×T
 // column-major matrix): T columns of LDP = NP + 4 doubles —
 //   [ ỹ_0 … ỹ_{N-1}, 0 … 0 (to NP), ȳ, ỹ'ỹ, isnan(any y), y'y ].
-#include "yfm_fixedz.hpp"
+#include "yfm_fixedz_mfma.hpp"
 
 namespace yfm {
 
@@ -40,8 +40,6 @@ constexpr int kTC = 64;  // panel columns per LDS chunk (DNS; GNS5 keeps 32: its
 // the σ-permuted 16-byte ones, the first chunks loaded after the setup, no mid-block steady switch, MFMA A
 // operands copied to VGPRs, two (4, 4) tile groups, chunk rotations after a block's steps, and the timing
 // probes (phase cycle counters, MFMAs issued twice, z̃ never stored) that located the costs.
-constexpr bool kMfma4 = true;   // GNS5 Z'ỹ on v_mfma_f64_4x4x4_4b_f64 (DNS keeps v_mfma_f64_16x16x4_f64)
-constexpr bool kZBasis = true;  // GNS5 fragments e = 1 − e^{−λm} against (ỹ, ỹ/m): see the kernel
 
 __global__ void prep_panel_kernel(const double* __restrict__ Y, int N, int T, int np, int ldp,
                                   double* __restrict__ out) {
@@ -273,8 +271,6 @@ __device__ __forceinline__ void dot_zt(const double* __restrict__ col, const dou
   for (int cz = 0; cz < NZ; ++cz) zt[cz] = a[cz][0] + a[cz][1];
 }
 
-typedef double yfm_double4 __attribute__((ext_vector_type(4)));
-
 // Fixed-loading models: DNS (M = 3, one γ, dns.jl:51-65) and the 5-factor
 // generalised NS extension (M = 5, two γ; SURVEY §8 a9, not in the reference).
 // Z column 0 is ones; columns 1.. come in (slope, curvature) pairs per γ:
@@ -309,32 +305,22 @@ __device__ __forceinline__ void fixedz_loglik_body(
   // instead of 32: 0.2040 → 0.2022 ms at config 2, profiles/r4/ab23/); 32 where the LDS is taken by GNS5's
   // z̃ scratch
   constexpr int TC = (M == 3) ? kTC : 32;
-  constexpr bool USE_MFMA_ = (M - 1 == 2 || M - 1 == 4) && (NP <= 32);
+  constexpr int NZ = M - 1;                   // non-constant loading columns
+  constexpr bool USE_MFMA = (NZ == 2 || NZ == 4) && (NP <= 32);  // fragments + LDS scratch budget
   // frozen-covariance steady state (FixedZFilter): the loglik-mode DNS instantiation
   // with STEADY_ (the plain instantiation is the full recursion, YFM_DNS_STEADY=0)
-  constexpr bool STEADY = STEADY_ && !RECORD && (M == 3 || M == 5) && USE_MFMA_;
+  constexpr bool STEADY = STEADY_ && !RECORD && (M == 3 || M == 5) && USE_MFMA;
   constexpr bool SPLIT_INIT = (M == 5);  // initial state from fixedz_init_kernel
   constexpr int CH = TC * LDP;               // doubles per chunk
   constexpr int PER = (CH + kBlock - 1) / kBlock;
-  constexpr int NZ = M - 1;                   // non-constant loading columns
-  constexpr bool USE_MFMA = (NZ == 2 || NZ == 4) && (NP <= 32);  // fragments + LDS scratch budget
   constexpr bool KTRIM = KTRIM_ && USE_MFMA && ktrim_applies(NP, M);  // the last maturity eliminated (header)
   constexpr int NK = ktrim_nk(NP, KTRIM);     // MFMA k-steps (4 maturities each)
-  constexpr int NRT = 64 * NZ / 16;           // MFMA row tiles per wave (16 (cand, col) pairs each)
-  // row tiles accumulated at once (bounds live accumulators).  DNS: two groups of 4, so the first group's
-  // z̃ stores overlap the second group's MFMAs (8: 0.2173 → 4: 0.2165 ms at config 2, 2: 0.2197 ms — two
-  // accumulator chains expose the MFMA latency; profiles/r4/ab9, ab10)
-  constexpr int RGN = 4;
-  constexpr int RGN4 = (NZ == 2) ? NRT : 8;   // the same for the 4×4×4 form (one double per accumulator)
-  constexpr int TB = 16;                      // steps per MFMA block
-  // GNS5 (two γ): the MFMA rows are e_l = 1 − e^{−λ_l m} (one per γ) against the panel columns ỹ and
-  // ỹ/m, so a candidate holds LEAD fragment rows instead of NZ = 2·LEAD:
-  //   Σ S_l ỹ = (1/λ_l) Σ e_l ỹ/m,   Σ C_l ỹ = Σ (S_l − z_l) ỹ = Σ S_l ỹ + Σ e_l ỹ   (Σ ỹ = 0),
-  // which halves the fragment registers (the 5-state filter no longer spills).
-  constexpr bool ZB = USE_MFMA && kMfma4 && kZBasis && LEAD == 2;
+  constexpr int TB = kFzTB;                   // steps per MFMA block
+  // GNS5 (two γ) on the z-basis 4×4×4 MFMA (zty_zbasis): LEAD fragment rows per candidate instead of NZ = 2·LEAD
+  constexpr bool ZB = USE_MFMA && LEAD == 2;
   constexpr int RPC = ZB ? LEAD : NZ;         // fragment rows per candidate
   constexpr int NRTA = 64 * RPC / 16;         // fragment row tiles per wave
-  constexpr int SS = 64 * NZ + 2;             // scratch row stride (doubles): one row per step
+  constexpr int SS = fz_scratch_stride(NZ);   // scratch row stride (doubles): one row per step
   // (also the fragment staging image of 32 candidates: 32·RPC rows of 4·NK + 1 maturities)
   constexpr int SCR = USE_MFMA ? ((TB * SS > 32 * RPC * (4 * NK + 1)) ? TB * SS : 32 * RPC * (4 * NK + 1)) : 2;
   static_assert(NZ == 2 * LEAD, "loading columns come in (S, C) pairs per gamma");
@@ -355,23 +341,8 @@ __device__ __forceinline__ void fixedz_loglik_body(
   const int nobs = T_use ? T_use[bb] : T;
 
   // panel chunk loads (PER doubles per thread; LDS holds chunks c and c+1 while chunk c is processed)
-  auto load_into = [&](double* dst, int c) {
-    const size_t base = (size_t)c * CH;
-    const size_t lim = (size_t)T * LDP;
-#pragma unroll
-    for (int r = 0; r < PER; ++r) {
-      const int e = r * kBlock + tid;
-      const size_t g = base + e;
-      dst[r] = (e < CH && g < lim) ? panel[g] : 0.0;
-    }
-  };
-  auto store_from = [&](const double* src, double* buf) {
-#pragma unroll
-    for (int r = 0; r < PER; ++r) {
-      const int e = r * kBlock + tid;
-      if (e < CH) buf[e] = src[r];
-    }
-  };
+  auto load_into = [&](double* dst, int c) { chunk_load<PER, kBlock>(panel, (size_t)T * LDP, CH, c, tid, dst); };
+  auto store_from = [&](const double* src, double* buf) { chunk_store<PER, kBlock>(src, CH, tid, buf); };
   // EARLY: chunks 0 and 1 issued before the setup, so their HBM latency hides under the θ decode and the
   // loadings instead of two serial round trips after it (stored to LDS where the staging starts below)
   constexpr bool EARLY = M == 3 && NP <= 32;  // GNS5 and NP > 32 spill with the 2·PER registers
@@ -459,16 +430,10 @@ __device__ __forceinline__ void fixedz_loglik_body(
 
   // MFMA A fragments: tile r, k-step kk — lane l holds Z of pair p = 16r + σ(l & 15)
   // (candidate p / NZ of this wave, column p % NZ) at maturity 4kk + (l >> 4).
-  // Gathered once through the wave's scratch, 16 candidates at a time.
-  // σ (the 16×16×4 form only): row i = g + 4q of a tile holds pair 16r + 4g + q, so the four D values a lane
-  // holds (rows g, g+4, g+8, g+12 of one step) are four consecutive pairs — two 16-byte LDS stores per tile
-  // instead of four 8-byte ones, and still one candidate's z̃ in consecutive doubles for the step reads
-  constexpr bool SIGMA = USE_MFMA && !ZB && !(kMfma4 && NZ == 4);
-  // IL: the row tiles in three groups (4, 2, 2), each group's stores interleaved with the next group's MFMAs
-  // (NP 29–32: one store per k-step; with 7 k-steps the last k-step takes the store left over)
-  constexpr bool IL = SIGMA && NRT == 2 * RGN && (NK == 2 * RGN || NK == 2 * RGN - 1);
-  constexpr bool IL5 = ZB && NK == NRTA;  // GNS5: the same across step pairs
-  auto sigma = [](int i) { return SIGMA ? 4 * (i & 3) + (i >> 2) : i; };
+  // Gathered once through the wave's scratch, 32 candidates at a time.
+  // σ (fz_sigma): the pair permutation of the 16×16×4 form (DNS), which makes its D tiles 16-byte stores
+  constexpr bool SIGMA = USE_MFMA && !ZB;
+  auto sigma = [](int i) { return SIGMA ? fz_sigma(i) : i; };
   double Af[USE_MFMA ? NRTA : 1][USE_MFMA ? NK : 1];
   // KTRIM: the loadings of the last maturity (N is a runtime value: a select chain, no indexed register array)
   // and this lane's two differenced loadings of slot 28, which the step adds on the VALU
@@ -560,7 +525,6 @@ __device__ __forceinline__ void fixedz_loglik_body(
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) wmin = min(wmin, __shfl_xor(wmin, off));
   const int wave_min_data = __builtin_amdgcn_readfirstlane(wmin);
-  const bool wave_all_collapsed = true;  // non-collapsed lanes are deferred (their values are discarded)
 
   __syncthreads();
   const int nsteps = max(s_nobs_max, 0);
@@ -583,21 +547,11 @@ __device__ __forceinline__ void fixedz_loglik_body(
     load_chunk(2);
   }
   auto col_of = [&](int t) -> const double* { return sh[(t / TC) & 1] + (t % TC) * LDP; };
-  // a 16×16×4 D tile into a scratch buffer: lane l holds step l & 15, pairs 16r + 4(l >> 4) + q (σ above)
-  auto store_tile = [&](double* dst, int r, const yfm_double4& a) {
-    if constexpr (SIGMA) {
-      double* d = dst + (lane & 15) * SS + 16 * r + 4 * (lane >> 4);
-      *reinterpret_cast<double2*>(d) = make_double2(a[0], a[1]);
-      *reinterpret_cast<double2*>(d + 2) = make_double2(a[2], a[3]);
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) dst[(lane & 15) * SS + 16 * r + (lane >> 4) + 4 * q] = a[q];
-    }
-  };
 
   // one filter step given z̃_t (zc), (ȳ, ỹ'ỹ) and (nanflag, y'y) of column t
+  // (fast whatever the lanes' Z'Z: non-collapsed lanes are deferred and their values discarded)
   auto do_step = [&](int t, const double (&zc)[NZ], double2 yb_c, double2 meta_c) {
-    const bool fast = (t >= 1) && (meta_c.x == 0.0) && (t < wave_min_data) && wave_all_collapsed;
+    const bool fast = (t >= 1) && (meta_c.x == 0.0) && (t < wave_min_data);
     f.step(t, zc, yb_c, meta_c, fast, my_steps, my_data);
   };
   auto record = [&](int t) {
@@ -630,7 +584,7 @@ __device__ __forceinline__ void fixedz_loglik_body(
       // accumulators are live (FixedZFilter::prepare_bound)
       if constexpr (STEADY) f.prepare_bound();
       if constexpr (SIGMA || M == 5) {
-        // the A fragments stay in AGPRs, where the 16×16×4 MFMA reads them as its A operand (left to itself the
+        // the A fragments stay in AGPRs, where the MFMA reads them as its A operand (left to itself the
         // allocator copies each one to a VGPR before its MFMA: 128 v_accvgpr_read per block)
 #pragma unroll
         for (int r = 0; r < NRTA; ++r)
@@ -638,19 +592,67 @@ __device__ __forceinline__ void fixedz_loglik_body(
           for (int kk = 0; kk < NK; ++kk) asm volatile("" : "+a"(Af[r][kk]));
       }
       double* scr = scratch[wave];
-      // ---- z̃ for steps t0 .. t0+15 of all 64 candidates: NRT·NK MFMAs ----
+      // ---- z̃ for steps t0 .. t0+15 of all 64 candidates: NRTA·NK MFMAs per block or step pair ----
       const double* cb = col_of(t0);  // TB consecutive columns of one chunk
       // the block's NaN flags, one column per lane, read before the MFMAs so the steady-block vote after them
       // does not wait for an LDS round trip (0.2179 → 0.2168 ms at config 2, profiles/r4/ab9/)
       const double col_flag = cb[min(lane, TB - 1) * LDP + NP + 2];
-      if constexpr (ZB && IL5) {
-        // as below, software-pipelined over the step pairs: step pair sp − 1's 8 results are stored one per
-        // k-step of step pair sp's MFMAs (the wave issues the stores while the matrix pipe works)
-        double accp[NRTA];
+      if constexpr (ZB) {
+        // GNS5 on v_mfma_f64_4x4x4_4b_f64 in the z-basis (layout: yfm_fixedz_mfma.hpp).  Inline: as functions
+        // these two arms changed the register allocation of every GNS5 MFMA kernel
+        // (even a local lambda for the B operand or the store slot does).
+        // rows: pair 16r + 4blk + i = (candidate, γ index); columns j of step pair sp: step
+        // 2sp + (j >> 1), ỹ (j even) or ỹ/m (j odd).  Results — lane l: pair 16r + 4((l >> 2) & 3) + (l >> 4),
+        // step 2sp + ((l & 3) >> 1), column l & 1; per step a candidate's four values are
+        // (Σe₁ỹ, Σe₁ỹ/m, Σe₂ỹ, Σe₂ỹ/m)
+        if constexpr (NK == NRTA) {
+          // software-pipelined over the step pairs: step pair sp − 1's 8 results are stored one per k-step of
+          // step pair sp's MFMAs (the wave issues the stores while the matrix pipe works)
+          double accp[NRTA];
 #pragma unroll
-        for (int sp = 0; sp <= TB / 2; ++sp) {
-          double acc[NRTA];
-          if (sp < TB / 2) {
+          for (int sp = 0; sp <= TB / 2; ++sp) {
+            double acc[NRTA];
+            if (sp < TB / 2) {
+              double bv[NK];
+#pragma unroll
+              for (int kk = 0; kk < NK; ++kk) {
+                const int m = 4 * kk + (lane >> 4);
+                const double y = (m < NP) ? cb[(2 * sp + ((lane & 3) >> 1)) * LDP + m] : 0.0;
+                bv[kk] = (lane & 1) ? y * s_rm[m < NP ? m : 0] : y;
+              }
+#pragma unroll
+              for (int r = 0; r < NRTA; ++r) acc[r] = 0.0;
+#pragma unroll
+              for (int kk = 0; kk < NK; ++kk) {
+#pragma unroll
+                for (int r = 0; r < NRTA; ++r)
+                  acc[r] = __builtin_amdgcn_mfma_f64_4x4x4f64(Af[r][kk], bv[kk], acc[r], 0, 0, 0);
+                if (sp > 0)
+                  scr[(2 * (sp - 1) + ((lane & 3) >> 1)) * SS + 2 * (16 * kk + 4 * ((lane >> 2) & 3) + (lane >> 4)) +
+                      (lane & 1)] = accp[kk];
+              }
+            } else {
+#pragma unroll
+              for (int r = 0; r < NRTA; ++r)
+                scr[(2 * (sp - 1) + ((lane & 3) >> 1)) * SS + 2 * (16 * r + 4 * ((lane >> 2) & 3) + (lane >> 4)) +
+                    (lane & 1)] = accp[r];
+            }
+            if (sp < TB / 2) {
+#pragma unroll
+              for (int r = 0; r < NRTA; ++r) accp[r] = acc[r];
+            }
+          }
+          __builtin_amdgcn_sched_group_barrier(0x008, NRTA * NK, 0);  // step pair 0's MFMAs
+#pragma unroll
+          for (int sp = 1; sp < TB / 2; ++sp)
+#pragma unroll
+            for (int kk = 0; kk < NK; ++kk) {
+              __builtin_amdgcn_sched_group_barrier(0x008, NRTA, 0);  // a k-step of step pair sp
+              __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);     // one store of step pair sp − 1
+            }
+        } else {
+#pragma unroll
+          for (int sp = 0; sp < TB / 2; ++sp) {
             double bv[NK];
 #pragma unroll
             for (int kk = 0; kk < NK; ++kk) {
@@ -658,50 +660,6 @@ __device__ __forceinline__ void fixedz_loglik_body(
               const double y = (m < NP) ? cb[(2 * sp + ((lane & 3) >> 1)) * LDP + m] : 0.0;
               bv[kk] = (lane & 1) ? y * s_rm[m < NP ? m : 0] : y;
             }
-#pragma unroll
-            for (int r = 0; r < NRTA; ++r) acc[r] = 0.0;
-#pragma unroll
-            for (int kk = 0; kk < NK; ++kk) {
-#pragma unroll
-              for (int r = 0; r < NRTA; ++r)
-                acc[r] = __builtin_amdgcn_mfma_f64_4x4x4f64(Af[r][kk], bv[kk], acc[r], 0, 0, 0);
-              if (sp > 0)
-                scr[(2 * (sp - 1) + ((lane & 3) >> 1)) * SS + 2 * (16 * kk + 4 * ((lane >> 2) & 3) + (lane >> 4)) +
-                    (lane & 1)] = accp[kk];
-            }
-          } else {
-#pragma unroll
-            for (int r = 0; r < NRTA; ++r)
-              scr[(2 * (sp - 1) + ((lane & 3) >> 1)) * SS + 2 * (16 * r + 4 * ((lane >> 2) & 3) + (lane >> 4)) +
-                  (lane & 1)] = accp[r];
-          }
-          if (sp < TB / 2) {
-#pragma unroll
-            for (int r = 0; r < NRTA; ++r) accp[r] = acc[r];
-          }
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, NRTA * NK, 0);  // step pair 0's MFMAs
-#pragma unroll
-        for (int sp = 1; sp < TB / 2; ++sp)
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-            __builtin_amdgcn_sched_group_barrier(0x008, NRTA, 0);  // a k-step of step pair sp
-            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);     // one store of step pair sp − 1
-          }
-      } else if constexpr (ZB) {
-        // rows: pair 16r + 4blk + i = (candidate, γ index); columns j of step pair sp: step
-        // 2sp + (j >> 1), ỹ (j even) or ỹ/m (j odd)
-#pragma unroll
-        for (int sp = 0; sp < TB / 2; ++sp) {
-          double bv[NK];
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-            const int m = 4 * kk + (lane >> 4);
-            const double y = (m < NP) ? cb[(2 * sp + ((lane & 3) >> 1)) * LDP + m] : 0.0;
-            bv[kk] = (lane & 1) ? y * s_rm[m < NP ? m : 0] : y;
-          }
-#pragma unroll
-          for (int r0 = 0; r0 < NRTA; r0 += NRTA) {
             double acc[NRTA];
 #pragma unroll
             for (int r = 0; r < NRTA; ++r) acc[r] = 0.0;
@@ -710,44 +668,10 @@ __device__ __forceinline__ void fixedz_loglik_body(
 #pragma unroll
               for (int r = 0; r < NRTA; ++r)
                 acc[r] = __builtin_amdgcn_mfma_f64_4x4x4f64(Af[r][kk], bv[kk], acc[r], 0, 0, 0);
-            // lane l: pair 16r + 4((l >> 2) & 3) + (l >> 4), step 2sp + ((l & 3) >> 1), column l & 1;
-            // per step a candidate's four values are (Σe₁ỹ, Σe₁ỹ/m, Σe₂ỹ, Σe₂ỹ/m)
 #pragma unroll
             for (int r = 0; r < NRTA; ++r)
               scr[(2 * sp + ((lane & 3) >> 1)) * SS + 2 * (16 * r + 4 * ((lane >> 2) & 3) + (lane >> 4)) + (lane & 1)] =
                   acc[r];
-          }
-        }
-      } else if constexpr (kMfma4 && NZ == 4) {
-        // v_mfma_f64_4x4x4_4b_f64: block blk of instruction (r, s, kk) is D[4×4] = A[4 pairs ×
-        // 4 maturities]·B[4 maturities × 4 steps] for pairs 16r + 4blk + i, steps 4s + j,
-        // maturities 4kk + k.  Operand lanes (tools/mfma_f64_4x4_probe.hip): A[blk][i][k] in
-        // lane 16k + 4blk + i — exactly the 16×16×4 A fragment above — B[blk][k][j] in lane
-        // 16k + 4blk + j (the same panel values for every block), D[blk][i][j] in lane
-        // 16i + 4blk + j.  512 flops per instruction at ≈17 cycles vs 2,048 at ≈144 for the
-        // 16×16×4 form at one wave per SIMD (profiles/r2/micro).
-#pragma unroll
-        for (int s = 0; s < TB / 4; ++s) {
-          double bv[NK];
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-            const int m = 4 * kk + (lane >> 4);
-            bv[kk] = (m < NP) ? cb[(4 * s + (lane & 3)) * LDP + m] : 0.0;
-          }
-#pragma unroll
-          for (int r0 = 0; r0 < NRT; r0 += RGN4) {
-            double acc[RGN4];
-#pragma unroll
-            for (int r = 0; r < RGN4; ++r) acc[r] = 0.0;
-#pragma unroll
-            for (int kk = 0; kk < NK; ++kk)
-#pragma unroll
-              for (int r = 0; r < RGN4; ++r)
-                acc[r] = __builtin_amdgcn_mfma_f64_4x4x4f64(Af[r0 + r][kk], bv[kk], acc[r], 0, 0, 0);
-            // lane l holds pair 16r + 4((l >> 2) & 3) + (l >> 4) at step 4s + (l & 3)
-#pragma unroll
-            for (int r = 0; r < RGN4; ++r)
-              scr[(4 * s + (lane & 3)) * SS + 16 * (r0 + r) + 4 * ((lane >> 2) & 3) + (lane >> 4)] = acc[r];
           }
         }
       } else {
@@ -757,84 +681,10 @@ __device__ __forceinline__ void fixedz_loglik_body(
           const int m = 4 * kk + (lane >> 4);
           bvk[kk] = (m < NP) ? cb[(lane & 15) * LDP + m] : 0.0;  // B[k = m][col = step]
         }
-        if constexpr (IL) {
-          // three groups of 4, 2, 2 tiles: the first group's 8 stores during the second group's MFMAs, the
-          // second's 4 during the third's, so only the last 2 tiles' 4 stores trail the block.  Store s of a group
-          // (tile s >> 1, half s & 1) goes after a k-step of the next group: the first group's store s after
-          // k-step s, the second's after k-step 2s + 1 — with 7 k-steps the last k-step takes the store that
-          // would have followed the eighth (two of the first group's, the second group's fourth)
-          constexpr int H = RGN / 2;
-          constexpr int NS1 = 2 * RGN, NS2 = 2 * H;  // 16-byte stores of the first and the second group
-          auto last1 = [](int kk) { return kk == NK - 1 ? NS1 : kk + 1; };  // first-group stores issued by k-step kk
-          auto at2 = [](int s) { return 2 * s + 1 < NK - 1 ? 2 * s + 1 : NK - 1; };  // k-step of second-group store s
-          yfm_double4 a1[RGN], a2[H], a3[H];
-#pragma unroll
-          for (int r = 0; r < RGN; ++r) a1[r] = yfm_double4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int r = 0; r < H; ++r) a2[r] = a3[r] = yfm_double4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk)
-#pragma unroll
-            for (int r = 0; r < RGN; ++r)
-              a1[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[r][kk], bvk[kk], a1[r], 0, 0, 0);
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-#pragma unroll
-            for (int r = 0; r < H; ++r)
-              a2[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[RGN + r][kk], bvk[kk], a2[r], 0, 0, 0);
-#pragma unroll
-            for (int s = kk; s < last1(kk); ++s) {
-              const int r1 = s >> 1, h = s & 1;
-              double* d = scr + (lane & 15) * SS + 16 * r1 + 4 * (lane >> 4) + 2 * h;
-              *reinterpret_cast<double2*>(d) = make_double2(a1[r1][2 * h], a1[r1][2 * h + 1]);
-            }
-          }
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-#pragma unroll
-            for (int r = 0; r < H; ++r)
-              a3[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[RGN + H + r][kk], bvk[kk], a3[r], 0, 0, 0);
-#pragma unroll
-            for (int s = 0; s < NS2; ++s) {
-              if (at2(s) == kk) {
-                const int r2 = s >> 1, h = s & 1;
-                double* d = scr + (lane & 15) * SS + 16 * (RGN + r2) + 4 * (lane >> 4) + 2 * h;
-                *reinterpret_cast<double2*>(d) = make_double2(a2[r2][2 * h], a2[r2][2 * h + 1]);
-              }
-            }
-          }
-          __builtin_amdgcn_sched_group_barrier(0x008, RGN * NK, 0);  // the first group's MFMAs
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-            __builtin_amdgcn_sched_group_barrier(0x008, H, 0);  // a k-step of the second group
-#pragma unroll
-            for (int s = kk; s < last1(kk); ++s) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // one store of the first
-          }
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk) {
-            __builtin_amdgcn_sched_group_barrier(0x008, H, 0);  // a k-step of the third group
-#pragma unroll
-            for (int s = 0; s < NS2; ++s)
-              if (at2(s) == kk) __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);  // one store of the second
-          }
-#pragma unroll
-          for (int r = 0; r < H; ++r) store_tile(scr, RGN + H + r, a3[r]);
-        } else {
-#pragma unroll
-        for (int r0 = 0; r0 < NRT; r0 += RGN) {
-          yfm_double4 acc[RGN];
-#pragma unroll
-          for (int r = 0; r < RGN; ++r) acc[r] = yfm_double4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-          for (int kk = 0; kk < NK; ++kk)
-#pragma unroll
-            for (int r = 0; r < RGN; ++r)
-              acc[r] = __builtin_amdgcn_mfma_f64_16x16x4f64(Af[r0 + r][kk], bvk[kk], acc[r], 0, 0, 0);
-          // D[row][col = step]: lane l holds step l & 15, rows (l >> 4) + 4q = pairs 16r + 4(l >> 4) + q
-#pragma unroll
-          for (int r = 0; r < RGN; ++r) store_tile(scr, r0 + r, acc[r]);
-        }
-        }
+        if constexpr (fz_interleaved(NRTA, NK))
+          zty_dns_interleaved(Af, bvk, scr, lane);
+        else
+          zty_dns(Af, bvk, scr, lane);
       }
       __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): this wave's scratch writes landed
       __builtin_amdgcn_wave_barrier();
@@ -856,14 +706,6 @@ __device__ __forceinline__ void fixedz_loglik_body(
       // (KTRIM: the operands carry ỹ₂₈ of the step's column in element NZ — a wave-uniform 16-byte read — and
       // z_of adds the leftover term when the step consumes them)
       constexpr int NZX = NZ + (KTRIM ? 1 : 0);
-      auto z_of = [&](const double (&zx)[NZX], double (&z)[NZ]) {
-        if constexpr (KTRIM) {
-          ktrim_leftover<NZ>(zd28, zx, z);
-        } else {
-#pragma unroll
-          for (int j = 0; j < NZ; ++j) z[j] = zx[j];
-        }
-      };
       auto read_z = [&](int tt, double (&z)[NZX]) {  // this lane's pairs NZ·lane .. NZ·lane + NZ − 1
         if constexpr (KTRIM) z[NZ] = reinterpret_cast<const double2*>(cb + tt * LDP + kTrimSlot)->x;
         const double* sp = scr + tt * SS + NZ * lane;
@@ -894,7 +736,7 @@ __device__ __forceinline__ void fixedz_loglik_body(
         ybn_ = *reinterpret_cast<const double2*>(cb + tn * LDP + NP);
         metan_ = *reinterpret_cast<const double2*>(cb + tn * LDP + NP + 2);
         double z[NZ];
-        z_of(zc_, z);
+        z_of<NZ, KTRIM>(zd28, zc_, z);
         do_step(t, z, yb_, meta_);
         record(t);
         if ((t + 1) % TC == 0) rot_t = t;  // the chunk rotation, deferred to the next block's start
@@ -906,7 +748,7 @@ __device__ __forceinline__ void fixedz_loglik_body(
         read_z(tn, zn_);
         ybn_ = *reinterpret_cast<const double2*>(cb + tn * LDP + NP);
         double z[NZ];
-        z_of(zc_, z);
+        z_of<NZ, KTRIM>(zd28, zc_, z);
         f.steady_step(z, yb_);
         if ((t0 + tt + 1) % TC == 0) rot_t = t0 + tt;
       };
@@ -928,7 +770,7 @@ __device__ __forceinline__ void fixedz_loglik_body(
               read_z(tn, zq[nx]);
               ybq[nx] = *reinterpret_cast<const double2*>(cb + tn * LDP + NP);
               double z[NZ];
-              z_of(zq[cur], z);
+              z_of<NZ, KTRIM>(zd28, zq[cur], z);
               f.steady_step(z, ybq[cur]);
             }
             rot_t = ((t0 + TB) % TC == 0) ? t0 + TB - 1 : -1;  // at the next block's start
@@ -1068,42 +910,22 @@ __global__ __launch_bounds__(kBlock, 1) void fixedz_loglik_kernel(
 // ------------------------------------------------------------------------------------
 #include "yfm_internal.hpp"
 
-#include <cstdlib>
+#include <cstring>
 
 namespace yfm {
 
-// the frozen-covariance steady state of the DNS loglik kernel (FixedZFilter): on unless YFM_DNS_STEADY=0
-static int steady_enabled() {
-  const char* e = std::getenv("YFM_DNS_STEADY");
-  return (e && e[0] == '0') ? 0 : 1;
-}
-
 // DNS at NP = 30 with the last maturity eliminated (7 MFMA k-steps; ktrim_* in yfm_fixedz.hpp): on unless
 // YFM_DNS_KTRIM=0 (declared in yfm_internal.hpp: the two-wave kernel obeys it too)
-int ktrim_enabled() {
-  const char* e = std::getenv("YFM_DNS_KTRIM");
-  return (e && e[0] == '0') ? 0 : 1;
-}
+int ktrim_enabled() { return env_or("YFM_DNS_KTRIM", "1")[0] != '0'; }
 
-// the GNS5 steady state: off unless YFM_GNS5_STEADY=1
-static int gns5_steady_enabled() {
-  const char* e = std::getenv("YFM_GNS5_STEADY");
-  return (e && e[0] == '1') ? 1 : 0;
-}
-
-// diagnostic: YFM_FZ_SPLIT_FORM=1 selects the two-function update form (FixedZFilter SPLIT_FORM)
-static int split_form_enabled() {
-  const char* e = std::getenv("YFM_FZ_SPLIT_FORM");
-  return (e && e[0] == '1') ? 1 : 0;
-}
-
-// GNS5 initial state: two lanes per candidate (fixedz_init_coop_kernel); YFM_GNS5_INIT_LANES=1 runs the per-lane
-// kernel it is bitwise equal to (tests/test_gpu_gns5_init.py).  Four lanes per candidate, at two waves per SIMD,
-// measured slower (0.83 vs 0.74 ms at config 5; per-lane 1.05 ms): the replicated decode and pivot search cost more
-// than the second wave hides (profiles/r6/gns5_init/).
-static int gns5_init_lanes() {
-  const char* e = std::getenv("YFM_GNS5_INIT_LANES");
-  return (e && e[0] == '1' && e[1] == 0) ? 1 : 2;
+// The kernel of one instantiation.  KTRIM (the default) goes by the six-argument name, so where KTRIM does not
+// apply no second copy of a kernel is instantiated under the seven-argument one.
+template <int NP, int M, int LEAD, bool RECORD, bool STEADY, bool SPLIT_FORM, bool KTRIM>
+static constexpr auto fixedz_kernel() {
+  if constexpr (KTRIM)
+    return &fixedz_loglik_kernel<NP, M, LEAD, RECORD, STEADY, SPLIT_FORM>;
+  else
+    return &fixedz_loglik_kernel<NP, M, LEAD, RECORD, STEADY, SPLIT_FORM, false>;
 }
 
 template <int NP, int M, int LEAD>
@@ -1111,8 +933,11 @@ static hipError_t launch_fixedz_np(const LaunchArgs& a) {
   const int grid = (a.B + kBlock - 1) / kBlock;
   if constexpr (M == 5) {
     if (!a.scratch) return hipErrorInvalidValue;
-    const int ir = gns5_init_lanes();
-    if (ir == 1) {
+    // GNS5 initial state: two lanes per candidate (fixedz_init_coop_kernel); YFM_GNS5_INIT_LANES=1 runs the
+    // per-lane kernel it is bitwise equal to (tests/test_gpu_gns5_init.py).  Four lanes per candidate, at two waves
+    // per SIMD, measured slower (0.83 vs 0.74 ms at config 5; per-lane 1.05 ms): the replicated decode and pivot
+    // search cost more than the second wave hides (profiles/r6/gns5_init/).
+    if (std::strcmp(env_or("YFM_GNS5_INIT_LANES", "2"), "1") == 0) {
       hipLaunchKernelGGL((fixedz_init_kernel<M, LEAD>), dim3(grid), dim3(kBlock), 0, a.stream, a.theta, a.P, a.B,
                          a.space, a.scratch, a.flags_next);
     } else {
@@ -1121,39 +946,36 @@ static hipError_t launch_fixedz_np(const LaunchArgs& a) {
                          a.space, a.scratch, a.flags_next);
     }
   }
-  // YFM_DNS_KTRIM=0: the 8-k-step instantiations of DNS at NP = 30 (the seven-argument kernels)
+  // The instantiations a runtime switch can select (a false k… names the default one again):
+  // YFM_DNS_KTRIM=0: the 8-k-step kernels of DNS at NP = 30 (the seven-argument names)
   constexpr bool kTrimmable = ktrim_applies(NP, M) && (NP <= 32);
-  bool untrimmed = false;
-  if constexpr (kTrimmable) untrimmed = !ktrim_enabled();
+  // the frozen-covariance steady state (FixedZFilter) of the MFMA instantiations, loglik mode
+  constexpr bool kSteady = (M == 3 || M == 5) && (NP <= 32);
+  // diagnostic, YFM_FZ_SPLIT_FORM=1: the two-function form of the update (commit 7a42719's regression test),
+  // GNS5 full recursion
+  constexpr bool kSplitForm = (M == 5) && (NP == 30 || NP == 48);
+  const bool untrimmed = kTrimmable && !ktrim_enabled();
   if (a.rec_beta) {
-    auto* k = &fixedz_loglik_kernel<NP, M, LEAD, true, false, false>;
-    if constexpr (kTrimmable) {
-      if (untrimmed) k = &fixedz_loglik_kernel<NP, M, LEAD, true, false, false, false>;
-    }
+    auto* k = untrimmed ? fixedz_kernel<NP, M, LEAD, true, false, false, !kTrimmable>()
+                        : fixedz_kernel<NP, M, LEAD, true, false, false, true>();
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, a.stream, a.theta, a.P,
                        a.B, a.space, a.panel, a.T, a.N, a.mats, a.T_use, a.out, a.flags, a.rec_beta, a.rec_P,
                        a.horizon, a.rec_len, a.defer_list, a.defer_count, a.scratch, M == 5 ? nullptr : a.flags_next, 0);
   } else {
-    constexpr bool kSteady = (M == 3 || M == 5) && (NP <= 32);  // the MFMA instantiations
     // short panels: the first (full) block and the freeze tests cost more than the steady steps save
     // (T = 34: 0.054 vs 0.045 ms; equal at T = 66; profiles/r3/probes/dns_tsweep/)
     constexpr int kSteadyMinT = 80;
-    // GNS5: opt-in (YFM_GNS5_STEADY=1) — the freeze rule's contraction bound is loose for its slower closed
-    // loop (spectral radius ≈ 0.74 at θ₀): almost no config-5 wave freezes, and the steady instantiation's
-    // freeze tests and bound then cost 19.7 → 26.6 ms (profiles/r4/)
-    const bool on = steady_enabled() && a.T >= kSteadyMinT && (M != 5 || gns5_steady_enabled());
-    auto* k = (kSteady && on) ? &fixedz_loglik_kernel<NP, M, LEAD, false, kSteady>
-                              : &fixedz_loglik_kernel<NP, M, LEAD, false, false>;
-    // diagnostic: the two-function form of the update (commit 7a42719's regression test), GNS5 full recursion
-    constexpr bool kSplitForm = (M == 5) && (NP == 30 || NP == 48);
-    if constexpr (kSplitForm) {
-      if (split_form_enabled()) k = &fixedz_loglik_kernel<NP, M, LEAD, false, false, true>;
-    }
-    if constexpr (kTrimmable) {
-      if (untrimmed)
-        k = (kSteady && on) ? &fixedz_loglik_kernel<NP, M, LEAD, false, kSteady, false, false>
-                            : &fixedz_loglik_kernel<NP, M, LEAD, false, false, false, false>;
-    }
+    // on unless YFM_DNS_STEADY=0.  GNS5: opt-in (YFM_GNS5_STEADY=1) — the freeze rule's contraction bound is
+    // loose for its slower closed loop (spectral radius ≈ 0.74 at θ₀): almost no config-5 wave freezes, and the
+    // steady instantiation's freeze tests and bound then cost 19.7 → 26.6 ms (profiles/r4/)
+    const bool steady = kSteady && env_or("YFM_DNS_STEADY", "1")[0] != '0' && a.T >= kSteadyMinT &&
+                        (M != 5 || env_or("YFM_GNS5_STEADY", "0")[0] == '1');
+    const bool split_form = kSplitForm && env_or("YFM_FZ_SPLIT_FORM", "0")[0] == '1';
+    auto* k = untrimmed    ? (steady ? fixedz_kernel<NP, M, LEAD, false, kSteady, false, !kTrimmable>()
+                                     : fixedz_kernel<NP, M, LEAD, false, false, false, !kTrimmable>())
+              : split_form ? fixedz_kernel<NP, M, LEAD, false, false, kSplitForm, true>()
+              : steady     ? fixedz_kernel<NP, M, LEAD, false, kSteady, false, true>()
+                           : fixedz_kernel<NP, M, LEAD, false, false, false, true>();
     hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, a.stream, a.theta, a.P, a.B, a.space, a.panel, a.T, a.N,
                        a.mats, a.T_use, a.out, a.flags, nullptr, nullptr, 0, 0, a.defer_list, a.defer_count,
                        a.scratch, M == 5 ? nullptr : a.flags_next, 1);
@@ -1177,11 +999,8 @@ int fixedz_np_for(int N) {
 }
 
 hipError_t launch_fixedz(int kind, const LaunchArgs& a) {
-  if (kind == 0 && dns_split_supported(a.np)) {
-    // the two-wave kernel (yfm_split.hip) is measured slower on MI355X: opt-in only
-    const char* e = std::getenv("YFM_DNS_SPLIT");
-    if (e && e[0] == '1') return launch_dns_split(a);
-  }
+  // the two-wave kernel (yfm_split.hip) is measured slower on MI355X: opt-in only
+  if (kind == 0 && dns_split_supported(a.np) && env_or("YFM_DNS_SPLIT", "0")[0] == '1') return launch_dns_split(a);
   if (kind == 0) {
     switch (a.np) {
       case 8: return launch_fixedz_np<8, 3, 1>(a);

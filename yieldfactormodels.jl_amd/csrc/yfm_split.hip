@@ -23,10 +23,9 @@
 // Trajectory mode (predict / filter_states): the mean wave records β, the covariance wave P.
 // Ill-conditioned Z'Z lanes are deferred to the double-double kernel exactly as in the per-lane
 // kernel (both waves compute the same decision).
-#include "yfm_fixedz.hpp"
+#include "yfm_fixedz_mfma.hpp"
 #include "yfm_internal.hpp"
 
-#include <cstdlib>
 #include <type_traits>
 
 namespace yfm {
@@ -187,23 +186,8 @@ __global__ __launch_bounds__(kSplitBlock, 1) void dns_split_kernel(
 
   // ---- panel staging (all 512 threads): LDS holds chunks c and c+1 --------------------------
   double pre[PER];
-  auto load_chunk = [&](int c) {
-    const size_t base = (size_t)c * CH;
-    const size_t lim = (size_t)T * LDP;
-#pragma unroll
-    for (int r = 0; r < PER; ++r) {
-      const int e = r * kSplitBlock + tid;
-      const size_t g = base + e;
-      pre[r] = (e < CH && g < lim) ? panel[g] : 0.0;
-    }
-  };
-  auto store_chunk = [&](double* buf) {
-#pragma unroll
-    for (int r = 0; r < PER; ++r) {
-      const int e = r * kSplitBlock + tid;
-      if (e < CH) buf[e] = pre[r];
-    }
-  };
+  auto load_chunk = [&](int c) { chunk_load<PER, kSplitBlock>(panel, (size_t)T * LDP, CH, c, tid, pre); };
+  auto store_chunk = [&](double* buf) { chunk_store<PER, kSplitBlock>(pre, CH, tid, buf); };
   if (nsteps > 0) {
     load_chunk(0);
     store_chunk(sh[0]);

@@ -43,7 +43,23 @@ typedef struct yfm_ctx yfm_ctx;
 enum yfm_model_kind {
   YFM_MODEL_DNS = 0,  /* "1C" / "0": DNSModel, fixed λ, M = 3, P = 20 (dns.jl) */
   YFM_MODEL_TVL = 1,  /* "TVλ" / "1": TVλDNSModel EKF, M = 4, P = 31 (tvλdns.jl) */
-  YFM_MODEL_GNS5 = 2  /* extension, not in the reference: 5-factor generalised NS, M = 5, P = 48 */
+  YFM_MODEL_GNS5 = 2, /* extension, not in the reference: 5-factor generalised NS, M = 5, P = 48 */
+  /* The static and score-driven λ models of src/models/filter.jl:52-110 (model_dictionary.jl:17-35): not Kalman
+   * filters.  M = 3 factors, L = 1 observation-driven parameter γ = log(λ − 0.01).  θ_c = [A, B, ω, δ(3), vec Φ(9)]
+   * (msedriven/paramteroperations.jl:25-65), Φ COLUMN-major (reshape), without B for the random-walk variants and
+   * [γ, δ(3), vec Φ(9)] for NS (static/paramteroperations.jl:19-43).  Unconstrained space: A → exp,
+   * B → 1/(1 + e^−x), the diagonal of Φ → from_R_to_11, the rest identity (mselambda.jl:17-34, msebasemodel.jl:77-90).
+   * For these kinds loglik_out is get_loss of src/models/filter.jl:209-243 — minus the mean squared one-step
+   * prediction error, mse/N/nobs — and −Inf where that returns −Inf (a non-finite running sum: a NaN anywhere in a
+   * compared column, or a step whose OLS fails twice, filter.jl:62-67, :122-137).  Nothing throws at
+   * initialisation: n_init_throw stays 0.  Value 7 is not a kind.  The two scaled kinds evaluate their score at the
+   * refined OLS β (csrc/yfm_msed.hpp): where the Float64 reference's score is rounding noise (N = 3) they follow the
+   * exact recursion, not the noise. */
+  YFM_MODEL_NS = 3,      /* "NS" / "2": StaticλModel, P = 13 (staticlambda.jl) */
+  YFM_MODEL_SD_NS = 4,   /* "SD-NS" / "4": MSEDλModel, P = 15 (mselambda.jl) */
+  YFM_MODEL_RWSD_NS = 5, /* "RWSD-NS" / "5": random walk γ (no B), P = 14 */
+  YFM_MODEL_SSD_NS = 6,  /* "SSD-NS" / "6": score scaled by its EWMA root (filter.jl:29-44, f = 0.98), P = 15 */
+  YFM_MODEL_SRWSD_NS = 8 /* "SRWSD-NS" / "7": scaled, random walk, P = 14 */
 };
 
 /* param_space */
@@ -84,7 +100,7 @@ enum yfm_precision { YFM_PREC_CERTIFIED = 0, YFM_PREC_FP64 = 1 };
 int yfm_abi_version(void);
 /* Length P of θ for a model kind (kalmanbasemodel.jl:106-112 + dns.jl:15-22). */
 int yfm_param_count(int model_kind);
-/* State dimension M (3 DNS, 4 TVλ, 5 GNS5). */
+/* State dimension M (3 DNS, 4 TVλ, 5 GNS5; 3 for the λ kinds NS .. SRWSD-NS, P = 13 / 15 / 14 / 15 / 14). */
 int yfm_state_dim(int model_kind);
 /* Thread-local message for the last failing call on this thread ("" if none). */
 const char* yfm_last_error(void);
@@ -118,7 +134,9 @@ int yfm_set_panel(yfm_ctx* ctx, const double* Y, int N, int T, const double* mat
  * theta: P×B column-major.  T_use: NULL (every candidate uses all T columns) or
  * B window lengths, candidate b then evaluates get_loss(model, data[:, 1:T_use[b]])
  * (the expanding-window re-estimation of forecasting.jl:140-176), 1 ≤ T_use[b] ≤ T.
- * loglik_out: B doubles.  Synchronous. */
+ * loglik_out: B doubles.  Synchronous.
+ * For YFM_MODEL_NS .. YFM_MODEL_SRWSD_NS get_loss is src/models/filter.jl:209-243 (a window of one column gives
+ * 0.0; the divisor is nobs); a candidate's value is bitwise independent of the batch it is evaluated in. */
 int yfm_loglik_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                      const int* T_use, double* loglik_out);
 
@@ -135,13 +153,14 @@ int yfm_loglik_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const
 /* Filtered-state trajectories for parity checks: after every filter! call t
  * (t = 1..T-1), beta and P hold a_{t+1|t}, P_{t+1|t} (filter.jl:125-179).
  * beta_out: M × (T-1) × B, P_out: M × M × (T-1) × B (column-major), loglik_out: B.
- * Meant for small B (the output is O(B·T·M²)).  Synchronous. */
+ * Meant for small B (the output is O(B·T·M²)).  Synchronous.  Kalman kinds only: the λ kinds have no
+ * covariance and return YFM_EUNSUPPORTED (their trajectory is yfm_predict's). */
 int yfm_filter_states(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                       const int* T_use, double* beta_out, double* P_out, double* loglik_out);
 
 /* Length L of base.gamma, the observation-driven parameters predict reports as
  * `states` (kalmanbasemodel.jl:58): 1 for DNS (dns.jl:18) and TVλ (tvλdns.jl:19,
- * never set, so zeros), 2 for the GNS5 extension. */
+ * never set, so zeros), 2 for the GNS5 extension, 1 for the λ kinds (γ_t, mselambda.jl:29). */
 int yfm_gamma_dim(int model_kind);
 
 /* Batched predict — replaces, per candidate b,
@@ -153,7 +172,10 @@ int yfm_gamma_dim(int model_kind);
  *   preds N×ncol×B (preds[:, j] = ŷ for observation j+1), factors M×ncol×B,
  *   states L×ncol×B (L = yfm_gamma_dim), loadings_1 / loadings_2 N×ncol×B (Z[:,2],
  *   Z[:,3]; either may be NULL).  A candidate whose initialize_filter would throw
- *   gets NaN everywhere.  Synchronous. */
+ *   gets NaN everywhere.  Synchronous.
+ * λ kinds: predict of src/models/filter.jl:284-306 — column j holds the prediction, β, γ and Z[:,2], Z[:,3]
+ * AFTER the step on observation j; a step that returns −Inf (filter.jl:62-67) gives a −Inf prediction column
+ * and leaves the state as the failing call left it. */
 int yfm_predict(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B, const int* T_use,
                 int horizon, double* preds, double* factors, double* states, double* loadings_1,
                 double* loadings_2);
@@ -170,7 +192,9 @@ int yfm_forecast(yfm_ctx* ctx, int model_kind, int param_space, const double* th
  * the reference) followed by NaN.  A candidate for which the reference returns the
  * scalar -Inf (a non-finite step) gets -Inf in all its entries; NaN where
  * initialize_filter would throw.  K > 1 passes continue the filter state, as in the
- * reference; K > 1 requires T_use = NULL.  Synchronous. */
+ * reference; K > 1 requires T_use = NULL.  Synchronous.
+ * λ kinds: get_loss_array of src/models/filter.jl:245-281 — entry t is −‖y_{t+1} − ŷ_t‖²/N/K and entry 1 is a
+ * real value; K = 1 only (K > 1 returns YFM_EUNSUPPORTED). */
 int yfm_loss_array(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                    const int* T_use, int K, double* mse_out);
 
@@ -187,7 +211,8 @@ int yfm_loss_array(yfm_ctx* ctx, int model_kind, int param_space, const double* 
  * init_p, optimization.jl:157-184, :298-302), ll_out R
  * (the reference's returned ll), status_out R (or NULL): 0 ok, 1 the reference would
  * throw (NaN outputs), 2 aborted after the first group iteration (parameters kept);
- * n_evals_out (or NULL): objective evaluations performed.  Synchronous. */
+ * n_evals_out (or NULL): objective evaluations performed.  Synchronous.  Kalman kinds only: the λ kinds'
+ * parameter groups need other optimisers (optimization.jl:442-479) and return YFM_EUNSUPPORTED. */
 int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const double* theta0, int P, int R,
                  const int* T_use, int iterations, double g_tol, int max_group_iters, double tol,
                  double* theta_c_out, double* p_out, double* init_c_out, double* ll_out, int* status_out,

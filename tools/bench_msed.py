@@ -1,0 +1,114 @@
+"""Cost of the batched loss of the static and score-driven λ models (csrc/yfm_msed.hip).
+
+    python tools/bench_msed.py [--T 600] [--reps 7] [--warmup 2] [--kinds 3,4,5,6,8]
+
+Three cases on the N = 30 grid, one yfm_loglik_batch_device launch each, HIP events around the launch, `warmup`
+untimed launches, the median of `reps` with min–max:
+  (a) the try_initializations grid of one window: the start and its 30 trials, 31 candidates;
+  (b) the rolling driver's grid: 240 T_use windows × 31 candidates = 7,440;
+  (c) 65,536 candidates (SD-NS only unless --all-kinds), T = 600.
+For scale: the Float64 NumPy restatement (tests/msed_reference.py) on (a), wall clock, and the project's own
+yfm_loglik_batch_device for DNS at the same B.  Prints one JSON line.  Not part of bench.py.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "yieldfactormodels.jl_amd"))
+sys.path.insert(0, str(ROOT / "tests"))
+
+import msed_reference as R  # noqa: E402
+from yfm_amd import KIND_DNS, KIND_SD_NS, Engine, n_params  # noqa: E402
+from yfm_amd import models as M  # noqa: E402
+from yfm_amd import params as P  # noqa: E402
+from yfm_amd import synthetic as S  # noqa: E402
+
+
+def timed(run, stream):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record(stream)
+    run()
+    e1.record(stream)
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def launch_stats(eng, kind, Th, space, tu, reps, warmup):
+    stream = torch.cuda.current_stream()
+    B = Th.shape[1]
+    d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
+    d_tu = None if tu is None else torch.from_numpy(np.ascontiguousarray(tu, dtype=np.int32)).cuda()
+    d_out = torch.empty(B, dtype=torch.float64, device="cuda")
+    run = lambda: eng.loglik_device(kind, d_th.data_ptr(), Th.shape[0], B, d_out.data_ptr(), space=space,
+                                    d_T_use=None if d_tu is None else d_tu.data_ptr(), stream=stream.cuda_stream)
+    for _ in range(warmup):
+        run()
+    torch.cuda.synchronize()
+    t = [timed(run, stream) for _ in range(reps)]
+    out = d_out.cpu().numpy()
+    return {"B": B, "ms_median": statistics.median(t), "ms_min": min(t), "ms_max": max(t),
+            "finite": int(np.isfinite(out).sum())}
+
+
+def grid(kind):
+    """The start and its (A, B) trials, constrained (P × 31, or P × 7 without B)."""
+    start = S.theta0_constrained(kind)
+    cols = [start]
+    k = 1
+    while (p := R.trial_params(kind, start, k)) is not None:
+        cols.append(p)
+        k += 1
+    return np.asfortranarray(np.stack(cols, axis=1))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=600)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--kinds", default="3,4,5,6,8")
+    ap.add_argument("--big", type=int, default=65536)
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    eng = Engine(0)
+    mats = S.maturities_30()
+    Y = S.simulate_panel(KIND_SD_NS, args.T, maturities=mats)
+    eng.set_panel(Y, mats)
+    res = {"T": args.T, "N": len(mats), "cases": {}}
+    windows = np.linspace(args.T - 239, args.T, 240).astype(np.int32)
+    for kind in [int(k) for k in args.kinds.split(",")]:
+        name = P.KIND_NAMES[kind]
+        G = grid(kind) if kind != P.KIND_NS else S.theta_batch(kind, 31, seed=5, bad_frac=0.0)
+        space = 1 if kind != P.KIND_NS else 0
+        n = G.shape[1]
+        r = {"a_grid": launch_stats(eng, kind, G, space, None, args.reps, args.warmup)}
+        r["b_windows"] = launch_stats(eng, kind, np.asfortranarray(np.tile(G, (1, 240))), space, np.repeat(windows, n),
+                                      args.reps, args.warmup)
+        if kind == KIND_SD_NS:
+            Th = S.theta_batch(kind, args.big, seed=5, bad_frac=0.0)
+            r["c_big"] = launch_stats(eng, kind, Th, 0, None, args.reps, args.warmup)
+            t0 = time.perf_counter()
+            for b in range(n):
+                R.get_loss(kind, mats, Y, G[:, b], space, R.FLOAT)
+            r["a_grid_numpy_restatement_ms"] = 1e3 * (time.perf_counter() - t0)
+        res["cases"][name] = r
+    # the project's own DNS loglik at the same batch sizes
+    dns = {}
+    for B in (31, 7440, args.big):
+        dns[str(B)] = launch_stats(eng, KIND_DNS, S.theta_batch(KIND_DNS, B, seed=5, bad_frac=0.0), 0, None, args.reps,
+                                   args.warmup)
+    res["dns_loglik"] = dns
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()

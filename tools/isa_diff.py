@@ -67,6 +67,10 @@ def main() -> int:
             d.mkdir()
         tar = subprocess.run(["git", "-C", str(ROOT), "archive", rev, str(CSRC), "include"], check=True, capture_output=True)
         subprocess.run(["tar", "-x", "-C", str(old)], input=tar.stdout, check=True)
+        # a translation unit the revision does not have is new: nothing to compare it with
+        for s in [s for s in stems if not (old / CSRC / f"{s}.hip").exists()]:
+            print(f"{s}: new translation unit (not in {rev})")
+            stems.remove(s)
         jobs = [(r, s, Path(tmp) / o) for s in stems for r, o in ((old, "a"), (ROOT, "b"))]
         with ThreadPoolExecutor(max_workers=4) as ex:
             files = list(ex.map(lambda j: compile_s(*j), jobs))

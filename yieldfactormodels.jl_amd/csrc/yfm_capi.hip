@@ -38,11 +38,16 @@ int set_error(int code, const char* fmt, ...) {
     if (_e != hipSuccess) return set_error(YFM_EHIP, "%s: %s", #expr, hipGetErrorString(_e)); \
   } while (0)
 
-int state_dim(int kind) { return kind == YFM_MODEL_DNS ? 3 : kind == YFM_MODEL_TVL ? 4 : kind == YFM_MODEL_GNS5 ? 5 : -1; }
+int state_dim(int kind) {
+  if (yfm::msed_kind(kind)) return 3;  // the λ models' β (msebasemodel.jl:64, staticbasemodel.jl:40)
+  return kind == YFM_MODEL_DNS ? 3 : kind == YFM_MODEL_TVL ? 4 : kind == YFM_MODEL_GNS5 ? 5 : -1;
+}
 int n_lead(int kind) { return kind == YFM_MODEL_DNS ? 1 : kind == YFM_MODEL_TVL ? 0 : 2; }
-// L = length of base.gamma (kalmanbasemodel.jl:58): DNS 1 (dns.jl:18), TVλ 1 (tvλdns.jl:19, never set), GNS5 2
+// L = length of base.gamma (kalmanbasemodel.jl:58): DNS 1 (dns.jl:18), TVλ 1 (tvλdns.jl:19, never set), GNS5 2,
+// the λ models 1 (mselambda.jl:29, staticlambda.jl:20)
 int gamma_dim(int kind) { return kind == YFM_MODEL_GNS5 ? 2 : (state_dim(kind) < 0 ? -1 : 1); }
 int param_count(int kind) {
+  if (yfm::msed_kind(kind)) return yfm::msed_param_count(kind);
   const int M = state_dim(kind);
   if (M < 0) return -1;
   return n_lead(kind) + 1 + M * (M + 1) / 2 + M + M * M;
@@ -120,6 +125,11 @@ int check_batch(yfm_ctx* ctx, int kind, int space, int P, int B) {
     return set_error(YFM_EINVAL, "P = %d but model_kind %d has %d parameters", P, kind, param_count(kind));
   if (B < 0) return set_error(YFM_EINVAL, "B = %d < 0", B);
   if (ctx->T <= 0) return set_error(YFM_ENOPANEL, "no panel: call yfm_set_panel first");
+  if (yfm::msed_kind(kind)) {
+    if (ctx->N > yfm::msed_max_n())
+      return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the λ-model kernel's %d", ctx->N, yfm::msed_max_n());
+    return YFM_OK;
+  }
   if (kind == YFM_MODEL_TVL) {
     if (ctx->N > yfm::tvl_max_n())
       return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the TVλ kernel's %d", ctx->N, yfm::tvl_max_n());
@@ -263,6 +273,7 @@ struct Launch {
   const PanelView* panel = nullptr;  // nullptr: the context's panel
   bool continues = false;  // a later chunk of a pipelined batch: accumulates into the previous chunk's counters
   int share = 1;           // launches of this size the caller keeps in flight at once (yfm::loglik_device_ws)
+  const yfm::MsedRecord* msed_rec = nullptr;  // λ models: the trajectory outputs this launch writes (nullptr: the loss)
 };
 
 // The plain log-likelihood launch, in the argument order of yfm_loglik_batch_device.
@@ -323,7 +334,10 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
   }
   a.stream = s;
   hipError_t e;
-  if (q.kind == YFM_MODEL_TVL) {
+  if (yfm::msed_kind(q.kind)) {
+    const int lanes = yfm::msed_lanes_for(B);
+    e = q.msed_rec ? yfm::launch_msed_record(q.kind, a, lanes, *q.msed_rec) : yfm::launch_msed(q.kind, a, lanes);
+  } else if (q.kind == YFM_MODEL_TVL) {
     int lanes = yfm::tvl_lanes_for(B, ctx->N, q.share);
     const char* const ov = yfm::env_or("YFM_TVL_LANES", nullptr);  // tuning override: 1, 2, 4, …, 64
     if (ov) {
@@ -742,6 +756,9 @@ int yfm_filter_states(yfm_ctx* ctx, int model_kind, int param_space, const doubl
                       const int* T_use, double* beta_out, double* P_out, double* loglik_out) {
   if (int r = check_ctx(ctx)) return r;
   if (int r = check_batch(ctx, model_kind, param_space, P, B)) return r;
+  if (yfm::msed_kind(model_kind))
+    return set_error(YFM_EUNSUPPORTED, "yfm_filter_states is built for the Kalman kinds only: model_kind %d has no "
+                     "covariance trajectory (use yfm_predict)", model_kind);
   if (B > 0 && (!theta || !beta_out || !P_out || !loglik_out)) return set_error(YFM_EINVAL, "null pointer argument");
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
   if (B == 0 || ctx->T < 2) {
@@ -806,19 +823,41 @@ int yfm_predict(yfm_ctx* ctx, int model_kind, int param_space, const double* the
   Launch q;
   if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
   q.horizon = horizon;
-  q.rec_len = ctx->T + horizon;  // every step of the longest candidate
-  if (int r = run_trajectory(ctx, q)) return r;
   // outputs: one device block [preds | load1 | load2 | factors | states]
   const size_t nN = (size_t)N * ncol * B, nM = (size_t)M * ncol * B, nL = (size_t)L * ncol * B;
   YFM_HIP_CHECK(ctx->rec_P.ensure(sizeof(double) * (3 * nN + nM + nL)));
   double* d = static_cast<double*>(ctx->rec_P.p);
-  yfm::PredictArgs a = predict_args(ctx, q, horizon);
+  yfm::PredictArgs a{};
   a.preds = d;
   a.load1 = loadings_1 ? d + nN : nullptr;
   a.load2 = loadings_2 ? d + 2 * nN : nullptr;
   a.factors = d + 3 * nN;
   a.states = d + 3 * nN + nM;
-  YFM_HIP_CHECK(yfm::launch_predict_emit(a));
+  if (yfm::msed_kind(model_kind)) {
+    // the λ kernel writes the outputs itself, into a NaN-filled block
+    YFM_HIP_CHECK(hipMemsetAsync(d, 0xff, sizeof(double) * (3 * nN + nM + nL), ctx->stream));
+    yfm::MsedRecord rec;
+    rec.mode = 1;
+    rec.horizon = horizon;
+    rec.ncol = (int)ncol;
+    rec.preds = a.preds;
+    rec.factors = a.factors;
+    rec.states = a.states;
+    rec.load1 = a.load1;
+    rec.load2 = a.load2;
+    q.msed_rec = &rec;
+    if (int r = launch(ctx, q)) return r;
+  } else {
+    q.rec_len = ctx->T + horizon;  // every step of the longest candidate
+    if (int r = run_trajectory(ctx, q)) return r;
+    yfm::PredictArgs full = predict_args(ctx, q, horizon);
+    full.preds = a.preds;
+    full.load1 = a.load1;
+    full.load2 = a.load2;
+    full.factors = a.factors;
+    full.states = a.states;
+    YFM_HIP_CHECK(yfm::launch_predict_emit(full));
+  }
   YFM_HIP_CHECK(hipMemcpyAsync(preds, a.preds, sizeof(double) * nN, hipMemcpyDeviceToHost, ctx->stream));
   if (loadings_1)
     YFM_HIP_CHECK(hipMemcpyAsync(loadings_1, a.load1, sizeof(double) * nN, hipMemcpyDeviceToHost, ctx->stream));
@@ -842,13 +881,26 @@ int yfm_forecast(yfm_ctx* ctx, int model_kind, int param_space, const double* th
   Launch q;
   if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
   q.horizon = horizon;
-  q.rec_len = horizon + 1;
-  if (int r = run_trajectory(ctx, q)) return r;
   const size_t n = (size_t)(M + L + N) * horizon * B;
   YFM_HIP_CHECK(ctx->rec_P.ensure(sizeof(double) * n));
-  yfm::PredictArgs a = predict_args(ctx, q, horizon);
+  yfm::PredictArgs a{};
   a.preds = static_cast<double*>(ctx->rec_P.p);
-  YFM_HIP_CHECK(yfm::launch_forecast_emit(a));
+  if (yfm::msed_kind(model_kind)) {
+    YFM_HIP_CHECK(hipMemsetAsync(a.preds, 0xff, sizeof(double) * n, ctx->stream));
+    yfm::MsedRecord rec;
+    rec.mode = 2;
+    rec.horizon = horizon;
+    rec.preds = a.preds;
+    q.msed_rec = &rec;
+    if (int r = launch(ctx, q)) return r;
+  } else {
+    q.rec_len = horizon + 1;
+    if (int r = run_trajectory(ctx, q)) return r;
+    double* const blocks = a.preds;
+    a = predict_args(ctx, q, horizon);
+    a.preds = blocks;
+    YFM_HIP_CHECK(yfm::launch_forecast_emit(a));
+  }
   YFM_HIP_CHECK(hipMemcpyAsync(out, a.preds, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
   YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return YFM_OK;
@@ -863,9 +915,26 @@ int yfm_loss_array(yfm_ctx* ctx, int model_kind, int param_space, const double* 
   if (B > 0 && (!theta || !mse_out)) return set_error(YFM_EINVAL, "null pointer argument");
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
   const int T1 = ctx->T - 1;
+  if (yfm::msed_kind(model_kind) && K > 1)
+    return set_error(YFM_EUNSUPPORTED, "K = %d passes are not built for model_kind %d (K = 1 only)", K, model_kind);
   if (B == 0 || T1 <= 0) return YFM_OK;
   Launch q;
   if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  if (yfm::msed_kind(model_kind)) {
+    // get_loss_array of filter.jl:245-281: the λ kernel writes the rows itself (NaN beyond each window)
+    const size_t nb = sizeof(double) * (size_t)T1 * B;
+    YFM_HIP_CHECK(ctx->rec_P.ensure(nb));
+    YFM_HIP_CHECK(hipMemsetAsync(ctx->rec_P.p, 0xff, nb, ctx->stream));
+    yfm::MsedRecord rec;
+    rec.mode = 3;
+    rec.ncol = T1;
+    rec.preds = static_cast<double*>(ctx->rec_P.p);
+    q.msed_rec = &rec;
+    if (int r = launch(ctx, q)) return r;
+    YFM_HIP_CHECK(hipMemcpyAsync(mse_out, rec.preds, nb, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return YFM_OK;
+  }
   PanelView pv{static_cast<const double*>(ctx->raw.p), static_cast<const double*>(ctx->panel.p), ctx->T};
   if (K > 1) {
     // the K passes continue the filter state (filter.jl:221-242 never re-initialises):

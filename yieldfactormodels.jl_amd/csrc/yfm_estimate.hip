@@ -228,6 +228,9 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
                             int* status_out, long long* n_evals_out) {
   if (!ctx) return yfm::api_error(YFM_EINVAL, "null context");
   if (yfm_param_count(model_kind) < 0) return yfm::api_error(YFM_EINVAL, "unknown model_kind");
+  if (yfm::msed_kind(model_kind))
+    return yfm::api_error(YFM_EUNSUPPORTED, "yfm_estimate is built for the Kalman kinds only: the λ kinds' parameter "
+                          "groups need other optimisers (optimization.jl:442-479)");
   if (P != yfm_param_count(model_kind)) return yfm::api_error(YFM_EINVAL, "P does not match model_kind");
   if (param_space != YFM_THETA_UNCONSTRAINED && param_space != YFM_THETA_CONSTRAINED)
     return yfm::api_error(YFM_EINVAL, "unknown param_space");

@@ -120,6 +120,28 @@ int tvl_dd_lanes_for(int B, int N, int want, int share = 1);
 hipError_t launch_tvl_dd_colsum(const double* Y, int N, int T, double* colsum, hipStream_t s);
 hipError_t launch_tvl_dd_init(const LaunchArgs& a, double* rec_dd);
 hipError_t launch_tvl_dd(const LaunchArgs& a, const double* rec_dd, const double* colsum, const TvlGaps& g, int lanes);
+// Static and score-driven λ models (yfm_msed.hip: NS, SD-NS, RWSD-NS, SSD-NS, SRWSD-NS; src/models/filter.jl:52-110).
+// msed_kind: the kind is one of them; msed_param_count: P (−1 for another kind); msed_lanes_for: lanes per
+// candidate for a batch (4 or 16 — a candidate's value does not depend on it).  launch_msed writes get_loss
+// (filter.jl:209-243) into a.out and counts the −Inf candidates in a.flags[1]; it zeroes a.flags_next.
+bool msed_kind(int kind);
+int msed_param_count(int kind);
+int msed_max_n();
+int msed_lanes_for(int B);
+hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes);
+// The same recursion writing its trajectory straight into the caller's (NaN-prefilled) device outputs:
+// mode 1 predict (filter.jl:284-306), 2 forecast blocks (forecasting.jl:236-250), 3 get_loss_array (filter.jl:245-281).
+struct MsedRecord {
+  int mode = 0;
+  int horizon = 1;            // predict / forecast
+  int ncol = 0;               // predict: T + horizon − 1 columns per candidate; loss array: T − 1
+  double* preds = nullptr;    // predict: N×ncol×B; forecast: (3 + 1 + N)×h×B; loss array: ncol×B
+  double* factors = nullptr;  // predict: 3×ncol×B
+  double* states = nullptr;   // predict: 1×ncol×B
+  double* load1 = nullptr;    // predict: N×ncol×B or nullptr
+  double* load2 = nullptr;
+};
+hipError_t launch_msed_record(int kind, const LaunchArgs& a, int lanes, const MsedRecord& r);
 // Trajectory outputs (yfm_predict.hip) from a recorded state trajectory.
 struct PredictArgs {
   int kind, M, L, N, P, B, T;

@@ -1,0 +1,472 @@
+// yfm_msed.hip — batched loss, per-step loss array, predict and forecast of the static and score-driven
+// λ Nelson–Siegel models (NS, SD-NS, RWSD-NS, SSD-NS, SRWSD-NS) for gfx950.  FP64.
+//
+// Restates, per candidate θ_b (the algebra is in yfm_msed.hpp, which names the model files):
+//   get_loss         src/models/filter.jl:209-243
+//   get_loss_array   src/models/filter.jl:245-281
+//   predict          src/models/filter.jl:284-306
+//   forecast blocks  src/forecasting.jl:236-250
+//   filter           src/models/filter.jl:52-110
+//
+// Mapping, the one of yfm_tvl.hip for the same reason — the loadings are recomputed every
+// step, so a step is O(N): ONE CANDIDATE PER GROUP OF L LANES, lane j owns the maturities i ≡ j (mod L), the
+// statistics are reduced over the group with DPP butterflies (no LDS reduction) and every lane of the group
+// runs the same 3×3 work, so the state stays replicated in VGPRs.  L ∈ {4, 16} is chosen per launch from B (one
+// candidate per lane was built and dropped: its part of the tree below holds five sets of statistics and spilled).
+//
+// A candidate's value does not depend on L: the sums are formed over 16 residue classes of the maturity
+// index (class c holds i ≡ c mod 16, added in order of i) combined by one fixed tree — class bit 3 first,
+// bit 0 last.  A lane forms the part of the tree over its own classes in registers and the group finishes
+// it with true xor exchanges in descending order.
+//
+// One pass per loading evaluation: the first pass of step t, at the loadings step t − 1 predicted with, also
+// forms ‖y_t − ŷ_t‖² of get_loss against that prediction (and, in record mode, writes the prediction and the
+// loading columns of step t − 1); the second pass, at the updated γ, serves the second OLS.  The static model
+// has only the first; the two scaled kinds add a refinement pass at the first loadings (yfm_msed.hpp).
+//
+// Panel: the caller's raw N×T column-major matrix, staged as yfm_tvl.hip stages it (TC columns in LDS, the
+// next chunk prefetched into registers).  The missing-data test is the reference's isnan(y[1]) on the raw
+// column, not the prepared panel's any-NaN flag.
+#pragma clang fp contract(off)
+#include "yfm_device.hpp"
+#include "yfm_internal.hpp"
+#include "yfm_msed.hpp"
+
+namespace yfm {
+
+namespace {
+
+constexpr int kMsedBlock = 256;
+constexpr int kMsedPre = 8;      // panel doubles prefetched per thread per chunk
+constexpr int kMsedClasses = 16;  // residue classes of the summation tree (the largest L)
+
+using namespace msed;
+
+// the statistics of one pass
+template <bool SCORE>
+struct Stats {
+  double o[NOLS];
+  double d[SCORE ? NSCORE : 1];
+  double vv;
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int k = 0; k < NOLS; ++k) o[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < (SCORE ? NSCORE : 1); ++k) d[k] = 0.0;
+    vv = 0.0;
+  }
+  template <class F>
+  __device__ __forceinline__ void each(F&& f) {
+#pragma unroll
+    for (int k = 0; k < NOLS; ++k) o[k] = f(o[k]);
+    if constexpr (SCORE) {
+#pragma unroll
+      for (int k = 0; k < NSCORE; ++k) d[k] = f(d[k]);
+    }
+    vv = f(vv);
+  }
+  __device__ __forceinline__ void add(const Stats& a, const Stats& b) {
+#pragma unroll
+    for (int k = 0; k < NOLS; ++k) o[k] = a.o[k] + b.o[k];
+    if constexpr (SCORE) {
+#pragma unroll
+      for (int k = 0; k < NSCORE; ++k) d[k] = a.d[k] + b.d[k];
+    } else {
+      d[0] = 0.0;
+    }
+    vv = a.vv + b.vv;
+  }
+};
+
+// the statistics of the scaled kinds' refinement pass
+struct Refine {
+  double r[NREFINE];
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int k = 0; k < NREFINE; ++k) r[k] = 0.0;
+  }
+  __device__ __forceinline__ void add(const Refine& a, const Refine& b) {
+#pragma unroll
+    for (int k = 0; k < NREFINE; ++k) r[k] = a.r[k] + b.r[k];
+  }
+};
+
+// x + (x of lane ^ 2^LVL): quad_perm for 1 and 2, ds_swizzle (the LDS crossbar, no memory) for 4, row_ror:8 for 8
+template <int LVL>
+__device__ __forceinline__ double xor_sum(double x) {
+  const int lo = __double2loint(x), hi = __double2hiint(x);
+  int plo, phi;
+  if constexpr (LVL == 2) {
+    constexpr int pat = (4 << 10) | 0x1f;  // bit-mask mode: and 0x1f, or 0, xor 4
+    plo = __builtin_amdgcn_ds_swizzle(lo, pat);
+    phi = __builtin_amdgcn_ds_swizzle(hi, pat);
+  } else {
+    constexpr int ctrl = LVL == 0 ? 0xB1 : LVL == 1 ? 0x4E : 0x128;
+    plo = __builtin_amdgcn_mov_dpp(lo, ctrl, 0xf, 0xf, true);
+    phi = __builtin_amdgcn_mov_dpp(hi, ctrl, 0xf, 0xf, true);
+  }
+  return x + __hiloint2double(phi, plo);
+}
+
+// the group's part of the tree: lane bits in descending order
+template <int L>
+__device__ __forceinline__ double group_sum_desc(double x) {
+  if constexpr (L >= 16) x = xor_sum<3>(x);
+  if constexpr (L >= 8) x = xor_sum<2>(x);
+  if constexpr (L >= 4) x = xor_sum<1>(x);
+  if constexpr (L >= 2) x = xor_sum<0>(x);
+  return x;
+}
+
+// a lane's part: the classes that agree with c in the bits below 4 − K; the node's last addition joins the
+// lowest of its free bits
+template <int K, class S, class Leaf>
+__device__ __forceinline__ void class_tree(int c, Leaf& leaf, S& s) {
+  if constexpr (K == 0) {
+    leaf(c, s);
+  } else {
+    S a, b;
+    class_tree<K - 1>(c, leaf, a);
+    class_tree<K - 1>(c | (kMsedClasses >> K), leaf, b);
+    s.add(a, b);
+  }
+}
+
+template <int L>
+constexpr int log_classes_per_lane() {
+  static_assert(L == 16 || L == 4, "lane counts the summation tree is built for");
+  return L == 16 ? 0 : 2;
+}
+
+struct MsedOut {
+  int mode;          // 0 loss, 1 predict, 2 forecast blocks, 3 loss array
+  int horizon;       // predict / forecast: NaN-padding columns + 1
+  int ncol;          // predict: columns per candidate (T + horizon − 1); loss array: T − 1
+  double* preds;     // predict: N×ncol×B; forecast: (4 + N)×h×B; loss array: ncol×B
+  double* factors;   // predict: 3×ncol×B
+  double* states;    // predict: 1×ncol×B
+  double* load1;     // predict: N×ncol×B or nullptr
+  double* load2;
+};
+
+template <int L, bool STATIC, bool HASB, bool SCALED, bool RECORD>
+__global__ __launch_bounds__(kMsedBlock) void msed_kernel(const double* __restrict__ theta, int P, int B, int space,
+                                                           const double* __restrict__ Y, int T, int N, int TC,
+                                                           const double* __restrict__ mats,
+                                                           const int* __restrict__ T_use, double* __restrict__ out,
+                                                           unsigned int* __restrict__ flags,
+                                                           unsigned int* __restrict__ flags_next, MsedOut ro) {
+  constexpr int GPB = kMsedBlock / L;
+  constexpr int KQ = log_classes_per_lane<L>();
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double2* s_mr = reinterpret_cast<double2*>(smem);  // (m_i, 1/m_i)
+  double* s_y = smem + 2 * N;                         // TC columns of N yields
+  __shared__ int s_iters_max;
+
+  const int tid = threadIdx.x;
+  if (flags_next && blockIdx.x == 0 && tid < kFlagsPerBank) flags_next[tid] = 0u;  // the next launch's counters
+  const int j = tid % L;
+  const int grp = tid / L;
+  const int b = blockIdx.x * GPB + grp;
+  const bool live = b < B;
+  const int bb = live ? b : (B - 1);
+  const int nobs = T_use ? T_use[bb] : T;
+
+  if (tid == 0) s_iters_max = 0;
+  for (int i = tid; i < N; i += kMsedBlock) {
+    const double m = mats[i];
+    s_mr[i] = make_double2(m, 1.0 / m);
+  }
+  __syncthreads();
+  // steps: the filter calls; iteration t runs the first pass on column t — the comparison and the outputs of
+  // step t − 1 — and then step t, so there is one iteration more than steps
+  const bool traj = RECORD && (ro.mode == 1 || ro.mode == 2);
+  const int my_steps = traj ? nobs + ro.horizon - 1 : nobs - 1;
+  const int my_iters = my_steps + 1;
+  atomicMax(&s_iters_max, live ? my_iters : 0);
+
+  Model mdl;
+  State st;
+  decode<STATIC, HASB>(theta + (size_t)bb * P, space, mdl);
+  init_state(mdl, st);
+  const double fN = (double)N;
+
+  double mse = 0.0;
+  bool fail = false;       // get_loss / get_loss_array return −Inf
+  bool pred_fail = false;  // the last step returned −Inf instead of a prediction
+
+  __syncthreads();
+  const int niter = s_iters_max;
+  const int CHY = TC * N;
+
+  // ---- panel staging: chunk c (columns cTC .. cTC+TC−1) in LDS, chunk c+1 in registers ----
+  double pre[kMsedPre];
+  auto load_chunk = [&](int c) {
+    const size_t base = (size_t)c * CHY;
+    const size_t lim = (size_t)T * N;
+#pragma unroll
+    for (int r = 0; r < kMsedPre; ++r) {
+      const int e = r * kMsedBlock + tid;
+      const size_t g = base + e;
+      pre[r] = (e < CHY && g < lim) ? Y[g] : 0.0;
+    }
+  };
+  auto store_chunk = [&]() {
+#pragma unroll
+    for (int r = 0; r < kMsedPre; ++r) {
+      const int e = r * kMsedBlock + tid;
+      if (e < CHY) s_y[e] = pre[r];
+    }
+  };
+  if (niter > 0) {
+    load_chunk(0);
+    store_chunk();
+    __syncthreads();
+    load_chunk(1);
+  }
+
+  for (int t = 0; t < niter; ++t) {
+    const int tt = t % TC;
+    const bool act = live && t < my_iters;
+    if (act) {
+      const double* col = s_y + tt * N;
+      const bool has_col = t < nobs;                     // a data column (the rest is the NaN padding)
+      const bool compare = !traj && t >= 1;              // y_t against the prediction of step t − 1 (t < nobs here)
+      const bool emit = traj && t >= 1;                  // outputs of step t − 1
+      // where the per-maturity outputs of step t − 1 go
+      double *e_pred = nullptr, *e_l1 = nullptr, *e_l2 = nullptr;
+      if constexpr (RECORD) {
+        if (emit && ro.mode == 1) {
+          const size_t o = ((size_t)b * ro.ncol + (t - 1)) * N;
+          e_pred = ro.preds + o;
+          e_l1 = ro.load1 ? ro.load1 + o : nullptr;
+          e_l2 = ro.load2 ? ro.load2 + o : nullptr;
+        } else if (emit && ro.mode == 2) {
+          const int k = (t - 1) - (nobs - 1);
+          if (k >= 0) e_pred = ro.preds + ((size_t)b * ro.horizon + k) * (4 + N) + 4;
+        }
+      }
+      // ---- first pass: the loadings at γ ----
+      const Lambda la = make_lambda(st.gamma);
+      const double ninf = -__builtin_inf();
+      Stats<!STATIC> sa;
+      auto leaf_a = [&](int c, Stats<!STATIC>& s) {
+        s.zero();
+        for (int i = c; i < N; i += kMsedClasses) {
+          const double2 mr = s_mr[i];
+          double z, z2, z3;
+          loadings(la, mr.x, mr.y, z, z2, z3);
+          const double y = has_col ? col[i] : 0.0;
+          accum_ols(s.o, z2, z3, y);
+          if constexpr (!STATIC) {
+            double d2, d3;
+            dloadings(la, mr.x, z, z2, d2, d3);
+            accum_score(s.d, z2, z3, d2, d3, y);
+          }
+          const double pr = fitted(st.beta, z2, z3);
+          const double v = y - pr;
+          s.vv = mfma(v, v, s.vv);
+          if constexpr (RECORD) {
+            if (e_pred) e_pred[i] = pred_fail ? ninf : pr;
+            if (e_l1) e_l1[i] = z2;
+            if (e_l2) e_l2[i] = z3;
+          }
+        }
+      };
+      class_tree<KQ>(j, leaf_a, sa);
+      sa.each([](double x) { return group_sum_desc<L>(x); });
+
+      if (compare) {
+        // v = y_t − ŷ_t; mse −= v'v; a non-finite running sum returns −Inf (filter.jl:226-234, :263-270)
+        const double step = pred_fail ? ninf : -sa.vv;
+        mse += step;
+        fail = fail || !(fabs(mse) <= __DBL_MAX__);
+        if constexpr (RECORD) {
+          if (ro.mode == 3) {
+            fail = fail || !(fabs(step) <= __DBL_MAX__);
+            if (j == 0) ro.preds[(size_t)b * ro.ncol + (t - 1)] = step / fN;
+          }
+        }
+      }
+
+      if (t < my_steps) {
+        // ---- step t (filter.jl:52-110) ----
+        const bool y0nan = !has_col || (col[0] != col[0]);
+        pred_fail = false;
+        if (y0nan) {
+          advance<HASB>(mdl, st);
+        } else if (bool ridged = false; !ols(sa.o, fN, st.beta, ridged)) {
+          pred_fail = true;
+        } else {
+          bool ok = true;
+          if constexpr (!STATIC) {
+            double g;
+            if constexpr (SCALED) {
+              // ---- refinement pass (yfm_msed.hpp): the residual at β with its rounding errors carried ----
+              Refine sr;
+              auto leaf_r = [&](int c, Refine& s) {
+                s.zero();
+                for (int i = c; i < N; i += kMsedClasses) {
+                  const double2 mr = s_mr[i];
+                  double z, z2, z3, d2, d3;
+                  loadings(la, mr.x, mr.y, z, z2, z3);
+                  dloadings(la, mr.x, z, z2, d2, d3);
+                  accum_refine(s.r, st.beta, z2, z3, d2, d3, col[i]);
+                }
+              };
+              class_tree<KQ>(j, leaf_r, sr);
+#pragma unroll
+              for (int k = 0; k < NREFINE; ++k) sr.r[k] = group_sum_desc<L>(sr.r[k]);
+              g = score_refined(sa.o, fN, ridged, sa.d, sr.r, st.beta);
+            } else {
+              g = score(sa.d, st.beta);
+            }
+            update_gamma<SCALED>(mdl, st, g);
+            // ---- second pass: the loadings at the updated γ ----
+            const Lambda lb = make_lambda(st.gamma);
+            Stats<false> sb;
+            auto leaf_b = [&](int c, Stats<false>& s) {
+              s.zero();
+              for (int i = c; i < N; i += kMsedClasses) {
+                const double2 mr = s_mr[i];
+                double z, z2, z3;
+                loadings(lb, mr.x, mr.y, z, z2, z3);
+                accum_ols(s.o, z2, z3, col[i]);
+              }
+            };
+            class_tree<KQ>(j, leaf_b, sb);
+#pragma unroll
+            for (int k = 0; k < NOLS; ++k) sb.o[k] = group_sum_desc<L>(sb.o[k]);
+            ok = ols(sb.o, fN, st.beta);
+          }
+          if (ok) {
+            advance<HASB>(mdl, st);
+          } else {
+            pred_fail = true;
+          }
+        }
+        if constexpr (RECORD) {
+          // factors and states of column t: β and γ after the step (filter.jl:299-300)
+          if (j == 0 && ro.mode == 1) {
+            const size_t o = (size_t)b * ro.ncol + t;
+#pragma unroll
+            for (int k = 0; k < kM; ++k) ro.factors[o * kM + k] = st.beta[k];
+            ro.states[o] = st.gamma;
+          } else if (j == 0 && ro.mode == 2) {
+            const int k = t - (nobs - 1);
+            if (k >= 0) {
+              double* o = ro.preds + ((size_t)b * ro.horizon + k) * (4 + N);
+#pragma unroll
+              for (int q = 0; q < kM; ++q) o[q] = st.beta[q];
+              o[kM] = st.gamma;
+            }
+          }
+        }
+      }
+    }
+    if (tt == TC - 1) {  // chunk done: its buffer takes the prefetched chunk, prefetch the one after
+      __syncthreads();
+      store_chunk();
+      __syncthreads();
+      load_chunk(t / TC + 2);
+    }
+  }
+
+  if (!live) return;
+  if constexpr (RECORD) {
+    if (ro.mode == 3) {
+      // a non-finite entry makes get_loss_array return the scalar −Inf (filter.jl:268-270): the whole row
+      if (fail) {
+        for (int k = j; k < nobs - 1; k += L) ro.preds[(size_t)b * ro.ncol + k] = -__builtin_inf();
+        if (j == 0) atomicAdd(&flags[1], 1u);
+      }
+      return;
+    }
+    if (traj) return;
+  }
+  if (j != 0) return;
+  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
+  if (fail) {
+    ll = -__builtin_inf();
+    atomicAdd(&flags[1], 1u);
+  }
+  out[b] = ll;
+}
+
+template <int L, bool STATIC, bool HASB, bool SCALED>
+hipError_t launch_variant(const LaunchArgs& a, int TC, const MsedOut* ro) {
+  constexpr int GPB = kMsedBlock / L;
+  const int grid = (a.B + GPB - 1) / GPB;
+  const size_t shmem = sizeof(double) * (size_t)(2 * a.N + TC * a.N);
+  if (ro) {
+    hipLaunchKernelGGL((msed_kernel<L, STATIC, HASB, SCALED, true>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
+                       a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags, a.flags_next,
+                       *ro);
+  } else {
+    hipLaunchKernelGGL((msed_kernel<L, STATIC, HASB, SCALED, false>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
+                       a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags, a.flags_next,
+                       MsedOut{});
+  }
+  return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_lanes(int kind, const LaunchArgs& a, int TC, const MsedOut* ro) {
+  switch (kind) {
+    case YFM_MODEL_NS: return launch_variant<L, true, false, false>(a, TC, ro);
+    case YFM_MODEL_SD_NS: return launch_variant<L, false, true, false>(a, TC, ro);
+    case YFM_MODEL_RWSD_NS: return launch_variant<L, false, false, false>(a, TC, ro);
+    case YFM_MODEL_SSD_NS: return launch_variant<L, false, true, true>(a, TC, ro);
+    case YFM_MODEL_SRWSD_NS: return launch_variant<L, false, false, true>(a, TC, ro);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_any(int kind, const LaunchArgs& a, int lanes, const MsedOut* ro) {
+  // columns per chunk: the prefetch registers hold ≤ kMsedPre·256 yields
+  int TC = (kMsedPre * kMsedBlock) / a.N;
+  if (TC > 32) TC = 32;
+  if (TC < 1 || a.N < 1) return hipErrorInvalidValue;
+  switch (lanes) {
+    case 4: return launch_lanes<4>(kind, a, TC, ro);
+    case 16: return launch_lanes<16>(kind, a, TC, ro);
+  }
+  return hipErrorInvalidValue;
+}
+
+}  // namespace
+
+bool msed_kind(int kind) { return msed::kind_known(kind); }
+
+int msed_param_count(int kind) { return msed::kind_known(kind) ? msed::kind_params(kind) : -1; }
+
+int msed_max_n() { return kMsedPre * kMsedBlock - 1; }
+
+int msed_lanes_for(int B) {
+  // 16 lanes per candidate until the groups fill two waves per SIMD of the chip's 1,024 (B = 8,192), then 4: the
+  // 3×3 work is replicated on every lane of a group, so fewer lanes per candidate is less work as soon as the
+  // chip is full either way.
+  const char* const ov = env_or("YFM_MSED_LANES", nullptr);  // tuning override: 4, 16
+  if (ov) {
+    const int l = std::atoi(ov);
+    if (l == 4 || l == 16) return l;
+  }
+  return B <= 8192 ? 16 : 4;
+}
+
+hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes) { return launch_any(kind, a, lanes, nullptr); }
+
+hipError_t launch_msed_record(int kind, const LaunchArgs& a, int lanes, const MsedRecord& r) {
+  MsedOut ro;
+  ro.mode = r.mode;
+  ro.horizon = r.horizon;
+  ro.ncol = r.ncol;
+  ro.preds = r.preds;
+  ro.factors = r.factors;
+  ro.states = r.states;
+  ro.load1 = r.load1;
+  ro.load2 = r.load2;
+  return launch_any(kind, a, lanes, &ro);
+}
+
+}  // namespace yfm

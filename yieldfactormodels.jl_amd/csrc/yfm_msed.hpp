@@ -1,0 +1,378 @@
+// yfm_msed.hpp — the algebra of the static and score-driven λ Nelson–Siegel models (NS, SD-NS, RWSD-NS,
+// SSD-NS, SRWSD-NS), as plain functions that compile for the device (yfm_msed.hip) and for the host
+// (tests/msed_host_check.cpp).
+//
+// Restates, per candidate θ_b (paths relative to the reference root):
+//   set_params!              src/models/msedriven/paramteroperations.jl:25-65, src/models/static/paramteroperations.jl:19-43
+//   transformations          src/models/msedriven/mselambda.jl:17-34, msebasemodel.jl:77-90, static/staticbasemodel.jl:48-59
+//   update_factor_loadings!  src/models/msedriven/mselambda.jl:63-76, src/models/static/staticlambda.jl:46-60
+//   filter (one step)        src/models/filter.jl:52-110
+//   get_β_OLS!               src/models/filter.jl:122-137
+//   get_grad_gamma!          src/models/filter.jl:168-184 (the exact derivative, no dual numbers)
+//   update_gamma_with_grad!  src/models/filter.jl:29-50
+//
+// One step needs the maturities only through sums, so a step is written as "accumulate the sufficient
+// statistics of every maturity, then do 3×3 work":
+//   OLS      G = Z'Z (G₁₁ = N and the five entries Σz₂, Σz₃, Σz₂², Σz₂z₃, Σz₃²) and Z'y (3);
+//   score    g = ∂(−‖y − Z(γ)β‖²)/∂γ = 2 v'(∂Z/∂γ)β with v = y − Zβ, expanded so that it needs no second
+//            pass over the maturities once β is known:
+//                g = 2 [ β₂ (d₂'y − d₂'Zβ) + β₃ (d₃'y − d₃'Zβ) ],   ∂Z/∂γ = [0, d₂, d₃]
+//            — the eight contractions d₂'[1 z₂ z₃], d₃'[1 z₂ z₃], d₂'y, d₃'y;
+//   loss     ‖y − ŷ‖² against the previous step's prediction ŷ = Z(γ)β, formed per maturity: the loadings
+//            a step starts from are the ones its predecessor predicted with, so the comparison of
+//            get_loss (filter.jl:226-230) shares the first pass of the next step.
+// The scaled kinds divide the score by the root of its own running mean square, which turns any rounding noise in
+// a score that is exactly zero (N = 3: OLS interpolates and v = 0) into a step of ±A.  They therefore evaluate the
+// score at the refined β: one more pass forms the residual v = y − Zβ with its rounding errors carried, Z'v and
+// v'(∂Z/∂γ)β, one correction δβ = (Z'Z)⁻¹Z'v reuses the factorisation's branch, and g = 2[v'w − δβ'Z'w].
+// The Cholesky pivots are formed without fused multiply-adds (contraction is off and no fma is written
+// there): a pivot that is exactly zero as LAPACK forms it — N = 1, or λ = Inf — is exactly zero here, so
+// the ridge retry of filter.jl:128-135 runs for the same candidates.
+#pragma once
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define YFM_MHD __host__ __device__ __forceinline__
+#else
+#include <math.h>
+#include <stddef.h>
+#define YFM_MHD inline
+#endif
+
+namespace yfm {
+namespace msed {
+
+constexpr int kM = 3;
+constexpr double kForget = 0.98;                  // forget_factor (mselambda.jl:15)
+constexpr double kRidge = 1e-3;                   // filter.jl:132
+constexpr double kEps = 2.220446049250313e-16;    // eps(Float64) (filter.jl:39)
+
+// model_kind values (include/yfm.h) → the three switches of the step
+YFM_MHD bool kind_known(int kind) { return kind == 3 || kind == 4 || kind == 5 || kind == 6 || kind == 8; }
+YFM_MHD bool kind_static(int kind) { return kind == 3; }
+YFM_MHD bool kind_has_b(int kind) { return kind == 4 || kind == 6; }
+YFM_MHD bool kind_scaled(int kind) { return kind == 6 || kind == 8; }
+YFM_MHD int kind_params(int kind) { return kind_static(kind) ? 13 : (kind_has_b(kind) ? 15 : 14); }
+
+YFM_MHD double mfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+// transformations.jl:21-26, evaluated as written
+YFM_MHD double from_R_to_11(double x) {
+  const double y = exp(x);
+  return 2.0 * y / (1.0 + y) - 1.0;
+}
+
+// What set_params! leaves in the model: the constants of the recursion and its initial state.
+struct Model {
+  double A, B, nu;   // A; B and ν = (1 − B)ω (0 and 0 where the model has no B, 0 everywhere for NS)
+  double mu[kM];     // (I − Φ)δ
+  double Phi[kM][kM];
+  double beta0[kM];  // δ
+  double gamma0;     // ω (NS: γ)
+};
+
+// The filter's state: β, γ and the score's second-moment average (reset by initialize_filter, filter.jl:19-26).
+struct State {
+  double beta[kM];
+  double gamma;
+  double ewma;
+  double fpow;  // forget_factor^count
+};
+
+// θ_b → Model.  Layouts: NS [γ, δ(3), vec Φ(9)]; SD-NS / SSD-NS [A, B, ω, δ(3), vec Φ(9)]; RWSD-NS / SRWSD-NS the
+// same without B.  vec Φ is column-major (reshape, paramteroperations.jl:56).  space 0: θ as compute_loss
+// receives it (A → exp, B → 1/(1 + e^−x), diagonal of Φ → from_R_to_11); space 1: θ_c as set_params! does.
+template <bool STATIC, bool HASB>
+YFM_MHD void decode(const double* th, int space, Model& m) {
+  const bool un = space == 0;
+  int k = 0;
+  m.A = 0.0;
+  m.B = 0.0;
+  if (!STATIC) {
+    m.A = un ? exp(th[k]) : th[k];
+    ++k;
+    if (HASB) {
+      m.B = un ? 1.0 / (1.0 + exp(-th[k])) : th[k];
+      ++k;
+    }
+  }
+  m.gamma0 = th[k++];
+  for (int i = 0; i < kM; ++i) m.beta0[i] = th[k + i];
+  k += kM;
+  for (int c = 0; c < kM; ++c)
+    for (int r = 0; r < kM; ++r) {
+      const double x = th[k + c * kM + r];
+      m.Phi[r][c] = (un && r == c) ? from_R_to_11(x) : x;
+    }
+  for (int r = 0; r < kM; ++r) {  // (I − Φ)δ, the matrix formed first (paramteroperations.jl:61)
+    double s = 0.0;
+    for (int c = 0; c < kM; ++c) s = s + ((r == c ? 1.0 : 0.0) - m.Phi[r][c]) * m.beta0[c];
+    m.mu[r] = s;
+  }
+  m.nu = HASB ? (1.0 - m.B) * m.gamma0 : 0.0;
+}
+
+YFM_MHD void init_state(const Model& m, State& s) {
+  for (int i = 0; i < kM; ++i) s.beta[i] = m.beta0[i];
+  s.gamma = m.gamma0;
+  s.ewma = 0.0;
+  s.fpow = 1.0;
+}
+
+// λ = 0.01 + e^γ with what the loadings and their γ-derivative need of it
+struct Lambda {
+  double lam, rl, dl;  // λ, 1/λ, dλ/dγ = e^γ
+};
+YFM_MHD Lambda make_lambda(double gamma) {
+  Lambda l;
+  l.dl = exp(gamma);
+  l.lam = 1e-2 + l.dl;
+  l.rl = 1.0 / l.lam;
+  return l;
+}
+
+// One maturity m (rm = 1/m): z = e^{−λm}, Z₂ = (1 − z)/(λm), Z₃ = Z₂ − z.  λ = Inf gives z = Z₂ = Z₃ = 0 exactly.
+YFM_MHD void loadings(const Lambda& l, double m, double rm, double& z, double& z2, double& z3) {
+  z = exp(-(l.lam * m));
+  z2 = (1.0 - z) * (l.rl * rm);
+  z3 = z2 - z;
+}
+
+// ∂Z₂/∂γ = (z − Z₂)·e^γ/λ and ∂Z₃/∂γ = ∂Z₂/∂γ + z·m·e^γ
+YFM_MHD void dloadings(const Lambda& l, double m, double z, double z2, double& d2, double& d3) {
+  d2 = (z - z2) * (l.dl * l.rl);
+  d3 = mfma(z * m, l.dl, d2);
+}
+
+// Indices of the statistics.
+enum : int { S2 = 0, S3, G22, G23, G33, Y1, Y2, Y3, NOLS };
+enum : int { D21 = 0, D22, D23, D31, D32, D33, DY2, DY3, NSCORE };
+
+YFM_MHD void accum_ols(double (&o)[NOLS], double z2, double z3, double y) {
+  o[S2] += z2;
+  o[S3] += z3;
+  o[G22] = mfma(z2, z2, o[G22]);
+  o[G23] = mfma(z2, z3, o[G23]);
+  o[G33] = mfma(z3, z3, o[G33]);
+  o[Y1] += y;
+  o[Y2] = mfma(z2, y, o[Y2]);
+  o[Y3] = mfma(z3, y, o[Y3]);
+}
+
+YFM_MHD void accum_score(double (&d)[NSCORE], double z2, double z3, double d2, double d3, double y) {
+  d[D21] += d2;
+  d[D22] = mfma(d2, z2, d[D22]);
+  d[D23] = mfma(d2, z3, d[D23]);
+  d[D31] += d3;
+  d[D32] = mfma(d3, z2, d[D32]);
+  d[D33] = mfma(d3, z3, d[D33]);
+  d[DY2] = mfma(d2, y, d[DY2]);
+  d[DY3] = mfma(d3, y, d[DY3]);
+}
+
+YFM_MHD double fitted(const double (&beta)[kM], double z2, double z3) { return mfma(beta[2], z3, mfma(beta[1], z2, beta[0])); }
+
+// Cholesky of the symmetric 3×3 (lower entries g) and the solve G x = b.  A pivot that is not > 0 (NaN included:
+// LAPACK's test) returns false and leaves x alone.
+YFM_MHD bool chol3_solve(double g11, double g21, double g31, double g22, double g32, double g33, const double (&b)[kM],
+                         double (&x)[kM]) {
+  if (!(g11 > 0.0)) return false;
+  const double r11 = 1.0 / sqrt(g11);
+  const double l21 = g21 * r11, l31 = g31 * r11;
+  const double a22 = g22 - l21 * l21;
+  if (!(a22 > 0.0)) return false;
+  const double r22 = 1.0 / sqrt(a22);
+  const double l32 = (g32 - l31 * l21) * r22;
+  const double a33 = g33 - (l31 * l31 + l32 * l32);
+  if (!(a33 > 0.0)) return false;
+  const double r33 = 1.0 / sqrt(a33);
+  const double w0 = b[0] * r11;
+  const double w1 = (b[1] - l21 * w0) * r22;
+  const double w2 = (b[2] - l31 * w0 - l32 * w1) * r33;
+  x[2] = w2 * r33;
+  x[1] = (w1 - l32 * x[2]) * r22;
+  x[0] = (w0 - l21 * x[1] - l31 * x[2]) * r11;
+  return true;
+}
+
+// get_β_OLS! (filter.jl:122-137): β = (Z'Z)⁻¹Z'y by Cholesky; on failure once more with 1e-3 added to the
+// diagonal (`ridged`); false where that fails too (the step then returns −Inf, filter.jl:62-67) — β is left alone.
+YFM_MHD bool ols(const double (&o)[NOLS], double n, double (&beta)[kM], bool& ridged) {
+  const double b[kM] = {o[Y1], o[Y2], o[Y3]};
+  ridged = false;
+  if (chol3_solve(n, o[S2], o[S3], o[G22], o[G23], o[G33], b, beta)) return true;
+  ridged = true;
+  return chol3_solve(n + kRidge, o[S2], o[S3], o[G22] + kRidge, o[G23], o[G33] + kRidge, b, beta);
+}
+YFM_MHD bool ols(const double (&o)[NOLS], double n, double (&beta)[kM]) {
+  bool ridged;
+  return ols(o, n, beta, ridged);
+}
+
+// s + e = a + b exactly
+YFM_MHD void two_sum(double a, double b, double& s, double& e) {
+  s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
+}
+
+// v = y − (β₁ + β₂z₂ + β₃z₃) with every rounding error of the evaluation carried: accurate relative to v itself,
+// however much of y cancels
+YFM_MHD double residual_carried(const double (&beta)[kM], double z2, double z3, double y) {
+  const double p1 = beta[1] * z2, e1 = mfma(beta[1], z2, -p1);
+  const double p2 = beta[2] * z3, e2 = mfma(beta[2], z3, -p2);
+  double s1, f1, s2, f2, s3, f3;
+  two_sum(y, -beta[0], s1, f1);
+  two_sum(s1, -p1, s2, f2);
+  two_sum(s2, -p2, s3, f3);
+  return s3 + ((((f1 + f2) + f3) - e1) - e2);
+}
+
+// statistics of the refinement pass: Z'v (3) and v'w, w = (∂Z/∂γ)β
+enum : int { R1 = 0, R2, R3, RH, NREFINE };
+
+YFM_MHD void accum_refine(double (&r)[NREFINE], const double (&beta)[kM], double z2, double z3, double d2, double d3,
+                          double y) {
+  const double v = residual_carried(beta, z2, z3, y);
+  const double w = mfma(d3, beta[2], d2 * beta[1]);
+  r[R1] += v;
+  r[R2] = mfma(z2, v, r[R2]);
+  r[R3] = mfma(z3, v, r[R3]);
+  r[RH] = mfma(v, w, r[RH]);
+}
+
+// g = 2 v'(∂Z/∂γ)β at the OLS β (filter.jl:168-184)
+YFM_MHD double score(const double (&d)[NSCORE], const double (&beta)[kM]) {
+  const double zb2 = mfma(d[D23], beta[2], mfma(d[D22], beta[1], d[D21] * beta[0]));  // d₂'Zβ
+  const double zb3 = mfma(d[D33], beta[2], mfma(d[D32], beta[1], d[D31] * beta[0]));  // d₃'Zβ
+  return 2.0 * mfma(beta[2], d[DY3] - zb3, beta[1] * (d[DY2] - zb2));
+}
+
+// The score at the refined β (the scaled kinds): δβ solves the system ols() solved (ridged or not) for the residual
+// of its normal equations, Z'v − ridge·β, and g = 2 (v − Zδβ)'w = 2 [v'w − δβ'(Z'w)], Z'w from the contractions.
+YFM_MHD double score_refined(const double (&o)[NOLS], double n, bool ridged, const double (&d)[NSCORE],
+                             const double (&r)[NREFINE], const double (&beta)[kM]) {
+  const double rd = ridged ? kRidge : 0.0;
+  const double rhs[kM] = {r[R1] - rd * beta[0], r[R2] - rd * beta[1], r[R3] - rd * beta[2]};
+  double db[kM] = {0.0, 0.0, 0.0};
+  (void)chol3_solve(n + rd, o[S2], o[S3], o[G22] + rd, o[G23], o[G33] + rd, rhs, db);
+  const double zw0 = mfma(d[D31], beta[2], d[D21] * beta[1]);
+  const double zw1 = mfma(d[D32], beta[2], d[D22] * beta[1]);
+  const double zw2 = mfma(d[D33], beta[2], d[D23] * beta[1]);
+  return 2.0 * (r[RH] - mfma(db[2], zw2, mfma(db[1], zw1, db[0] * zw0)));
+}
+
+// update_gamma_with_grad! (filter.jl:29-50): γ ← γ + A·g, g first scaled by the bias-corrected root of its
+// second-moment average where the model scales its score.
+template <bool SCALED>
+YFM_MHD void update_gamma(const Model& m, State& s, double g) {
+  if (SCALED) {
+    s.ewma = kForget * s.ewma + (1.0 - kForget) * (g * g);
+    s.fpow = s.fpow * kForget;
+    g = g / (sqrt(s.ewma / (1.0 - s.fpow)) + kEps);
+  }
+  s.gamma = s.gamma + g * m.A;
+}
+
+// The prediction half of a step (filter.jl:84-88, and the whole of a missing-data step, :53-59):
+// γ ← ν + Bγ where the model has a B, β ← μ + Φβ.
+template <bool HASB>
+YFM_MHD void advance(const Model& m, State& s) {
+  if (HASB) s.gamma = m.nu + m.B * s.gamma;
+  double nb[kM];
+  for (int r = 0; r < kM; ++r) {
+    double a = 0.0;
+    for (int c = 0; c < kM; ++c) a = mfma(m.Phi[r][c], s.beta[c], a);
+    nb[r] = m.mu[r] + a;
+  }
+  for (int r = 0; r < kM; ++r) s.beta[r] = nb[r];
+}
+
+// One filter step on the column y (N yields) with every maturity visited in order — the form the host check
+// runs; the kernel distributes the two accumulation loops over a lane group and runs the same 3×3 functions.
+// Returns false where the reference's step returns −Inf (the state then stays as the failing call left it).
+template <bool STATIC, bool HASB, bool SCALED>
+YFM_MHD bool filter_step(const Model& m, State& s, const double* mats, const double* y, int N) {
+  if (y[0] != y[0]) {  // isnan(y[1]) (filter.jl:53, :95): prediction only
+    advance<HASB>(m, s);
+    return true;
+  }
+  Lambda l = make_lambda(s.gamma);
+  double o[NOLS] = {0, 0, 0, 0, 0, 0, 0, 0}, d[NSCORE] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < N; ++i) {
+    double z, z2, z3, d2, d3;
+    loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+    accum_ols(o, z2, z3, y[i]);
+    if (!STATIC) {
+      dloadings(l, mats[i], z, z2, d2, d3);
+      accum_score(d, z2, z3, d2, d3, y[i]);
+    }
+  }
+  bool ridged;
+  if (!ols(o, (double)N, s.beta, ridged)) return false;
+  if (!STATIC) {
+    double g;
+    if (SCALED) {
+      double r[NREFINE] = {0, 0, 0, 0};
+      for (int i = 0; i < N; ++i) {
+        double z, z2, z3, d2, d3;
+        loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+        dloadings(l, mats[i], z, z2, d2, d3);
+        accum_refine(r, s.beta, z2, z3, d2, d3, y[i]);
+      }
+      g = score_refined(o, (double)N, ridged, d, r, s.beta);
+    } else {
+      g = score(d, s.beta);
+    }
+    update_gamma<SCALED>(m, s, g);
+    l = make_lambda(s.gamma);
+    double o2[NOLS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < N; ++i) {
+      double z, z2, z3;
+      loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+      accum_ols(o2, z2, z3, y[i]);
+    }
+    if (!ols(o2, (double)N, s.beta)) return false;
+  }
+  advance<HASB>(m, s);
+  return true;
+}
+
+// Z(γ)β of the current state for every maturity: the prediction filter returns (filter.jl:90, :109)
+YFM_MHD void predict_column(const State& s, const double* mats, int N, double* pred) {
+  const Lambda l = make_lambda(s.gamma);
+  for (int i = 0; i < N; ++i) {
+    double z, z2, z3;
+    loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+    pred[i] = fitted(s.beta, z2, z3);
+  }
+}
+
+// get_loss (filter.jl:209-243, K = 1) on the first nobs columns of Y (N×T column-major)
+template <bool STATIC, bool HASB, bool SCALED>
+YFM_MHD double get_loss(const double* th, int space, const double* mats, const double* Y, int N, int nobs,
+                        double* pred /* N scratch */) {
+  Model m;
+  State s;
+  decode<STATIC, HASB>(th, space, m);
+  init_state(m, s);
+  double mse = 0.0;
+  for (int t = 0; t + 1 < nobs; ++t) {
+    const bool ok = filter_step<STATIC, HASB, SCALED>(m, s, mats, Y + (size_t)t * N, N);
+    if (!ok) return -HUGE_VAL;
+    predict_column(s, mats, N, pred);
+    double vv = 0.0;
+    for (int i = 0; i < N; ++i) {
+      const double v = Y[(size_t)(t + 1) * N + i] - pred[i];
+      vv = mfma(v, v, vv);
+    }
+    mse -= vv;
+    if (!(fabs(mse) <= 1.79769313486231570815e308)) return -HUGE_VAL;  // isinf || isnan (filter.jl:232-234)
+  }
+  return mse / (double)N / (double)nobs;
+}
+
+}  // namespace msed
+}  // namespace yfm

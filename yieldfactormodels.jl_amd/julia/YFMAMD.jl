@@ -4,6 +4,9 @@ module YFMAMD
 const LIB = get(ENV, "YFM_LIB", joinpath(@__DIR__, "..", "yfm_amd", "libyfm_hip.so"))
 
 const YFM_MODEL_DNS, YFM_MODEL_TVL, YFM_MODEL_GNS5 = Cint(0), Cint(1), Cint(2)
+# the static and score-driven λ models of src/models/filter.jl:52-110 (7 is not a kind)
+const YFM_MODEL_NS, YFM_MODEL_SD_NS, YFM_MODEL_RWSD_NS, YFM_MODEL_SSD_NS, YFM_MODEL_SRWSD_NS =
+    Cint(3), Cint(4), Cint(5), Cint(6), Cint(8)
 const UNCONSTRAINED, CONSTRAINED = Cint(0), Cint(1)
 const PREC_CERTIFIED, PREC_FP64 = Cint(0), Cint(1)     # TVλ arithmetic (yfm_set_precision)
 
@@ -59,6 +62,11 @@ end
 
 kind(::YieldFactorModels.AbstractDNSModel) = YFM_MODEL_DNS
 kind(::YieldFactorModels.AbstractTVλDNSModel) = YFM_MODEL_TVL
+kind(::YieldFactorModels.AbstractStaticλModel) = YFM_MODEL_NS
+# MSEDλModel: random walk ⇔ no B (mselambda.jl:20-27), scale_grad (msebasemodel.jl:45)
+kind(m::YieldFactorModels.AbstractλMSEDrivenModel) =
+    isempty(m.base.B) ? (m.base.scale_grad ? YFM_MODEL_SRWSD_NS : YFM_MODEL_RWSD_NS) :
+                        (m.base.scale_grad ? YFM_MODEL_SSD_NS : YFM_MODEL_SD_NS)
 tuse_ptr(T_use) = T_use === nothing ? C_NULL : pointer(T_use)
 
 "Batched loglik: Θ is P×B (one candidate per column).  space: UNCONSTRAINED (compute_loss input) or CONSTRAINED (set_params! input)."

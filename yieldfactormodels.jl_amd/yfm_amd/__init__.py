@@ -4,11 +4,14 @@ The numerics live in ``libyfm_hip.so`` (HIP, gfx950) behind the C ABI of
 ``include/yfm.h``; this package is the host-side mirror of the reference's
 model / objective API (see :mod:`yfm_amd.models`).
 """
+from .params import (KIND_NS, KIND_RWSD_NS, KIND_SD_NS, KIND_SRWSD_NS, KIND_SSD_NS, LAMBDA_KINDS)
 from .params import (KIND_DNS, KIND_GNS, KIND_TVL, SPACE_CONSTRAINED, SPACE_UNCONSTRAINED, gamma_dim, n_params,
                      param_layout, state_dim)
 from .models import (DNSModel, EstimationError, GNS5Model, SingularException, TVLambdaDNSModel, compute_loss, compute_loss_batch, compute_loss_grad_batch,
                      create_model, estimate_, estimate_batch, estimate_lbfgs_batch, estimate_steps_, filter_states, forecast_batch, get_loss, get_loss_array, get_loss_batch,
                      get_params, predict, set_params_, transform_params, untransform_params)
+from .models import (MSEDLambdaModel, StaticLambdaModel, get_param_groups, try_initializations,
+                     try_initializations_batch)
 from .engine import Engine, get_engine
 from .driver import load_initial_parameters_, run
 from . import lbfgs
@@ -19,5 +22,6 @@ __all__ = [
     "set_params_", "transform_params", "untransform_params", "get_loss", "compute_loss", "get_loss_batch",
     "compute_loss_batch", "filter_states", "estimate_steps_", "estimate_batch", "predict", "get_loss_array", "forecast_batch", "gamma_dim", "Engine",
     "get_engine", "run", "load_initial_parameters_", "compute_loss_grad_batch", "estimate_", "estimate_lbfgs_batch",
-    "EstimationError", "lbfgs",
+    "EstimationError", "lbfgs", "KIND_NS", "KIND_SD_NS", "KIND_RWSD_NS", "KIND_SSD_NS", "KIND_SRWSD_NS", "LAMBDA_KINDS",
+    "StaticLambdaModel", "MSEDLambdaModel", "get_param_groups", "try_initializations", "try_initializations_batch",
 ]

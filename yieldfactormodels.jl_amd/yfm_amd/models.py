@@ -1,4 +1,5 @@
-"""Host-side mirror of the reference's Kalman model API (the drop-in surface).
+"""Host-side mirror of the reference's model API (the drop-in surface): the Kalman models and the static and
+score-driven λ models.
 
 Reference interface mirrored (paths relative to the reference root):
 
@@ -24,6 +25,14 @@ forecast blocks forecasting.jl:236-250      :func:`forecast_batch`
 ``estimate!`` optimization.jl:329-410       :func:`estimate_` (+ batched
                                             :func:`estimate_lbfgs_batch`; gradient:
                                             :func:`compute_loss_grad_batch`)
+``StaticλModel`` staticlambda.jl:3-32        :class:`StaticLambdaModel` ("NS" / "2")
+``MSEDλModel`` mselambda.jl:3-49            :class:`MSEDLambdaModel` ("SD-NS" / "4", "RWSD-NS" / "5",
+                                            "SSD-NS" / "6", "SRWSD-NS" / "7")
+``get_loss`` / ``get_loss_array`` /         the same functions: for the λ models they restate
+``predict`` src/models/filter.jl:209-306    src/models/filter.jl (K = 1)
+``get_param_groups`` msebasemodel.jl:153-162  :func:`get_param_groups`
+``try_initializations``                     :func:`try_initializations` (+ batched
+optimization.jl:73-114                      :func:`try_initializations_batch`): the (A, B) grid in one launch
 =======================================  =================================================
 
 plus the batched forms the device boundary exists for: :func:`get_loss_batch` and
@@ -117,20 +126,69 @@ class GNS5Model(AbstractKalmanModel):
         self.device = device
 
 
+class StaticLambdaModel(AbstractKalmanModel):
+    """staticlambda.jl:3-32: static Nelson–Siegel, θ_c = [γ, δ, vec Φ], P = 13.  (The base record is shared with
+    the Kalman models: it holds the fields the device path reads.)"""
+
+    def __init__(self, maturities, N: int, M: int = 3, model_string: str = "NS", results_location: str = "results/",
+                 device: int = 0):
+        if M != 3:
+            raise ValueError("StaticLambdaModel is a 3-factor model (M = 3)")
+        self.base = KalmanBaseModel(np.asarray(maturities, dtype=np.float64), N, 3, 1, _p.KIND_NS, model_string,
+                                    results_location)
+        self.device = device
+
+
+class MSEDLambdaModel(AbstractKalmanModel):
+    """mselambda.jl:3-49: score-driven λ, θ_c = [A, B, ω, δ, vec Φ] (no B when ``random_walk``), P = 15 / 14.
+    ``scale_grad`` divides the score by the bias-corrected root of its EWMA, forget factor 0.98
+    (filter.jl:29-44)."""
+
+    A_guesses = (1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1)  # mselambda.jl:26
+    B_guesses = (0.9, 0.95, 0.98, 0.99, 0.999)         # mselambda.jl:27
+    forget_factor = 0.98
+
+    def __init__(self, maturities, N: int, M: int = 3, random_walk: bool = False, model_string: str = "MSEDλ",
+                 results_location: str = "results/", scale_grad: bool = False, device: int = 0):
+        if M != 3:
+            raise ValueError("MSEDLambdaModel is a 3-factor model (M = 3)")
+        kind = {(False, False): _p.KIND_SD_NS, (True, False): _p.KIND_RWSD_NS, (False, True): _p.KIND_SSD_NS,
+                (True, True): _p.KIND_SRWSD_NS}[(bool(random_walk), bool(scale_grad))]
+        self.random_walk = bool(random_walk)
+        self.scale_grad = bool(scale_grad)
+        self.base = KalmanBaseModel(np.asarray(maturities, dtype=np.float64), N, 3, 1, kind, model_string,
+                                    results_location)
+        self.device = device
+
+
+def _msed(random_walk, scale_grad):
+    def make(mats, N, M, model_string, results_location, device):
+        return MSEDLambdaModel(mats, N, M, random_walk, model_string=model_string, results_location=results_location,
+                               scale_grad=scale_grad, device=device)
+    return make
+
+
 _CODES = {
     "1C": ("1C", DNSModel), "0": ("1C", DNSModel),
     "TVλ": ("TVλ", TVLambdaDNSModel), "1": ("TVλ", TVLambdaDNSModel),
     "GNS5": ("GNS5", GNS5Model),
+    # model_dictionary.jl:17-35
+    "NS": ("NS", StaticLambdaModel), "2": ("NS", StaticLambdaModel),
+    "SD-NS": ("SD-NS", _msed(False, False)), "4": ("SD-NS", _msed(False, False)),
+    "RWSD-NS": ("RWSD-NS", _msed(True, False)), "5": ("RWSD-NS", _msed(True, False)),
+    "SSD-NS": ("SSD-NS", _msed(False, True)), "6": ("SSD-NS", _msed(False, True)),
+    "SRWSD-NS": ("SRWSD-NS", _msed(True, True)), "7": ("SRWSD-NS", _msed(True, True)),
 }
 
 
 def create_model(model_type: str, maturities, N: int, M: int = 3, float_type=np.float64,
                  results_location: str = "results/", device: int = 0):
-    """model_dictionary.jl:7-16 for the Kalman codes; returns (model, standardized model_type)."""
+    """model_dictionary.jl:7-35 for the Kalman codes and the static / score-driven λ codes; returns
+    (model, standardized model_type)."""
     if np.dtype(float_type) != np.float64:
         raise ValueError("the MI355X path computes in Float64 only (the reference's Float64 path, test.jl:25)")
     if model_type not in _CODES:
-        raise ValueError(f"Invalid model type: {model_type} (Kalman codes: {sorted(_CODES)})")
+        raise ValueError(f"Invalid model type: {model_type} (codes: {sorted(_CODES)})")
     std, cls = _CODES[model_type]
     mats = np.asarray(maturities, dtype=np.float64)
     if len(mats) != N:
@@ -158,6 +216,70 @@ def untransform_params(model: AbstractKalmanModel, params) -> np.ndarray:
     return _p.untransform_params(model.kind, params)
 
 
+def get_param_groups(model: AbstractKalmanModel, param_groups=()) -> list:
+    """msebasemodel.jl:153-162 / staticbasemodel.jl:103-112: the caller's groups when there is one per parameter,
+    else the defaults — "1" for the leading parameters, "2" for the M(M + 1) entries of δ and Φ."""
+    if not _p.is_lambda_kind(model.kind):
+        raise NotImplementedError("Kalman models estimate every parameter in group \"1\"")
+    P, M = _p.n_params(model.kind), model.base.M
+    groups = list(param_groups)
+    if len(groups) == P:
+        return groups
+    return ["1"] * (P - M * (M + 1)) + ["2"] * (M * (M + 1))
+
+
+def _trial_grid(model) -> np.ndarray:
+    """get_new_initial_params (msedriven/paramteroperations.jl:132-187, the n_unique == 1 branch): the (A, B)
+    of trial 1, 2, … — B cycles fastest; the random-walk variants have the A trials only.  2×n_trials (row 2 NaN
+    without B)."""
+    A, Bg = MSEDLambdaModel.A_guesses, MSEDLambdaModel.B_guesses
+    if _p.lambda_has_b(model.kind):
+        return np.array([[a, b] for a in A for b in Bg]).T
+    return np.array([[a, np.nan] for a in A]).T
+
+
+def try_initializations_batch(best_params, model: AbstractKalmanModel, data, T_use=None):
+    """optimization.jl:73-114 for W starts at once: column w of ``best_params`` (P×W, constrained) on the window
+    ``data[:, :T_use[w]]``.  The start and its 30 (A, B) trials (6 for the random-walk variants) of every window go
+    through ONE launch; the winner is the reference's: a trial replaces the running best only on a strict
+    improvement, in trial order.  Returns (P×W winners, W losses, the loss being −get_loss)."""
+    if not isinstance(model, MSEDLambdaModel):
+        raise TypeError("try_initializations walks the (A, B) grid of a score-driven model")
+    best = np.asarray(best_params, dtype=np.float64)
+    best = best.reshape(best.shape[0], -1)
+    P, W = best.shape
+    grid = _trial_grid(model)
+    n = grid.shape[1]
+    cand = np.repeat(best[:, :, None], n + 1, axis=2)  # P × W × (1 + n): the start, then the trials
+    cand[0, :, 1:] = grid[0]
+    if _p.lambda_has_b(model.kind):
+        cand[1, :, 1:] = grid[1]
+    tu = None if T_use is None else np.repeat(np.broadcast_to(T_use, (W,)), n + 1)
+    loss = -get_loss_batch(model, data, cand.reshape(P, W * (n + 1)), space=_p.SPACE_CONSTRAINED, T_use=tu)
+    loss = loss.reshape(W, n + 1)
+    out = np.empty((P, W), order="F")
+    out_loss = np.empty(W)
+    for w in range(W):
+        k_best = 0
+        for k in range(1, n + 1):
+            if loss[w, k] < loss[w, k_best]:  # `loss < init_loss` (optimization.jl:105)
+                k_best = k
+        out[:, w] = cand[:, w, k_best]
+        out_loss[w] = loss[w, k_best]
+    return out, out_loss
+
+
+def try_initializations(best_params, model: AbstractKalmanModel, data):
+    """optimization.jl:73-114: the P×1 winner among the start and the (A, B) trials.  Other models return the
+    start unchanged (optimization.jl:33-35)."""
+    best = np.asarray(best_params, dtype=np.float64).reshape(-1)
+    if not isinstance(model, MSEDLambdaModel):
+        return best.reshape(-1, 1).copy()
+    out, _ = try_initializations_batch(best[:, None], model, data)
+    set_params_(model, out[:, 0])  # the reference leaves the model at the last trial; the winner is the useful state
+    return out
+
+
 def _engine(model, data):
     eng = get_engine(model.device)
     eng.set_panel(data, model.base.maturities)
@@ -168,7 +290,7 @@ def get_loss(model: AbstractKalmanModel, data) -> float:
     """filter.jl:182-209 for the model's current (constrained) parameters."""
     eng = _engine(model, data)
     ll = float(eng.loglik(model.kind, model.base.flat_params, space=_p.SPACE_CONSTRAINED)[0])
-    if np.isnan(ll):
+    if np.isnan(ll) and not _p.is_lambda_kind(model.kind):
         raise SingularException("initialize_filter: singular I - Φ or I - Φ⊗Φ")
     return ll
 
@@ -213,7 +335,7 @@ def predict(model: AbstractKalmanModel, data, horizon: int = 1, Theta=None, spac
     out = eng.predict(model.kind, Theta, space=space, T_use=T_use, horizon=horizon)
     if single:
         out = {k: v[:, :, 0] for k, v in out.items()}
-        if np.isnan(out["factors"]).all():
+        if np.isnan(out["factors"]).all() and not _p.is_lambda_kind(model.kind):
             raise SingularException("initialize_filter: singular I - Φ or I - Φ⊗Φ")
     return out
 
@@ -226,7 +348,7 @@ def get_loss_array(model: AbstractKalmanModel, data, K: int = 1, Theta=None, spa
     out = eng.loss_array(model.kind, model.base.flat_params if single else Theta, space=space, T_use=T_use, K=K)
     if single:
         row = out[:, 0]
-        if np.isnan(row).all() and row.size:
+        if np.isnan(row).all() and row.size and not _p.is_lambda_kind(model.kind):
             raise SingularException("initialize_filter: singular I - Φ or I - Φ⊗Φ")
         if row.size and np.isneginf(row).all():
             return -np.inf

@@ -15,8 +15,8 @@ import math
 
 import numpy as np
 
-from .params import (KIND_DNS, KIND_GNS, KIND_TVL, n_params, param_layout,
-                     untransform_params)
+from .params import (KIND_DNS, KIND_GNS, KIND_NS, KIND_TVL, is_lambda_kind, lambda_has_b, lambda_layout, n_params,
+                     param_layout, untransform_params)
 
 PANEL_SEED = 20260227
 BATCH_SEED = 20260228
@@ -35,6 +35,15 @@ def maturities_360() -> np.ndarray:
 
 def theta0_constrained(kind: int = KIND_DNS) -> np.ndarray:
     """θ₀ in the constrained space (as ``set_params!`` consumes it)."""
+    if is_lambda_kind(kind):
+        # [A, B, ω, δ, vec Φ] (msedriven/paramteroperations.jl:25-65) with the DNS δ and Φ; Φ column-major
+        dns = theta0_constrained(KIND_DNS)
+        lay = param_layout(KIND_DNS)
+        delta = dns[lay.delta_offset:lay.delta_offset + 3]
+        phi = dns[lay.phi_offset:lay.phi_offset + 9].reshape(3, 3)
+        lead = [] if kind == KIND_NS else ([1e-3, 0.98] if lambda_has_b(kind) else [1e-3])
+        return np.asarray(lead + [math.log(0.0609 - 0.01)] + list(delta) + list(phi.reshape(-1, order="F")),
+                          dtype=np.float64)
     if kind == KIND_DNS:
         M = 3
         lead = [math.log(0.0609 - 0.01)]
@@ -110,6 +119,8 @@ def _loadings(gammas, maturities, M):
 
 def simulate_panel(kind: int = KIND_DNS, T: int = 600, maturities=None, seed: int = PANEL_SEED) -> np.ndarray:
     """Simulate y_t = Z β_t + ε_t, β_{t+1} = δ + Φ β_t + η_t at θ₀ (yields in percent). Returns N×T (F-order)."""
+    if is_lambda_kind(kind):
+        kind = KIND_DNS  # the λ models are fitted to the same data: the DNS panel at the DNS θ₀
     if maturities is None:
         maturities = maturities_360() if kind == KIND_TVL else maturities_30()
     maturities = np.asarray(maturities, dtype=np.float64)
@@ -145,7 +156,7 @@ def theta_batch(kind: int = KIND_DNS, B: int = 65536, scale: float = 0.1, seed: 
     Theta = np.asfortranarray(th0[:, None] + scale * rng.standard_normal((P, B)))
     nbad = int(round(bad_frac * B))
     if nbad:
-        lay = param_layout(kind)
+        lay = lambda_layout(kind) if is_lambda_kind(kind) else param_layout(kind)
         idx = rng.choice(B, size=nbad, replace=False)
         a = np.where(np.arange(nbad) % 2 == 0, 0.8, 3.0)
         Theta[lay.phi_offset + 1, idx] = a  # Φ[1,2] (row-major)

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YFM_ABI_VERSION 3
+#define YFM_ABI_VERSION 4
 
 typedef struct yfm_ctx yfm_ctx;
 
@@ -264,6 +264,45 @@ int yfm_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, 
  * the dense path of optimization.jl:10-23 there).  0 after a batch that asked for no gradient.  For
  * yfm_loglik_grad_batch_device, synchronise the stream first. */
 int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n);
+
+/* The λ kinds' loss WITH its gradient with respect to δ and Φ — replaces, per candidate, the value and the
+ * gradient that Optim.LBFGS asks for in estimate_steps! when it optimises parameter group "2", the M(M+1) = 12
+ * entries of δ and vec Φ (optimization.jl:137-312, :442-479; the groups: msebasemodel.jl:153-162,
+ * staticbasemodel.jl:103-112), with the sign of get_loss: loss_out[b] is bitwise what yfm_loglik_batch returns
+ * (filter.jl:209-243) and grad_out[:, b] (12×B column-major: δ(3), then vec Φ column-major — the order of θ's last
+ * 12 rows) = ∂(+get_loss)/∂θ_i in the space the caller passed; the unconstrained space includes the derivative
+ * of from_R_to_11 on the diagonal of Φ (transformations.jl:21-26), everything else there is the identity.  The
+ * gradient is exact and needs no tangent recursion: on a data column filter replaces β by an OLS fit and takes
+ * the score from it (filter.jl:52-91), so δ and Φ enter only the prediction μ + Φβ (filter.jl:84-88).  A missing
+ * first column makes step 1 prediction-only from β₀ = δ (filter.jl:53-59).  The derivatives with respect to the
+ * leading parameters (A, B, ω; γ for NS) are not formed: the reference's defaults optimise those by Nelder–Mead.
+ * YFM_MODEL_NS, SD_NS, RWSD_NS, SSD_NS and SRWSD_NS only: the Kalman kinds return YFM_EUNSUPPORTED (their
+ * gradient is yfm_loglik_grad_batch).  grad_out[:, b] is NaN in all 12 entries where loss_out[b] is −Inf
+ * (n_neg_inf).  A candidate's 13 outputs do not depend on the batch.  yfm_last_batch_flags keeps its meaning.
+ * Synchronous. */
+int yfm_lambda_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                               const int* T_use, double* loss_out, double* grad_out);
+
+/* Same (optimization.jl:442-479, filter.jl:209-243) with DEVICE pointers on the caller's HIP stream;
+ * asynchronous, with the ordering rules of yfm_loglik_batch_device. */
+int yfm_lambda_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                      int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                                      void* hip_stream);
+
+/* One Optim.NelderMead run per chain on a block of coordinates — what estimate_steps! does for a parameter group
+ * that uses opt1 (optimization.jl:218-247 with :442-451, :479: NelderMead, `iterations`, g_tol), without the outer
+ * group loop, the sanitising or the rescaling around it (:157-184, :249-281), which stay with the caller.  p is
+ * P×R column-major, UNCONSTRAINED, in/out: chain r minimises compute_loss (optimization.jl:10-23, = −get_loss) of
+ * column r on the window T_use[r] (NULL: the whole panel) over the n_idx distinct coordinates idx[] (0-based rows
+ * of θ), the other coordinates held at their values in p; on return those coordinates hold Optim's minimizer and
+ * f_out[r] its compute_loss.  The simplex dimension is n_idx.  All model kinds.  The rounds are yfm_estimate's:
+ * one batched launch per round and chain group, the speculation tree, each trial point embedded into the chain's
+ * full θ in its batch slot; a chain's sequence of simplices is bitwise that of a sequential Optim run on the same
+ * objective values.  Where the objective throws (NaN: a Kalman kind's initialize_filter), the chain's column
+ * of p is left as it came and f_out[r] is NaN.  n_evals_out (may be NULL): evaluations the chains consumed.
+ * Synchronous. */
+int yfm_nm_block(yfm_ctx* ctx, int model_kind, double* p, int P, int R, const int* T_use, const int* idx, int n_idx,
+                 int iterations, double g_tol, double* f_out, long long* n_evals_out);
 
 #ifdef __cplusplus
 }

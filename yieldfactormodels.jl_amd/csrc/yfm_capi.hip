@@ -68,7 +68,7 @@ struct yfm::Workspace {
   DevBuf scratch_dd;  // TVλ double-double records (YFM_PREC_CERTIFIED)
   DevBuf defer;       // candidates handed from the FP64 fixed-loading kernels to the dd kernel
   DevBuf scratch_fd;  // their double-double records (yfm_fixedz_dd.hip)
-  DevBuf grad;        // P×B gradient staging of the host-pointer gradient call (yfm_loglik_grad_batch)
+  DevBuf grad;        // gradient staging of the host-pointer gradient calls (yfm_loglik_grad_batch, yfm_lambda_loss_grad_batch)
   // allocate and zero the two counter banks
   hipError_t init() {
     const size_t nb = 2 * yfm::kFlagsPerBank * sizeof(unsigned int);
@@ -274,6 +274,7 @@ struct Launch {
   bool continues = false;  // a later chunk of a pipelined batch: accumulates into the previous chunk's counters
   int share = 1;           // launches of this size the caller keeps in flight at once (yfm::loglik_device_ws)
   const yfm::MsedRecord* msed_rec = nullptr;  // λ models: the trajectory outputs this launch writes (nullptr: the loss)
+  double* msed_grad = nullptr;  // λ models: 12×B device, ∂loss/∂(δ, Φ) written with the loss (yfm_lambda_loss_grad_batch)
 };
 
 // The plain log-likelihood launch, in the argument order of yfm_loglik_batch_device.
@@ -336,7 +337,9 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
   hipError_t e;
   if (yfm::msed_kind(q.kind)) {
     const int lanes = yfm::msed_lanes_for(B);
-    e = q.msed_rec ? yfm::launch_msed_record(q.kind, a, lanes, *q.msed_rec) : yfm::launch_msed(q.kind, a, lanes);
+    e = q.msed_grad  ? yfm::launch_msed_grad(q.kind, a, lanes, q.msed_grad)
+        : q.msed_rec ? yfm::launch_msed_record(q.kind, a, lanes, *q.msed_rec)
+                     : yfm::launch_msed(q.kind, a, lanes);
   } else if (q.kind == YFM_MODEL_TVL) {
     int lanes = yfm::tvl_lanes_for(B, ctx->N, q.share);
     const char* const ov = yfm::env_or("YFM_TVL_LANES", nullptr);  // tuning override: 1, 2, 4, …, 64
@@ -427,6 +430,14 @@ int check_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
   if (ctx->N > yfm::grad_max_n())
     return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the gradient kernel's %d", ctx->N, yfm::grad_max_n());
   return YFM_OK;
+}
+
+// The λ gradient entry points' model check: the five kinds of yfm_msed.hip only.
+int check_lambda_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
+  if (state_dim(kind) >= 0 && !yfm::msed_kind(kind))
+    return set_error(YFM_EUNSUPPORTED, "the δ/Φ loss gradient is built for the λ kinds only (model_kind %d: use "
+                     "yfm_loglik_grad_batch)", kind);
+  return check_batch(ctx, kind, space, P, B);
 }
 
 // The loglik launch q on the context's own workspace, then the tangent kernel on the same stream: it reads the
@@ -743,6 +754,40 @@ int yfm_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, 
     return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_grad_out");
   return launch_grad(ctx, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
                                         static_cast<hipStream_t>(hip_stream)), d_grad_out);
+}
+
+int yfm_lambda_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                               const int* T_use, double* loss_out, double* grad_out) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_lambda_grad(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !loss_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loss_out or grad_out");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  const size_t gb = sizeof(double) * yfm::kMsedGrad * (size_t)(B > 0 ? B : 1);
+  YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
+  q.msed_grad = static_cast<double*>(ctx->own.grad.p);
+  if (int r = launch(ctx, q)) return r;
+  if (B > 0) {
+    YFM_HIP_CHECK(hipMemcpyAsync(loss_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, q.msed_grad, sizeof(double) * yfm::kMsedGrad * (size_t)B,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+int yfm_lambda_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                      int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                                      void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_lambda_grad(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_loss_out || !d_grad_out))
+    return set_error(YFM_EINVAL, "null d_theta, d_loss_out or d_grad_out");
+  Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
+                           static_cast<hipStream_t>(hip_stream));
+  q.msed_grad = d_grad_out;
+  return launch(ctx, q);
 }
 
 int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n) {

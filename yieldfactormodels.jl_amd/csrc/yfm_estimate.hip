@@ -35,6 +35,11 @@
 // the tree until an outcome was not speculated.  The chain's sequence of states, and so its
 // result, is bitwise that of one iteration per round; n_evals counts the evaluations the chain
 // consumed (as without speculation).
+//
+// yfm_nm_block runs the same rounds (run_chains) for one NelderMead group of one group iteration: the simplex spans a
+// block of coordinates and every trial point is embedded into the chain's full θ in its batch slot.  It serves the
+// models whose parameter groups use several optimisers (the λ kinds: "1" NelderMead, "2" L-BFGS,
+// optimization.jl:442-494), whose outer loop is host code above the C ABI.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -220,44 +225,14 @@ class Pool {
   std::atomic<bool> stop_a_{false};
 };
 
-}  // namespace
-
-extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const double* theta0, int P, int R,
-                            const int* T_use, int iterations, double g_tol, int max_group_iters, double tol,
-                            double* theta_c_out, double* p_out, double* init_c_out, double* ll_out,
-                            int* status_out, long long* n_evals_out) {
-  if (!ctx) return yfm::api_error(YFM_EINVAL, "null context");
-  if (yfm_param_count(model_kind) < 0) return yfm::api_error(YFM_EINVAL, "unknown model_kind");
-  if (yfm::msed_kind(model_kind))
-    return yfm::api_error(YFM_EUNSUPPORTED, "yfm_estimate is built for the Kalman kinds only: the λ kinds' parameter "
-                          "groups need other optimisers (optimization.jl:442-479)");
-  if (P != yfm_param_count(model_kind)) return yfm::api_error(YFM_EINVAL, "P does not match model_kind");
-  if (param_space != YFM_THETA_UNCONSTRAINED && param_space != YFM_THETA_CONSTRAINED)
-    return yfm::api_error(YFM_EINVAL, "unknown param_space");
-  if (R < 0 || iterations < 0 || max_group_iters < 1)
-    return yfm::api_error(YFM_EINVAL, "R, iterations must be >= 0 and max_group_iters >= 1");
-  if (R == 0) return YFM_OK;
-  if (!theta0 || !theta_c_out || !ll_out) return yfm::api_error(YFM_EINVAL, "null pointer argument");
-  const int Tp = yfm::panel_T(ctx);
-  if (Tp <= 0) return yfm::api_error(YFM_ENOPANEL, "no panel: call yfm_set_panel first");
-  // the estimator's group streams share the context's buffers with any earlier launch on a caller's stream
-  if (yfm::settle_foreign_launch(ctx) != hipSuccess) return yfm::api_error(YFM_EHIP, "device synchronisation failed");
-  if (T_use)
-    for (int r = 0; r < R; ++r)
-      if (T_use[r] < 1 || T_use[r] > Tp) return yfm::api_error(YFM_EINVAL, "T_use outside [1, T]");
-  const std::vector<int> codes = transform_codes(model_kind);
-  std::vector<Chain> chains(R);
-  for (int r = 0; r < R; ++r) {
-    Chain& c = chains[r];
-    c.n = P;
-    c.window = T_use ? T_use[r] : 0;
-    c.p.resize(P);
-    for (int i = 0; i < P; ++i) {
-      double x = theta0[(size_t)r * P + i];
-      if (param_space == YFM_THETA_CONSTRAINED) x = to_unconstrained(codes[i], x);
-      c.p[i] = std::isfinite(x) ? x : 0.0;  // _sanitize_parameters (optimization.jl:422-432)
-    }
-  }
+// The round loop every estimation entry point shares: advance the chains until all are done, one batched launch
+// per round and chain group.  A chain's simplex lives either in the whole θ (idx == nullptr, n = P) or in the
+// n_idx coordinates idx of it, the other coordinates held at the chain's column of `base` (P×R): each trial point
+// is then embedded into the chain's full θ in its batch slot.  Sums the evaluations the chains consumed into *evals.
+int run_chains(yfm_ctx* ctx, int model_kind, std::vector<Chain>& chains, int P, const int* T_use, int iterations,
+               double g_tol, int max_group_iters, double tol, const int* idx, int n_idx, const double* base,
+               const char* who, long long* evals_out) {
+  const int R = (int)chains.size();
   int spec_nodes = 16;
   if (const char* e = std::getenv("YFM_NM_SPEC")) spec_nodes = std::max(1, std::min(kMaxNodes, std::atoi(e)));
   const bool stats = std::getenv("YFM_EST_STATS") != nullptr;
@@ -265,7 +240,8 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
   // speculated points; the rest of the slot keeps earlier values and its results are ignored),
   // so each chain's host work — consume the last results, prepare, write the slot — runs in
   // parallel, straight into page-locked memory, and T_use is written once.
-  const int SLOT = std::max(4 * spec_nodes, P + 1);
+  const int n_dim = idx ? n_idx : P;  // the simplex dimension
+  const int SLOT = std::max(4 * spec_nodes, n_dim + 1);
   if (SLOT > kMaxSlot) return yfm::api_error(YFM_EINVAL, "too many parameters for the estimation driver");
   const int B = R * SLOT;
   PinnedBuf pin_th, pin_tu, pin_out;
@@ -284,7 +260,12 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
   if (zero_copy && (hipHostGetDevicePointer(reinterpret_cast<void**>(&map_th), th, 0) != hipSuccess ||
                     hipHostGetDevicePointer(reinterpret_cast<void**>(&map_out), out, 0) != hipSuccess))
     zero_copy = false;
-  std::memset(th, 0, sizeof(double) * (size_t)B * P);
+  if (idx) {  // every point of a chain's slot is the chain's θ; a round then writes the block's coordinates only
+    for (int r = 0; r < R; ++r)
+      for (int k = 0; k < SLOT; ++k) std::memcpy(th + ((size_t)r * SLOT + k) * P, base + (size_t)r * P, sizeof(double) * P);
+  } else {
+    std::memset(th, 0, sizeof(double) * (size_t)B * P);
+  }
   if (T_use)
     for (int r = 0; r < R; ++r) std::fill_n(static_cast<int*>(pin_tu.p) + (size_t)r * SLOT, SLOT, T_use[r]);
   // Chains are split into G groups, each with its own stream and launch workspace: while one
@@ -350,10 +331,14 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
       for (int m = last_active.load(std::memory_order_relaxed); m < r;)
         if (last_active.compare_exchange_weak(m, r, std::memory_order_relaxed)) break;
       double* slot = th + (size_t)r * SLOT * P;
-      if (c.nodes.empty())
-        std::memcpy(slot, c.trial.data(), sizeof(double) * c.trial.size());
-      else
-        std::memcpy(slot, c.pts.data(), sizeof(double) * c.nodes.size() * 4 * (size_t)P);
+      const double* src = c.nodes.empty() ? c.trial.data() : c.pts.data();
+      const size_t npts = c.nodes.empty() ? (size_t)c.n_req : c.nodes.size() * 4;
+      if (!idx) {
+        std::memcpy(slot, src, sizeof(double) * npts * (size_t)P);
+      } else {
+        for (size_t k = 0; k < npts; ++k)
+          for (int q = 0; q < n_idx; ++q) slot[k * P + idx[q]] = src[k * n_idx + q];
+      }
     }
     if (stats) {
       const auto h3 = clk::now();
@@ -430,8 +415,8 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
     hits += c.spec_hits;
   }
   if (stats) {
-    std::fprintf(stderr, "yfm_estimate: %lld rounds, %lld chain evaluations, %lld device evaluations, %lld "
-                 "speculated iterations used; host %.3f s, waiting on the device %.3f s (%d groups)\n", rounds, evals,
+    std::fprintf(stderr, "%s: %lld rounds, %lld chain evaluations, %lld device evaluations, %lld "
+                 "speculated iterations used; host %.3f s, waiting on the device %.3f s (%d groups)\n", who, rounds, evals,
                  device_evals, hits, t_host, t_dev, G);
     long long tr[8][8] = {}, dh[8] = {}, rc[2] = {};
     for (const Chain& c : chains) {
@@ -442,20 +427,66 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
       rc[0] += c.recent[0];
       rc[1] += c.recent[1];
     }
-    std::fprintf(stderr, "yfm_estimate: host thread time: consume + tree walk %.3f s, prepare %.3f s, slot copy %.3f s "
-                 "(%d threads)\n", ns_consume.load() * 1e-9, ns_prepare.load() * 1e-9, ns_copy.load() * 1e-9,
+    std::fprintf(stderr, "%s: host thread time: consume + tree walk %.3f s, prepare %.3f s, slot copy %.3f s "
+                 "(%d threads)\n", who, ns_consume.load() * 1e-9, ns_prepare.load() * 1e-9, ns_copy.load() * 1e-9,
                  std::min(nthreads, std::max(1, R / (4 * G))));
-    std::fprintf(stderr, "yfm_estimate: %d tree nodes per round; iterations per NM round:", spec_nodes);
+    std::fprintf(stderr, "%s: %d tree nodes per round; iterations per NM round:", who, spec_nodes);
     for (int a = 1; a < 8; ++a) std::fprintf(stderr, " %d:%lld", a, dh[a]);
     std::fprintf(stderr, "; worst = previously replaced vertex in %lld of %lld non-new outcomes\n", rc[0], rc[1]);
-    std::fprintf(stderr, "yfm_estimate: iteration outcome transitions (row: previous, col: next; "
-                 "R E O O* I I* S, * = new vertex is the worst; row 7 = first)\n");
+    std::fprintf(stderr, "%s: iteration outcome transitions (row: previous, col: next; "
+                 "R E O O* I I* S, * = new vertex is the worst; row 7 = first)\n", who);
     for (int a = 0; a < 8; ++a) {
       std::fprintf(stderr, "  %d:", a);
       for (int b = 0; b < 7; ++b) std::fprintf(stderr, " %9lld", tr[a][b]);
       std::fprintf(stderr, "\n");
     }
   }
+  if (evals_out) *evals_out = evals;
+  return YFM_OK;
+}
+
+}  // namespace
+
+extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const double* theta0, int P, int R,
+                            const int* T_use, int iterations, double g_tol, int max_group_iters, double tol,
+                            double* theta_c_out, double* p_out, double* init_c_out, double* ll_out,
+                            int* status_out, long long* n_evals_out) {
+  if (!ctx) return yfm::api_error(YFM_EINVAL, "null context");
+  if (yfm_param_count(model_kind) < 0) return yfm::api_error(YFM_EINVAL, "unknown model_kind");
+  if (yfm::msed_kind(model_kind))
+    return yfm::api_error(YFM_EUNSUPPORTED, "yfm_estimate is built for the Kalman kinds only: the λ kinds' parameter "
+                          "groups need other optimisers (optimization.jl:442-479)");
+  if (P != yfm_param_count(model_kind)) return yfm::api_error(YFM_EINVAL, "P does not match model_kind");
+  if (param_space != YFM_THETA_UNCONSTRAINED && param_space != YFM_THETA_CONSTRAINED)
+    return yfm::api_error(YFM_EINVAL, "unknown param_space");
+  if (R < 0 || iterations < 0 || max_group_iters < 1)
+    return yfm::api_error(YFM_EINVAL, "R, iterations must be >= 0 and max_group_iters >= 1");
+  if (R == 0) return YFM_OK;
+  if (!theta0 || !theta_c_out || !ll_out) return yfm::api_error(YFM_EINVAL, "null pointer argument");
+  const int Tp = yfm::panel_T(ctx);
+  if (Tp <= 0) return yfm::api_error(YFM_ENOPANEL, "no panel: call yfm_set_panel first");
+  // the estimator's group streams share the context's buffers with any earlier launch on a caller's stream
+  if (yfm::settle_foreign_launch(ctx) != hipSuccess) return yfm::api_error(YFM_EHIP, "device synchronisation failed");
+  if (T_use)
+    for (int r = 0; r < R; ++r)
+      if (T_use[r] < 1 || T_use[r] > Tp) return yfm::api_error(YFM_EINVAL, "T_use outside [1, T]");
+  const std::vector<int> codes = transform_codes(model_kind);
+  std::vector<Chain> chains(R);
+  for (int r = 0; r < R; ++r) {
+    Chain& c = chains[r];
+    c.n = P;
+    c.window = T_use ? T_use[r] : 0;
+    c.p.resize(P);
+    for (int i = 0; i < P; ++i) {
+      double x = theta0[(size_t)r * P + i];
+      if (param_space == YFM_THETA_CONSTRAINED) x = to_unconstrained(codes[i], x);
+      c.p[i] = std::isfinite(x) ? x : 0.0;  // _sanitize_parameters (optimization.jl:422-432)
+    }
+  }
+  long long evals = 0;
+  if (int rc = run_chains(ctx, model_kind, chains, P, T_use, iterations, g_tol, max_group_iters, tol, nullptr, 0, nullptr,
+                          "yfm_estimate", &evals))
+    return rc;
   for (int r = 0; r < R; ++r) {
     const Chain& c = chains[r];
     const bool ok = c.status != 1;
@@ -467,6 +498,56 @@ extern "C" int yfm_estimate(yfm_ctx* ctx, int model_kind, int param_space, const
     }
     ll_out[r] = ok ? c.prev_ll : NAN;
     if (status_out) status_out[r] = c.status;
+  }
+  if (n_evals_out) *n_evals_out = evals;
+  return YFM_OK;
+}
+
+extern "C" int yfm_nm_block(yfm_ctx* ctx, int model_kind, double* p, int P, int R, const int* T_use, const int* idx,
+                            int n_idx, int iterations, double g_tol, double* f_out, long long* n_evals_out) {
+  if (!ctx) return yfm::api_error(YFM_EINVAL, "null context");
+  if (yfm_param_count(model_kind) < 0) return yfm::api_error(YFM_EINVAL, "unknown model_kind");
+  if (P != yfm_param_count(model_kind)) return yfm::api_error(YFM_EINVAL, "P does not match model_kind");
+  if (R < 0 || iterations < 0) return yfm::api_error(YFM_EINVAL, "R and iterations must be >= 0");
+  if (n_idx < 1 || n_idx > P || !idx) return yfm::api_error(YFM_EINVAL, "n_idx outside [1, P] or null idx");
+  std::vector<char> seen(P, 0);
+  for (int q = 0; q < n_idx; ++q) {
+    if (idx[q] < 0 || idx[q] >= P || seen[idx[q]]) return yfm::api_error(YFM_EINVAL, "idx entry out of range or repeated");
+    seen[idx[q]] = 1;
+  }
+  if (n_evals_out) *n_evals_out = 0;
+  if (R == 0) return YFM_OK;
+  if (!p || !f_out) return yfm::api_error(YFM_EINVAL, "null pointer argument");
+  const int Tp = yfm::panel_T(ctx);
+  if (Tp <= 0) return yfm::api_error(YFM_ENOPANEL, "no panel: call yfm_set_panel first");
+  if (yfm::settle_foreign_launch(ctx) != hipSuccess) return yfm::api_error(YFM_EHIP, "device synchronisation failed");
+  if (T_use)
+    for (int r = 0; r < R; ++r)
+      if (T_use[r] < 1 || T_use[r] > Tp) return yfm::api_error(YFM_EINVAL, "T_use outside [1, T]");
+  // one Optim.NelderMead run per chain: the chain machine of yfm_nm.hpp entered at the simplex construction of its
+  // first (and only) group iteration, with the block's coordinates as its parameters
+  std::vector<Chain> chains(R);
+  for (int r = 0; r < R; ++r) {
+    Chain& c = chains[r];
+    c.n = n_idx;
+    c.window = T_use ? T_use[r] : 0;
+    c.p.resize(n_idx);
+    for (int q = 0; q < n_idx; ++q) c.p[q] = p[(size_t)r * P + idx[q]];
+    c.outer = 1;
+    c.phase = NM_INIT;
+  }
+  long long evals = 0;
+  if (int rc = run_chains(ctx, model_kind, chains, P, T_use, iterations, g_tol, /*max_group_iters=*/1, /*tol=*/0.0, idx,
+                          n_idx, p, "yfm_nm_block", &evals))
+    return rc;
+  for (int r = 0; r < R; ++r) {
+    const Chain& c = chains[r];
+    if (c.status != YFM_OK) {  // the objective threw (NaN): the chain's parameters stay, its value is NaN
+      f_out[r] = NAN;
+      continue;
+    }
+    for (int q = 0; q < n_idx; ++q) p[(size_t)r * P + idx[q]] = c.p[q];
+    f_out[r] = -c.prev_ll;
   }
   if (n_evals_out) *n_evals_out = evals;
   return YFM_OK;

@@ -129,6 +129,11 @@ int msed_param_count(int kind);
 int msed_max_n();
 int msed_lanes_for(int B);
 hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes);
+// get_loss into a.out and ∂(get_loss)/∂(δ, vec Φ) — 12 per candidate, in the space a.space — into grad (12×B);
+// the loss is launch_msed's bit for bit, the gradient of a −Inf candidate is NaN (counted in a.flags[1] as there).
+// With filter.jl:52-91 the γ path does not depend on δ or Φ, so no tangent recursion runs (yfm_msed.hpp).
+constexpr int kMsedGrad = 12;
+hipError_t launch_msed_grad(int kind, const LaunchArgs& a, int lanes, double* grad);
 // The same recursion writing its trajectory straight into the caller's (NaN-prefilled) device outputs:
 // mode 1 predict (filter.jl:284-306), 2 forecast blocks (forecasting.jl:236-250), 3 get_loss_array (filter.jl:245-281).
 struct MsedRecord {

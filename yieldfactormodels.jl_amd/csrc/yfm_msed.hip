@@ -1,5 +1,5 @@
-// yfm_msed.hip — batched loss, per-step loss array, predict and forecast of the static and score-driven
-// λ Nelson–Siegel models (NS, SD-NS, RWSD-NS, SSD-NS, SRWSD-NS) for gfx950.  FP64.
+// yfm_msed.hip — batched loss, its δ/Φ gradient, per-step loss array, predict and forecast of the static and
+// score-driven λ Nelson–Siegel models (NS, SD-NS, RWSD-NS, SSD-NS, SRWSD-NS) for gfx950.  FP64.
 //
 // Restates, per candidate θ_b (the algebra is in yfm_msed.hpp, which names the model files):
 //   get_loss         src/models/filter.jl:209-243
@@ -393,6 +393,247 @@ __global__ __launch_bounds__(kMsedBlock) void msed_kernel(const double* __restri
   out[b] = ll;
 }
 
+// The first pass's statistics with Z'v of the comparison (yfm_msed.hpp, ∂loss/∂(δ, Φ)) through the same tree.
+template <bool SCORE>
+struct GradStats {
+  Stats<SCORE> s;
+  double zv[kM];
+  __device__ __forceinline__ void zero() {
+    s.zero();
+#pragma unroll
+    for (int k = 0; k < kM; ++k) zv[k] = 0.0;
+  }
+  __device__ __forceinline__ void add(const GradStats& a, const GradStats& b) {
+    s.add(a.s, b.s);
+#pragma unroll
+    for (int k = 0; k < kM; ++k) zv[k] = a.zv[k] + b.zv[k];
+  }
+};
+
+// get_loss and its gradient with respect to δ and Φ in one pass: msed_kernel's loss mode — the same mapping,
+// staging, passes and sums, so the loss is the same bits — whose comparison also forms s = Z'v, from which every
+// lane of the group updates the 12 accumulators (replicated like the state: DESIGN.md §3.6).  Writes the loss to
+// out[b] and the gradient, in the caller's space, to grad[12·b ..]; NaN where the loss is −Inf.
+template <int L, bool STATIC, bool HASB, bool SCALED>
+__global__ __launch_bounds__(kMsedBlock) void lambda_grad_kernel(const double* __restrict__ theta, int P, int B,
+                                                                  int space, const double* __restrict__ Y, int T,
+                                                                  int N, int TC, const double* __restrict__ mats,
+                                                                  const int* __restrict__ T_use,
+                                                                  double* __restrict__ out, double* __restrict__ grad,
+                                                                  unsigned int* __restrict__ flags,
+                                                                  unsigned int* __restrict__ flags_next) {
+  constexpr int GPB = kMsedBlock / L;
+  constexpr int KQ = log_classes_per_lane<L>();
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double2* s_mr = reinterpret_cast<double2*>(smem);  // (m_i, 1/m_i)
+  double* s_y = smem + 2 * N;                         // TC columns of N yields
+  __shared__ int s_iters_max;
+
+  const int tid = threadIdx.x;
+  if (flags_next && blockIdx.x == 0 && tid < kFlagsPerBank) flags_next[tid] = 0u;  // the next launch's counters
+  const int j = tid % L;
+  const int grp = tid / L;
+  const int b = blockIdx.x * GPB + grp;
+  const bool live = b < B;
+  const int bb = live ? b : (B - 1);
+  const int nobs = T_use ? T_use[bb] : T;
+
+  if (tid == 0) s_iters_max = 0;
+  for (int i = tid; i < N; i += kMsedBlock) {
+    const double m = mats[i];
+    s_mr[i] = make_double2(m, 1.0 / m);
+  }
+  __syncthreads();
+  const int my_steps = nobs - 1;
+  const int my_iters = my_steps + 1;  // iteration t: the comparison of step t − 1, then step t
+  atomicMax(&s_iters_max, live ? my_iters : 0);
+
+  const double* th = theta + (size_t)bb * P;
+  Model mdl;
+  State st;
+  decode<STATIC, HASB>(th, space, mdl);
+  init_state(mdl, st);
+  const double fN = (double)N;
+
+  double mse = 0.0;
+  bool fail = false;
+  bool pred_fail = false;
+  Grad g;
+  grad_zero(g);
+  double bpost[kM] = {0.0, 0.0, 0.0};  // the β step t − 1 predicted from
+  bool pred_only = false;              // step t − 1 was prediction-only
+
+  __syncthreads();
+  const int niter = s_iters_max;
+  const int CHY = TC * N;
+
+  // ---- panel staging, as msed_kernel ----
+  double pre[kMsedPre];
+  auto load_chunk = [&](int c) {
+    const size_t base = (size_t)c * CHY;
+    const size_t lim = (size_t)T * N;
+#pragma unroll
+    for (int r = 0; r < kMsedPre; ++r) {
+      const int e = r * kMsedBlock + tid;
+      const size_t gi = base + e;
+      pre[r] = (e < CHY && gi < lim) ? Y[gi] : 0.0;
+    }
+  };
+  auto store_chunk = [&]() {
+#pragma unroll
+    for (int r = 0; r < kMsedPre; ++r) {
+      const int e = r * kMsedBlock + tid;
+      if (e < CHY) s_y[e] = pre[r];
+    }
+  };
+  if (niter > 0) {
+    load_chunk(0);
+    store_chunk();
+    __syncthreads();
+    load_chunk(1);
+  }
+
+  for (int t = 0; t < niter; ++t) {
+    const int tt = t % TC;
+    const bool act = live && t < my_iters;
+    if (act) {
+      const double* col = s_y + tt * N;  // t < nobs: always a data column here
+      // ---- first pass: the loadings at γ ----
+      const Lambda la = make_lambda(st.gamma);
+      GradStats<!STATIC> sa;
+      auto leaf_a = [&](int c, GradStats<!STATIC>& s) {
+        s.zero();
+        for (int i = c; i < N; i += kMsedClasses) {
+          const double2 mr = s_mr[i];
+          double z, z2, z3;
+          loadings(la, mr.x, mr.y, z, z2, z3);
+          const double y = col[i];
+          accum_ols(s.s.o, z2, z3, y);
+          if constexpr (!STATIC) {
+            double d2, d3;
+            dloadings(la, mr.x, z, z2, d2, d3);
+            accum_score(s.s.d, z2, z3, d2, d3, y);
+          }
+          const double v = y - fitted(st.beta, z2, z3);
+          s.s.vv = mfma(v, v, s.s.vv);
+          accum_zv(s.zv, z2, z3, v);
+        }
+      };
+      class_tree<KQ>(j, leaf_a, sa);
+      sa.s.each([](double x) { return group_sum_desc<L>(x); });
+#pragma unroll
+      for (int k = 0; k < kM; ++k) sa.zv[k] = group_sum_desc<L>(sa.zv[k]);
+
+      if (t >= 1) {
+        // v = y_t − ŷ_t; mse −= v'v; a non-finite running sum returns −Inf (filter.jl:226-234)
+        mse += pred_fail ? -__builtin_inf() : -sa.s.vv;
+        fail = fail || !(fabs(mse) <= __DBL_MAX__);
+        grad_accum(mdl, pred_only, sa.zv, bpost, g);
+      }
+
+      if (t < my_steps) {
+        // ---- step t (filter.jl:52-110), as msed_kernel ----
+        pred_only = col[0] != col[0];
+        pred_fail = false;
+        if (pred_only) {
+          advance<HASB>(mdl, st);
+        } else if (bool ridged = false; !ols(sa.s.o, fN, st.beta, ridged)) {
+          pred_fail = true;
+        } else {
+          bool ok = true;
+          if constexpr (!STATIC) {
+            double sc;
+            if constexpr (SCALED) {
+              Refine sr;
+              auto leaf_r = [&](int c, Refine& s) {
+                s.zero();
+                for (int i = c; i < N; i += kMsedClasses) {
+                  const double2 mr = s_mr[i];
+                  double z, z2, z3, d2, d3;
+                  loadings(la, mr.x, mr.y, z, z2, z3);
+                  dloadings(la, mr.x, z, z2, d2, d3);
+                  accum_refine(s.r, st.beta, z2, z3, d2, d3, col[i]);
+                }
+              };
+              class_tree<KQ>(j, leaf_r, sr);
+#pragma unroll
+              for (int k = 0; k < NREFINE; ++k) sr.r[k] = group_sum_desc<L>(sr.r[k]);
+              sc = score_refined(sa.s.o, fN, ridged, sa.s.d, sr.r, st.beta);
+            } else {
+              sc = score(sa.s.d, st.beta);
+            }
+            update_gamma<SCALED>(mdl, st, sc);
+            // ---- second pass: the loadings at the updated γ ----
+            const Lambda lb = make_lambda(st.gamma);
+            Stats<false> sb;
+            auto leaf_b = [&](int c, Stats<false>& s) {
+              s.zero();
+              for (int i = c; i < N; i += kMsedClasses) {
+                const double2 mr = s_mr[i];
+                double z, z2, z3;
+                loadings(lb, mr.x, mr.y, z, z2, z3);
+                accum_ols(s.o, z2, z3, col[i]);
+              }
+            };
+            class_tree<KQ>(j, leaf_b, sb);
+#pragma unroll
+            for (int k = 0; k < NOLS; ++k) sb.o[k] = group_sum_desc<L>(sb.o[k]);
+            ok = ols(sb.o, fN, st.beta);
+          }
+          if (ok) {
+#pragma unroll
+            for (int k = 0; k < kM; ++k) bpost[k] = st.beta[k];
+            advance<HASB>(mdl, st);
+          } else {
+            pred_fail = true;
+          }
+        }
+      }
+    }
+    if (tt == TC - 1) {  // chunk done: its buffer takes the prefetched chunk, prefetch the one after
+      __syncthreads();
+      store_chunk();
+      __syncthreads();
+      load_chunk(t / TC + 2);
+    }
+  }
+
+  if (!live || j != 0) return;
+  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
+  if (fail) {
+    ll = -__builtin_inf();
+    atomicAdd(&flags[1], 1u);
+  }
+  out[b] = ll;
+  double go[kGrad];
+  grad_finish(g, th, P, space, fN, nobs, fail, go);
+#pragma unroll
+  for (int k = 0; k < kGrad; ++k) grad[(size_t)b * kGrad + k] = go[k];
+}
+
+template <int L, bool STATIC, bool HASB, bool SCALED>
+hipError_t launch_grad_variant(const LaunchArgs& a, int TC, double* grad) {
+  constexpr int GPB = kMsedBlock / L;
+  const int grid = (a.B + GPB - 1) / GPB;
+  const size_t shmem = sizeof(double) * (size_t)(2 * a.N + TC * a.N);
+  hipLaunchKernelGGL((lambda_grad_kernel<L, STATIC, HASB, SCALED>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
+                     a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, grad, a.flags,
+                     a.flags_next);
+  return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_grad_lanes(int kind, const LaunchArgs& a, int TC, double* grad) {
+  switch (kind) {
+    case YFM_MODEL_NS: return launch_grad_variant<L, true, false, false>(a, TC, grad);
+    case YFM_MODEL_SD_NS: return launch_grad_variant<L, false, true, false>(a, TC, grad);
+    case YFM_MODEL_RWSD_NS: return launch_grad_variant<L, false, false, false>(a, TC, grad);
+    case YFM_MODEL_SSD_NS: return launch_grad_variant<L, false, true, true>(a, TC, grad);
+    case YFM_MODEL_SRWSD_NS: return launch_grad_variant<L, false, false, true>(a, TC, grad);
+  }
+  return hipErrorInvalidValue;
+}
+
 template <int L, bool STATIC, bool HASB, bool SCALED>
 hipError_t launch_variant(const LaunchArgs& a, int TC, const MsedOut* ro) {
   constexpr int GPB = kMsedBlock / L;
@@ -422,11 +663,16 @@ hipError_t launch_lanes(int kind, const LaunchArgs& a, int TC, const MsedOut* ro
   return hipErrorInvalidValue;
 }
 
+// columns per chunk: the prefetch registers hold ≤ kMsedPre·256 yields (0: N is out of range)
+int chunk_columns(int N) {
+  if (N < 1) return 0;
+  const int TC = (kMsedPre * kMsedBlock) / N;
+  return TC > 32 ? 32 : TC;
+}
+
 hipError_t launch_any(int kind, const LaunchArgs& a, int lanes, const MsedOut* ro) {
-  // columns per chunk: the prefetch registers hold ≤ kMsedPre·256 yields
-  int TC = (kMsedPre * kMsedBlock) / a.N;
-  if (TC > 32) TC = 32;
-  if (TC < 1 || a.N < 1) return hipErrorInvalidValue;
+  const int TC = chunk_columns(a.N);
+  if (TC < 1) return hipErrorInvalidValue;
   switch (lanes) {
     case 4: return launch_lanes<4>(kind, a, TC, ro);
     case 16: return launch_lanes<16>(kind, a, TC, ro);
@@ -455,6 +701,16 @@ int msed_lanes_for(int B) {
 }
 
 hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes) { return launch_any(kind, a, lanes, nullptr); }
+
+hipError_t launch_msed_grad(int kind, const LaunchArgs& a, int lanes, double* grad) {
+  const int TC = chunk_columns(a.N);
+  if (TC < 1) return hipErrorInvalidValue;
+  switch (lanes) {
+    case 4: return launch_grad_lanes<4>(kind, a, TC, grad);
+    case 16: return launch_grad_lanes<16>(kind, a, TC, grad);
+  }
+  return hipErrorInvalidValue;
+}
 
 hipError_t launch_msed_record(int kind, const LaunchArgs& a, int lanes, const MsedRecord& r) {
   MsedOut ro;

@@ -290,11 +290,78 @@ YFM_MHD void advance(const Model& m, State& s) {
   for (int r = 0; r < kM; ++r) s.beta[r] = nb[r];
 }
 
+// ---- ∂loss/∂(δ, Φ) --------------------------------------------------------------------------------------------
+// On a data column the step replaces β by an OLS fit and takes the score at that β (filter.jl:52-91), so γ, the
+// loadings and β_post never see δ or Φ: they enter only the prediction β_pred = μ + Φβ_post = δ + Φ(β_post − δ).
+// With v = y_{t+1} − Zβ_pred at the loadings Z the prediction used and s = Z'v,
+//   loss = −Σ‖v‖²/(N·nobs),  ∂loss/∂δ = 2/(N·nobs)·Σ(I − Φ)'s,  ∂loss/∂Φ = 2/(N·nobs)·Σ s(β_post − δ)'
+// and no tangent is carried through the recursion.  A missing first column makes step 1 prediction-only from
+// β₀ = δ, so β_pred = δ: that step adds s to ∂/∂δ and nothing to ∂/∂Φ.  A missing column anywhere else inside the
+// window is compared (filter.jl:226-234) and makes the loss −Inf, whose gradient is NaN.
+constexpr int kGrad = kM + kM * kM;  // δ(3), then vec Φ column-major: the order of θ's last 12 rows
+
+struct Grad {
+  double d[kM];       // Σ ∂β_pred'/∂δ · s
+  double F[kM][kM];   // Σ s (β_post − δ)', F[r][c] ↔ Φ[r][c]
+};
+
+YFM_MHD void grad_zero(Grad& g) {
+  for (int r = 0; r < kM; ++r) {
+    g.d[r] = 0.0;
+    for (int c = 0; c < kM; ++c) g.F[r][c] = 0.0;
+  }
+}
+
+// Z'v of one maturity into s (the sums the comparison pass adds to its statistics)
+YFM_MHD void accum_zv(double (&s)[kM], double z2, double z3, double v) {
+  s[0] += v;
+  s[1] = mfma(z2, v, s[1]);
+  s[2] = mfma(z3, v, s[2]);
+}
+
+// One compared prediction: s = Z'v; bpost the β the prediction advanced from (unused where pred_only, the
+// prediction-only first step)
+YFM_MHD void grad_accum(const Model& m, bool pred_only, const double (&s)[kM], const double (&bpost)[kM], Grad& g) {
+  if (pred_only) {
+    for (int c = 0; c < kM; ++c) g.d[c] += s[c];
+    return;
+  }
+  for (int c = 0; c < kM; ++c) {
+    double a = 0.0;  // column c of (I − Φ) against s
+    for (int r = 0; r < kM; ++r) a = mfma((r == c ? 1.0 : 0.0) - m.Phi[r][c], s[r], a);
+    g.d[c] += a;
+    const double db = bpost[c] - m.beta0[c];
+    for (int r = 0; r < kM; ++r) g.F[r][c] = mfma(s[r], db, g.F[r][c]);
+  }
+}
+
+// The 12 entries in the caller's space: scaled by 2/(N·nobs); space 0 multiplies the diagonal of Φ by
+// d from_R_to_11/dx = 2y/(1 + y)², y = eˣ (δ and the off-diagonal entries are identity).  A candidate whose loss is
+// −Inf (fail) gets NaN in all 12.
+YFM_MHD void grad_finish(const Grad& g, const double* th, int P, int space, double n, int nobs, bool fail,
+                         double (&out)[kGrad]) {
+  const double sc = 2.0 / n / (double)nobs;
+  for (int c = 0; c < kM; ++c) out[c] = g.d[c] * sc;
+  for (int c = 0; c < kM; ++c)
+    for (int r = 0; r < kM; ++r) {
+      double v = g.F[r][c] * sc;
+      if (space == 0 && r == c) {
+        const double y = exp(th[P - kM * kM + c * kM + r]);
+        v = v * (2.0 * y / ((1.0 + y) * (1.0 + y)));
+      }
+      out[kM + c * kM + r] = v;
+    }
+  if (fail)
+    for (int k = 0; k < kGrad; ++k) out[k] = __builtin_nan("");
+}
+
 // One filter step on the column y (N yields) with every maturity visited in order — the form the host check
 // runs; the kernel distributes the two accumulation loops over a lane group and runs the same 3×3 functions.
 // Returns false where the reference's step returns −Inf (the state then stays as the failing call left it).
+// bpost, where given, receives the β a data step predicts from (a prediction-only step leaves it alone).
 template <bool STATIC, bool HASB, bool SCALED>
-YFM_MHD bool filter_step(const Model& m, State& s, const double* mats, const double* y, int N) {
+YFM_MHD bool filter_step(const Model& m, State& s, const double* mats, const double* y, int N,
+                         double* bpost = nullptr) {
   if (y[0] != y[0]) {  // isnan(y[1]) (filter.jl:53, :95): prediction only
     advance<HASB>(m, s);
     return true;
@@ -336,6 +403,8 @@ YFM_MHD bool filter_step(const Model& m, State& s, const double* mats, const dou
     }
     if (!ols(o2, (double)N, s.beta)) return false;
   }
+  if (bpost)
+    for (int r = 0; r < kM; ++r) bpost[r] = s.beta[r];
   advance<HASB>(m, s);
   return true;
 }
@@ -372,6 +441,44 @@ YFM_MHD double get_loss(const double* th, int space, const double* mats, const d
     if (!(fabs(mse) <= 1.79769313486231570815e308)) return -HUGE_VAL;  // isinf || isnan (filter.jl:232-234)
   }
   return mse / (double)N / (double)nobs;
+}
+
+// get_loss with ∂loss/∂(δ, Φ) in the caller's space (grad: kGrad entries).  The loss is get_loss's, sum for sum.
+template <bool STATIC, bool HASB, bool SCALED>
+YFM_MHD double get_loss_grad(const double* th, int space, const double* mats, const double* Y, int N, int nobs,
+                             double (&grad)[kGrad]) {
+  Model m;
+  State s;
+  decode<STATIC, HASB>(th, space, m);
+  init_state(m, s);
+  Grad g;
+  grad_zero(g);
+  const int P = STATIC ? 13 : (HASB ? 15 : 14);
+  double mse = 0.0;
+  bool fail = false;
+  for (int t = 0; t + 1 < nobs && !fail; ++t) {
+    const double* y = Y + (size_t)t * N;
+    const bool pred_only = y[0] != y[0];
+    double bpost[kM] = {0.0, 0.0, 0.0};
+    if (!filter_step<STATIC, HASB, SCALED>(m, s, mats, y, N, bpost)) {
+      fail = true;
+      break;
+    }
+    const Lambda l = make_lambda(s.gamma);
+    double vv = 0.0, zv[kM] = {0.0, 0.0, 0.0};
+    for (int i = 0; i < N; ++i) {
+      double z, z2, z3;
+      loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+      const double v = y[N + i] - fitted(s.beta, z2, z3);
+      vv = mfma(v, v, vv);
+      accum_zv(zv, z2, z3, v);
+    }
+    mse -= vv;
+    fail = !(fabs(mse) <= 1.79769313486231570815e308);
+    grad_accum(m, pred_only, zv, bpost, g);  // pred_only: t = 0 (a later missing column was compared: fail)
+  }
+  grad_finish(g, th, P, space, (double)N, nobs, fail, grad);
+  return fail ? -HUGE_VAL : mse / (double)N / (double)nobs;
 }
 
 }  // namespace msed

@@ -94,6 +94,36 @@ function loglik_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; sp
     ll, grad
 end
 
+"The λ models' loss and its gradient over parameter group \"2\" (optimization.jl:442-479): (loss[B], grad[12, B]),
+loss bitwise loglik_batch's (get_loss, filter.jl:209-243), grad[:, b] = ∂(+get_loss)/∂(δ, vec Φ) of Θ[:, b] in `space`
+— the rows are Θ's last 12.  NaN gradient columns where the loss is -Inf.  NS, SD-NS, RWSD-NS, SSD-NS, SRWSD-NS only."
+function lambda_loss_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,
+                                T_use::Union{Nothing,Vector{Cint}} = nothing)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    loss, grad = Vector{Float64}(undef, B), Matrix{Float64}(undef, 12, B)
+    GC.@preserve Θ loss grad T_use check(@ccall LIB.yfm_lambda_loss_grad_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, loss::Ptr{Cdouble},
+        grad::Ptr{Cdouble})::Cint)
+    loss, grad
+end
+
+"One Optim.NelderMead run (opt1, optimization.jl:442-451) per column of p (P×R, unconstrained) on the coordinates
+`inds` (1-based, as findall(param_groups .== g) gives them, optimization.jl:229), the others held: what estimate_steps!
+does for one NelderMead group of one group iteration (:218-247), all chains sharing one launch per round.  Returns
+(p with the block at Optim's minimizer, f[R] = compute_loss there, n_evals)."
+function nm_block(model, data::Matrix{Float64}, p::Matrix{Float64}, inds::Vector{Int}; T_use = nothing,
+                  iterations = 500, g_tol = 1e-6)
+    c = ensure_panel!(model, data)
+    P, R = size(p)
+    x, f, nev = copy(p), Vector{Float64}(undef, R), Ref{Clonglong}(0)
+    idx = Cint.(inds .- 1)
+    GC.@preserve x f idx T_use check(@ccall LIB.yfm_nm_block(c.ptr::Ptr{Cvoid}, kind(model)::Cint, x::Ptr{Cdouble},
+        Cint(P)::Cint, Cint(R)::Cint, tuse_ptr(T_use)::Ptr{Cint}, idx::Ptr{Cint}, Cint(length(idx))::Cint,
+        Cint(iterations)::Cint, Float64(g_tol)::Cdouble, f::Ptr{Cdouble}, nev::Ptr{Clonglong})::Cint)
+    x, f, nev[]
+end
+
 "Batched predict (filter.jl:250-282) on hcat(data[:, 1:T_use[b]], NaN × (horizon−1)); arrays get a trailing batch axis."
 function predict_batch(model, data::Matrix{Float64}, Θc::Matrix{Float64}; horizon::Integer = 1,
                        T_use::Union{Nothing,Vector{Cint}} = nothing)

@@ -10,8 +10,8 @@ from .params import (KIND_DNS, KIND_GNS, KIND_TVL, SPACE_CONSTRAINED, SPACE_UNCO
 from .models import (DNSModel, EstimationError, GNS5Model, SingularException, TVLambdaDNSModel, compute_loss, compute_loss_batch, compute_loss_grad_batch,
                      create_model, estimate_, estimate_batch, estimate_lbfgs_batch, estimate_steps_, filter_states, forecast_batch, get_loss, get_loss_array, get_loss_batch,
                      get_params, predict, set_params_, transform_params, untransform_params)
-from .models import (MSEDLambdaModel, StaticLambdaModel, get_param_groups, try_initializations,
-                     try_initializations_batch)
+from .models import (MSEDLambdaModel, StaticLambdaModel, compute_loss_grad_block, estimate_steps_batch,
+                     get_param_groups, try_initializations, try_initializations_batch)
 from .engine import Engine, get_engine
 from .driver import load_initial_parameters_, run
 from . import lbfgs
@@ -24,4 +24,5 @@ __all__ = [
     "get_engine", "run", "load_initial_parameters_", "compute_loss_grad_batch", "estimate_", "estimate_lbfgs_batch",
     "EstimationError", "lbfgs", "KIND_NS", "KIND_SD_NS", "KIND_RWSD_NS", "KIND_SSD_NS", "KIND_SRWSD_NS", "LAMBDA_KINDS",
     "StaticLambdaModel", "MSEDLambdaModel", "get_param_groups", "try_initializations", "try_initializations_batch",
+    "compute_loss_grad_block", "estimate_steps_batch",
 ]

@@ -53,9 +53,15 @@ SIGNATURES = {
     "yfm_loglik_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int,
                                                     _V, _V, _V, _V]),
     "yfm_last_batch_grad_unavailable": (ctypes.c_int, [_V, _LL]),
+    "yfm_nm_block": (ctypes.c_int, [_V, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _I, ctypes.c_int, ctypes.c_int,
+                                    ctypes.c_double, _D, _LL]),
+    "yfm_lambda_loss_grad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I,
+                                                  _D, _D]),
+    "yfm_lambda_loss_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
+                                                         ctypes.c_int, _V, _V, _V, _V]),
 }
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 # precision modes (include/yfm.h: enum yfm_precision)
 PREC_CERTIFIED, PREC_FP64 = 0, 1

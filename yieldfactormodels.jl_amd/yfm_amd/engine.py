@@ -131,6 +131,28 @@ class Engine:
                                                          ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
                                                          ctypes.c_void_p(stream) if stream else None))
 
+    def lambda_loss_grad(self, kind: int, theta, space: int = 0, T_use=None):
+        """(loss[B], grad[12, B]) of a λ model: get_loss as :meth:`loglik` returns it, bit for bit, and its
+        derivative with respect to δ(3) and vec Φ(9, column-major) — θ's last 12 rows — in the space passed
+        (include/yfm.h yfm_lambda_loss_grad_batch).  A candidate's gradient is NaN where its loss is −Inf."""
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        loss = np.empty(B, dtype=np.float64)
+        grad = np.empty((12, B), dtype=np.float64, order="F")
+        _lib.check(self.lib.yfm_lambda_loss_grad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                                       _lib.iptr(self._tuse(T_use, B)), _lib.dptr(loss),
+                                                       _lib.dptr(grad)))
+        return loss, grad
+
+    def lambda_loss_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int,
+                                space: int = 0, d_T_use: int | None = None, stream: int | None = None) -> None:
+        """Device-pointer variant of :meth:`lambda_loss_grad` (raw addresses; d_grad: 12×B column-major);
+        asynchronous on ``stream``."""
+        _lib.check(self.lib.yfm_lambda_loss_grad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
+                                                              ctypes.c_void_p(d_T_use) if d_T_use else None,
+                                                              ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
+                                                              ctypes.c_void_p(stream) if stream else None))
+
     def filter_states(self, kind: int, theta, space: int = 0, T_use=None):
         """Returns (loglik[B], beta[M, T-1, B], P[M, M, T-1, B]) — a_{t+1|t}, P_{t+1|t} after each filter! call."""
         Th = np.asfortranarray(np.atleast_2d(np.asarray(theta, dtype=np.float64).T).T)
@@ -210,6 +232,19 @@ class Engine:
                                          iterations, g_tol, max_group_iters, tol, _lib.dptr(th_c), _lib.dptr(p),
                                          _lib.dptr(init_c), _lib.dptr(ll), _lib.iptr(st), ctypes.byref(ne)))
         return dict(theta_c=th_c, p=p, init_c=init_c, ll=ll, status=st, n_evals=ne.value)
+
+    def nm_block(self, kind: int, p, idx, T_use=None, iterations: int = 500, g_tol: float = 1e-6):
+        """One Optim.NelderMead run per column of p (P×R, unconstrained) on the coordinates ``idx`` (0-based rows of
+        θ), the rest held (include/yfm.h yfm_nm_block).  Returns (p with the block at its minimiser — a copy —,
+        f[R] = compute_loss there, n_evals).  f is NaN, and the column unchanged, where the objective threw."""
+        X = self._batch(p, kind).copy(order="F")
+        P, R = X.shape
+        ix = np.ascontiguousarray(idx, dtype=np.int32)
+        f = np.empty(R)
+        ne = ctypes.c_longlong(0)
+        _lib.check(self.lib.yfm_nm_block(self.ctx, kind, _lib.dptr(X), P, R, _lib.iptr(self._tuse(T_use, R)),
+                                         _lib.iptr(ix), len(ix), iterations, g_tol, _lib.dptr(f), ctypes.byref(ne)))
+        return X, f, ne.value
 
     def last_flags(self):
         a, b = ctypes.c_longlong(0), ctypes.c_longlong(0)

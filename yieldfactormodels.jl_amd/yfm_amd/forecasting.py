@@ -28,7 +28,8 @@ import os
 import numpy as np
 
 from . import io as _io
-from .models import estimate_batch, _engine
+from . import params as _p
+from .models import estimate_batch, estimate_steps_batch, _engine
 
 
 def _tails(r: dict, T_b: np.ndarray, h: int) -> dict:
@@ -45,9 +46,10 @@ def _estimate_tasks(model, data, tasks, init_params, max_group_iters, group_tol,
     Theta0 = np.repeat(start[:, None], len(tasks), axis=1)
 
     def estimate(Th, tu):
-        return estimate_batch(model, data, Th, T_use=tu, space=1, iterations=iterations,
-                              max_group_iters=max_group_iters, tol=group_tol)
+        return _estimate(model, data, Th, tu, max_group_iters, group_tol, iterations)
 
+    if group is not None and _p.is_lambda_kind(model.kind):
+        raise NotImplementedError("the λ models' group estimation is not sharded over a process group (one GPU)")
     if group is not None:  # one process per GPU: windows split over the ranks, results all-gathered
         import torch
         from . import distributed as D
@@ -56,6 +58,16 @@ def _estimate_tasks(model, data, tasks, init_params, max_group_iters, group_tol,
     else:
         r = estimate(Theta0, tasks)
     return r["theta_c"], r["ll"], r["status"]
+
+
+def _estimate(model, data, Theta0, T_use, max_group_iters, group_tol, iterations) -> dict:
+    """estimate_steps! for every column of Θ₀: the Kalman models' single Nelder–Mead group (yfm_estimate), the λ
+    models' block-coordinate descent over their default groups (estimate_steps_batch)."""
+    if _p.is_lambda_kind(model.kind):
+        return estimate_steps_batch(model, data, Theta0, T_use=T_use, max_group_iters=max_group_iters,
+                                    tol=group_tol, iterations=iterations)
+    return estimate_batch(model, data, Theta0, T_use=T_use, space=1, iterations=iterations,
+                          max_group_iters=max_group_iters, tol=group_tol)
 
 
 def forecast_windows(model, data, in_sample_end: int, in_sample_start: int, forecast_horizon: int, window_type: str,
@@ -142,8 +154,7 @@ def run_forecast_no_window(model, data, thread_id: str, in_sample_end: int, fore
     h = int(forecast_horizon)
     start = np.asarray(init_params, dtype=np.float64)
     start = start[:, 0] if start.ndim == 2 else start
-    est = estimate_batch(model, data[:, :in_sample_end], start[:, None], space=1, iterations=iterations,
-                         max_group_iters=max_group_iters, tol=group_tol)
+    est = _estimate(model, data[:, :in_sample_end], start[:, None], None, max_group_iters, group_tol, iterations)
     params = est["theta_c"][:, 0]
     tasks = np.arange(in_sample_end, T + 1, dtype=np.int32)
     eng = _engine(model, data)

@@ -98,11 +98,12 @@ class _Chain:
 
 
 def minimize_batch(value_and_grad, X0, iterations: int = 1000, g_tol: float = 1e-6, f_abstol: float = 1e-6,
-                   allow_f_increases: bool = True, max_linesearch: int = 60) -> dict:
+                   allow_f_increases: bool = True, max_linesearch: int = 60, with_index: bool = False) -> dict:
     """Minimise from every column of X0 (P×B).  Returns x (P×B), f (B), g (P×B), x0 (P×B: the starts after
     any rescaling), iterations (B), status (B: 0 converged, 1 iteration limit, 2 line search failed, 3 no finite
     start), converged (B), n_evals, rounds.  `allow_f_increases` is accepted for the reference's option set;
-    the Armijo test never accepts an increase."""
+    the Armijo test never accepts an increase.  `with_index`: the objective is called as
+    value_and_grad(X, idx), idx naming the chain of every column of X (finished chains drop out of the batch)."""
     X0 = np.array(X0, dtype=np.float64, order="F")
     if X0.ndim == 1:
         X0 = X0[:, None]
@@ -113,7 +114,7 @@ def minimize_batch(value_and_grad, X0, iterations: int = 1000, g_tol: float = 1e
     def evaluate(idx, cols):
         nonlocal n_evals, rounds
         X = np.asfortranarray(np.stack(cols, axis=1))
-        f, G = value_and_grad(X)
+        f, G = value_and_grad(X, idx) if with_index else value_and_grad(X)
         n_evals += len(idx)
         rounds += 1
         return np.asarray(f, dtype=np.float64), np.asarray(G, dtype=np.float64)

@@ -21,7 +21,9 @@ reference                                 here
 ``get_loss_array`` kalman/filter.jl:211-247 :func:`get_loss_array`
 forecast blocks forecasting.jl:236-250      :func:`forecast_batch`
 ``estimate_steps!`` optimization.jl:137-312 :func:`estimate_steps_` (+ batched
-                                            :func:`estimate_batch`)
+                                            :func:`estimate_batch`; the λ models:
+                                            :func:`estimate_steps_batch`, gradient of group "2":
+                                            :func:`compute_loss_grad_block`)
 ``estimate!`` optimization.jl:329-410       :func:`estimate_` (+ batched
                                             :func:`estimate_lbfgs_batch`; gradient:
                                             :func:`compute_loss_grad_batch`)
@@ -50,13 +52,12 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
+from . import groups as _groups
 from . import params as _p
 from .engine import get_engine
+from .groups import EstimationError  # noqa: F401  (raised here and by the group descent)
 
 
-class EstimationError(RuntimeError):
-    """estimate_steps! rethrows from the first group iteration (optimization.jl:249-253); estimate! throws
-    where compute_loss does."""
 
 
 class SingularException(ArithmeticError):
@@ -366,14 +367,22 @@ def forecast_batch(model: AbstractKalmanModel, data, Theta, T_use, horizon: int,
 
 def estimate_steps_(model: AbstractKalmanModel, data, all_params, param_groups=None, max_group_iters: int = 10,
                     tol: float = 1e-8, printing: bool = False, iterations: int = 500):
-    """estimate_steps! (optimization.jl:137-312) for a Kalman model: all_params (P×n, constrained; Kalman
-    models use column 1 only, :153) → (init_p, ll, best_p, ir), init_p and best_p constrained like the
+    """estimate_steps! (optimization.jl:137-312): all_params (P×n, constrained; column 1 only is used, :153)
+    → (init_p, ll, best_p, ir), init_p and best_p constrained like the
     reference: init_p = transform_params of the untransformed, sanitised and ×0.95-rescaled start
     (:157-184, :298-302).
-    Parameter groups other than all-"1" are not supported (the Kalman default, kalmanbasemodel.jl:150-159).
+    Kalman models: parameter groups other than all-"1" are not supported (their default, kalmanbasemodel.jl:150-159).
+    λ models: :func:`estimate_steps_batch` with one chain.
     `iterations`: the NelderMead budget per group (opt1, optimization.jl:442-451: 500)."""
     A = np.asarray(all_params, dtype=np.float64)
     start = A[:, 0] if A.ndim == 2 else A
+    if _p.is_lambda_kind(model.kind):
+        # the λ models: block-coordinate descent over param_groups (default get_param_groups), column 1 only (:153)
+        r = estimate_steps_batch(model, data, start[:, None], param_groups=param_groups,
+                                 max_group_iters=max_group_iters, tol=tol, iterations=iterations)
+        if printing:
+            print(f"✓ Best overall LL = {r['ll'][0]} from start 1")
+        return r["init_c"][:, 0].copy(), float(r["ll"][0]), r["theta_c"][:, 0].copy(), 0
     if param_groups is not None and any(g != "1" for g in param_groups):
         raise NotImplementedError("Kalman models estimate every parameter in group \"1\"")
     r = estimate_batch(model, data, start[:, None], max_group_iters=max_group_iters, tol=tol, iterations=iterations)
@@ -393,12 +402,80 @@ def estimate_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, space: 
                         max_group_iters=max_group_iters, tol=tol)
 
 
+def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, param_groups=None,
+                         max_group_iters: int = 10, tol: float = 1e-8, iterations=None) -> dict:
+    """R independent estimate_steps! chains of a λ model (optimization.jl:137-312), one per column of Θ₀ (P×R,
+    constrained, as all_params) on the window ``data[:, :T_use[r]]``, advancing in lockstep: every step of the
+    block-coordinate descent (:mod:`yfm_amd.groups`) is one batched call for all unfinished chains.
+
+    * start: :func:`try_initializations_batch` for the score-driven kinds (NS keeps its start,
+      optimization.jl:33-35), untransform, sanitise, ×0.95 while the loss is not finite;
+    * group "1" / "4" (and any id without an optimiser of its own): Optim.NelderMead with opt1 on the group's
+      coordinates — ``yfm_nm_block``, one launch per round for all chains;
+    * group "2": L-BFGS (:mod:`yfm_amd.lbfgs`, opt2's options) on δ and Φ with value and gradient rows from
+      :func:`compute_loss_grad_block`, one launch per round;
+    * groups "3" / "5" (Adam) and a "2" group holding a leading parameter raise NotImplementedError.
+
+    `iterations` caps both optimisers' budgets (None: the reference's 500 and 250).  Returns what
+    :func:`estimate_batch` returns — theta_c, p, init_c (the reference's init_p), ll, status, n_evals — plus
+    evals_by_group, rounds_by_group and group_iters."""
+    if not _p.is_lambda_kind(model.kind):
+        raise NotImplementedError("estimate_steps_batch is the λ models' driver; Kalman models use estimate_batch")
+    kind = model.kind
+    Th = np.asarray(Theta0, dtype=np.float64)
+    Th = Th.reshape(Th.shape[0], -1)
+    P, R = Th.shape
+    groups = get_param_groups(model, () if param_groups is None else param_groups)
+    n_lead = P - model.base.M * (model.base.M + 1)
+    _groups.check_groups(groups, n_lead)  # before any launch
+    tu = None if T_use is None else np.ascontiguousarray(np.broadcast_to(T_use, (R,)), dtype=np.int32)
+    if isinstance(model, MSEDLambdaModel):
+        Th, _ = try_initializations_batch(Th, model, data, T_use=tu)
+    eng = _engine(model, data)
+
+    def win(cols):
+        return None if tu is None else tu[cols]
+
+    def value(X, cols):
+        return -eng.loglik(kind, X, space=_p.SPACE_UNCONSTRAINED, T_use=win(cols))
+
+    def value_grad(X, cols, rows):
+        loss, g = eng.lambda_loss_grad(kind, X, space=_p.SPACE_UNCONSTRAINED, T_use=win(cols))
+        return -loss, -g[np.asarray(rows) - n_lead]
+
+    def nelder_mead(X, cols, rows, its, g_tol):
+        return eng.nm_block(kind, X, rows, T_use=win(cols), iterations=its, g_tol=g_tol)
+
+    opts = dict(_groups.LBFGS_OPTIONS)
+    nm_its = _groups.NM_ITERATIONS
+    if iterations is not None:
+        opts["iterations"] = min(opts["iterations"], int(iterations))
+        nm_its = min(nm_its, int(iterations))
+    r = _groups.descend(_p.untransform_params(kind, Th), groups, value, value_grad, nelder_mead, n_lead,
+                        max_group_iters=max_group_iters, tol=tol, nm_iterations=nm_its, lbfgs_options=opts)
+    return dict(theta_c=np.asfortranarray(_p.transform_params(kind, r["p"])), p=r["p"],
+                init_c=np.asfortranarray(_p.transform_params(kind, r["init"])), ll=r["ll"], status=r["status"],
+                n_evals=r["n_evals"], evals_by_group=r["evals_by_group"], rounds_by_group=r["rounds_by_group"],
+                group_iters=r["group_iters"])
+
+
 def compute_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
     """Batched compute_loss with its gradient — what estimate!'s TwiceDifferentiable(...; autodiff=:forward)
     evaluates (optimization.jl:367): (−loglik[B], −∂loglik/∂θ[P, B]) for every unconstrained θ_b, the
     reference's loss sign.  DNS with N ≤ 64; NaN gradient columns as in :meth:`Engine.loglik_grad`."""
     ll, g = _engine(model, data).loglik_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
     return -ll, -g
+
+
+def compute_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_use=None):
+    """Batched compute_loss of a λ model with its gradient over parameter group "2" — what Optim.LBFGS evaluates
+    in estimate_steps! for the δ/Φ block (optimization.jl:442-479): (−loss[B], −∂loss/∂θ[12, B]) for every
+    unconstrained θ_b, the rows being θ's last 12 (δ, then vec Φ column-major).  NaN gradient columns where the
+    loss is −Inf."""
+    if not _p.is_lambda_kind(model.kind):
+        raise NotImplementedError("the δ/Φ block gradient is the λ models'; Kalman models use compute_loss_grad_batch")
+    loss, g = _engine(model, data).lambda_loss_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
+    return -loss, -g
 
 
 def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 1, **opts) -> dict:

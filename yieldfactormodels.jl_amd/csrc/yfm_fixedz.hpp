@@ -47,31 +47,67 @@ __device__ __forceinline__ double collapsed_cov(const double (&R)[M][M], const d
   return det;
 }
 
+// The head of the mean half: c = ĉ − β and the residual rr = ‖ỹ − Zĉ‖² = ỹ'ỹ − z̃'ĉ, with ĉ = G⁻¹(0, z̃) + ȳe₁.
+// One body for collapsed_mean and collapsed_update, so every kernel rounds these values the same way.
+//
+// M = 3 (DNS) reads G⁻¹ itself (Gi: FixedZFilter::setup holds it before it scales it to R), 9 operations
+// instead of 12: no z̃/σ², no fma onto a zero, and ȳ − β₀ seeds c₀'s chain instead of two additions after it
+// (ĉ₀ is never formed: nothing else reads it).  M = 5 keeps the R·(z̃/σ²) form: its kernels fill the register
+// file and have no room for 20 more doubles of G⁻¹.
+template <int M>
+constexpr bool mean_reads_ginv() { return M == 3; }
+
+template <int M>
+__device__ __forceinline__ void collapsed_innov(const double (&zt)[M - 1], double ybar, double ytt,
+                                                const double (&R)[M][M], const double (&Gi)[M][M], double rsig2,
+                                                const double (&beta)[M], double (&c)[M], double& rr) {
+  if constexpr (mean_reads_ginv<M>()) {
+    double ch[M];  // ĉ_j, j ≥ 1
+#pragma unroll
+    for (int i = 1; i < M; ++i) {
+      double s = Gi[i][1] * zt[0];
+#pragma unroll
+      for (int j = 2; j < M; ++j) s = fma(Gi[i][j], zt[j - 1], s);
+      ch[i] = s;
+    }
+    rr = ytt;
+#pragma unroll
+    for (int j = 1; j < M; ++j) rr = fma(-zt[j - 1], ch[j], rr);
+    double c0 = ybar - beta[0];
+#pragma unroll
+    for (int j = 1; j < M; ++j) c0 = fma(Gi[0][j], zt[j - 1], c0);
+    c[0] = c0;
+#pragma unroll
+    for (int i = 1; i < M; ++i) c[i] = ch[i] - beta[i];
+  } else {
+    double zs[M - 1];
+#pragma unroll
+    for (int j = 0; j < M - 1; ++j) zs[j] = zt[j] * rsig2;
+    double ch[M];  // ĉ = G⁻¹(0, z̃) (= R/σ² · (0, z̃))
+#pragma unroll
+    for (int i = 0; i < M; ++i) {
+      double s = 0.0;
+#pragma unroll
+      for (int j = 1; j < M; ++j) s = fma(R[i][j], zs[j - 1], s);
+      ch[i] = s;
+    }
+    rr = ytt;
+#pragma unroll
+    for (int j = 1; j < M; ++j) rr = fma(-zt[j - 1], ch[j], rr);
+    ch[0] += ybar;
+#pragma unroll
+    for (int i = 0; i < M; ++i) c[i] = ch[i] - beta[i];
+  }
+}
+
 template <int M>
 __device__ __forceinline__ void collapsed_mean(const double (&zt)[M - 1], double ybar, double ytt, const double (&R)[M][M],
-                                               double rsig2, const double (&beta)[M], const double (&Pm)[M][M],
-                                               const LDLT<M>& f, double (&bf)[M], double& q) {
-  double zs[M - 1];
+                                               const double (&Gi)[M][M], double rsig2, const double (&beta)[M],
+                                               const double (&Pm)[M][M], const LDLT<M>& f, double (&bf)[M], double& q) {
+  double c[M], x[M], rr;
+  collapsed_innov<M>(zt, ybar, ytt, R, Gi, rsig2, beta, c, rr);
 #pragma unroll
-  for (int j = 0; j < M - 1; ++j) zs[j] = zt[j] * rsig2;
-  double ch[M];  // ĉ = G⁻¹(0, z̃) (= R/σ² · (0, z̃))
-#pragma unroll
-  for (int i = 0; i < M; ++i) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 1; j < M; ++j) s = fma(R[i][j], zs[j - 1], s);
-    ch[i] = s;
-  }
-  double rr = ytt;  // ‖ỹ − Zĉ‖² = ỹ'ỹ − z̃'ĉ
-#pragma unroll
-  for (int j = 1; j < M; ++j) rr = fma(-zt[j - 1], ch[j], rr);
-  ch[0] += ybar;
-  double c[M], x[M];
-#pragma unroll
-  for (int i = 0; i < M; ++i) {
-    c[i] = ch[i] - beta[i];
-    x[i] = c[i];
-  }
+  for (int i = 0; i < M; ++i) x[i] = c[i];
   f.solve(x);  // x = S⁻¹c
   double cx = 0.0;
 #pragma unroll
@@ -91,29 +127,14 @@ __device__ __forceinline__ void collapsed_mean(const double (&zt)[M - 1], double
 // collapsed_cov + collapsed_mean, as one body (the per-lane kernels keep this form).
 template <int M>
 __device__ __forceinline__ void collapsed_update(const double (&zt)[M - 1], double ybar, double ytt,
-                                                 const double (&R)[M][M], double rsig2, const double (&beta)[M],
-                                                 const double (&Pm)[M][M], double (&bf)[M], double (&Pf)[M][M],
-                                                 double& det, double& q) {
-  double zs[M - 1];
-#pragma unroll
-  for (int j = 0; j < M - 1; ++j) zs[j] = zt[j] * rsig2;
-  double ch[M];  // ĉ = G⁻¹(0, z̃) (= R/σ² · (0, z̃))
-#pragma unroll
-  for (int i = 0; i < M; ++i) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 1; j < M; ++j) s = fma(R[i][j], zs[j - 1], s);
-    ch[i] = s;
-  }
-  double rr = ytt;  // ‖ỹ − Zĉ‖² = ỹ'ỹ − z̃'ĉ
-#pragma unroll
-  for (int j = 1; j < M; ++j) rr = fma(-zt[j - 1], ch[j], rr);
-  ch[0] += ybar;
+                                                 const double (&R)[M][M], const double (&Gi)[M][M], double rsig2,
+                                                 const double (&beta)[M], const double (&Pm)[M][M], double (&bf)[M],
+                                                 double (&Pf)[M][M], double& det, double& q) {
+  double c[M], rr;
+  collapsed_innov<M>(zt, ybar, ytt, R, Gi, rsig2, beta, c, rr);
   double S[M][M];
-  double c[M];
 #pragma unroll
   for (int i = 0; i < M; ++i) {
-    c[i] = ch[i] - beta[i];
 #pragma unroll
     for (int j = 0; j <= i; ++j) S[i][j] = Pm[i][j] + R[i][j];  // LDLᵀ reads the lower triangle only
   }
@@ -317,6 +338,7 @@ struct FixedZFilter {
   Params<M, LEAD> p;
   double sigma2, rsig2;
   double R[M][M];  // σ²(Z'Z)⁻¹ (meaningful on collapsed lanes only)
+  double Gi[M][M];  // (Z'Z)⁻¹, symmetrised: what the mean update of M = 3 reads (collapsed_innov; unset otherwise)
   double logdetG = 0.0;
   bool collapsed = false, init_ok = false;
   int N = 0;
@@ -416,7 +438,7 @@ struct FixedZFilter {
   __device__ __forceinline__ void steady_step(const double (&zc)[M - 1], double2 yb_c) {
     double bf[M], q, det;
     if constexpr (kCacheFactors) {
-      collapsed_mean<M>(zc, yb_c.x, yb_c.y, R, rsig2, beta, Pm, fs, bf, q);
+      collapsed_mean<M>(zc, yb_c.x, yb_c.y, R, Gi, rsig2, beta, Pm, fs, bf, q);
       det = dets;
     } else {
       double S[M][M];
@@ -426,7 +448,7 @@ struct FixedZFilter {
         for (int j = 0; j <= i; ++j) S[i][j] = Pm[i][j] + R[i][j];
       LDLT<M> fl;
       det = fl.factor(S);
-      collapsed_mean<M>(zc, yb_c.x, yb_c.y, R, rsig2, beta, Pm, fl, bf, q);
+      collapsed_mean<M>(zc, yb_c.x, yb_c.y, R, Gi, rsig2, beta, Pm, fl, bf, q);
     }
     propagate_mean_f<M>([&](int i, int j) { return p.Phi[i][j]; }, p.delta, bf, beta);
     last_det = det;
@@ -472,7 +494,10 @@ struct FixedZFilter {
 #pragma unroll
     for (int i = 0; i < M; ++i)
 #pragma unroll
-      for (int j = 0; j < M; ++j) R[i][j] = sigma2 * 0.5 * (X[i][j] + X[j][i]);
+      for (int j = 0; j < M; ++j) {
+        R[i][j] = sigma2 * 0.5 * (X[i][j] + X[j][i]);
+        if constexpr (mean_reads_ginv<M>()) Gi[i][j] = 0.5 * (X[i][j] + X[j][i]);
+      }
     if (do_init) init_ok = init_state<M, LEAD>(p, beta, Pm);
   }
 
@@ -481,9 +506,9 @@ struct FixedZFilter {
     if constexpr (SPLIT_FORM) {
       LDLT<M> fl;
       det = collapsed_cov<M>(R, Pm, fl, Pf);
-      collapsed_mean<M>(zc, yb_c.x, yb_c.y, R, rsig2, beta, Pm, fl, bf, q);
+      collapsed_mean<M>(zc, yb_c.x, yb_c.y, R, Gi, rsig2, beta, Pm, fl, bf, q);
     } else {
-      collapsed_update<M>(zc, yb_c.x, yb_c.y, R, rsig2, beta, Pm, bf, Pf, det, q);
+      collapsed_update<M>(zc, yb_c.x, yb_c.y, R, Gi, rsig2, beta, Pm, bf, Pf, det, q);
     }
   }
 

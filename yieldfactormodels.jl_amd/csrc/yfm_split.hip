@@ -333,7 +333,7 @@ __global__ __launch_bounds__(kSplitBlock, 1) void dns_split_kernel(
         Pm[2][2] = slot[11 * 64];
         const double det = slot[12 * 64];
         double bf[M], q;
-        collapsed_mean<M>(zc, yb.x, yb.y, f.R, f.rsig2, f.beta, Pm, fl, bf, q);
+        collapsed_mean<M>(zc, yb.x, yb.y, f.R, f.Gi, f.rsig2, f.beta, Pm, fl, bf, q);
         if (fast) {
           if (!RECORD || det != 0.0) propagate_mean_f<M>(phi, f.p.delta, bf, f.beta);
           f.last_det = det;

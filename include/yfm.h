@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define YFM_ABI_VERSION 4
+#define YFM_ABI_VERSION 5
 
 typedef struct yfm_ctx yfm_ctx;
 
@@ -59,7 +59,30 @@ enum yfm_model_kind {
   YFM_MODEL_SD_NS = 4,   /* "SD-NS" / "4": MSEDλModel, P = 15 (mselambda.jl) */
   YFM_MODEL_RWSD_NS = 5, /* "RWSD-NS" / "5": random walk γ (no B), P = 14 */
   YFM_MODEL_SSD_NS = 6,  /* "SSD-NS" / "6": score scaled by its EWMA root (filter.jl:29-44, f = 0.98), P = 15 */
-  YFM_MODEL_SRWSD_NS = 8 /* "SRWSD-NS" / "7": scaled, random walk, P = 14 */
+  YFM_MODEL_SRWSD_NS = 8, /* "SRWSD-NS" / "7": scaled, random walk, P = 14 */
+  /* The neural Nelson–Siegel models (ABI 5; model_dictionary.jl:20-112, mseneural.jl, staticneural.jl): the same
+   * filter with L = 18 — γ[0..8] drives Z₂ and γ[9..17] drives Z₃, each block [w₁(3), b(3), w₂(3)] of a 1→3→1 tanh
+   * network without output bias, followed by the transforms of src/utils/neural_network_transform.jl (the
+   * -Anchored kinds: transform_bool = false).  tanh is the mathematical function.  θ_c = [γ(18), δ(3), vec Φ(9)],
+   * P = 30, for the static kinds and [A_unique, B_unique (absent for random walk), ω(18), δ(3), vec Φ(9)] for the
+   * score-driven ones, whose duplicator (`dynamics`) expands 2 (scalar: 9 + 9), 6 (block_diag: 3 each) or 18
+   * (diag) unique values: P = 34 / 42 / 66, random walk 32 / 36 / 48.  Unconstrained space: A → exp,
+   * B → 1/(1 + e^−x), the diagonal of Φ → from_R_to_11.  The scaled kinds' EWMA is per component with f = 0.9.
+   * 4 ≤ N ≤ 1024 (below 4 the transforms' anchor slots alias): other N return YFM_EUNSUPPORTED, as do
+   * yfm_estimate, yfm_filter_states, yfm_loglik_grad_batch and yfm_lambda_loss_grad_batch for these kinds.
+   * yfm_predict's states are 18×n per candidate and a yfm_forecast block has 3 + 18 + N rows. */
+  YFM_MODEL_NNS = 16,          /* "NNS" / "3": StaticNeuralModel */
+  YFM_MODEL_NNS_ANCHORED = 17, /* "NNS-Anchored" / "20" */
+  /* score-driven: YFM_MODEL_SD_NNS | dynamics | YFM_NNS_RW | YFM_NNS_SCALED | YFM_NNS_ANCHORED, dynamics 0 scalar
+   * ("1…"), 1 block_diag ("2…"), 2 diag ("3…"); value 3 in the low two bits is not a kind.  Reference codes
+   * "8" … "19" are {1,2,3}{SD,RWSD}-NNS then {1,2,3}{SSD,SRWSD}-NNS, "21" … "32" the same with -Anchored:
+   *   32 "1SD-NNS"/"8"    36 "1RWSD-NNS"/"9"    33 "2SD-NNS"/"10"   37 "2RWSD-NNS"/"11"   34 "3SD-NNS"/"12"   38 "3RWSD-NNS"/"13"
+   *   40 "1SSD-NNS"/"14"  44 "1SRWSD-NNS"/"15"  41 "2SSD-NNS"/"16"  45 "2SRWSD-NNS"/"17"  42 "3SSD-NNS"/"18"  46 "3SRWSD-NNS"/"19"
+   *   48 … 54 and 56 … 62: the same with "-Anchored", codes "21" … "26" and "27" … "32" */
+  YFM_MODEL_SD_NNS = 32,
+  YFM_NNS_RW = 4,        /* random walk γ: no B */
+  YFM_NNS_SCALED = 8,    /* scale_grad */
+  YFM_NNS_ANCHORED = 16  /* transform_bool = false */
 };
 
 /* param_space */

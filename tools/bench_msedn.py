@@ -1,0 +1,108 @@
+"""Cost of the batched loss of the neural Nelson–Siegel models (csrc/yfm_msedn.hip).
+
+    python tools/bench_msedn.py [--T 600] [--reps 7] [--warmup 2] [--cases abcd]
+
+The method of tools/bench_msed.py: one yfm_loglik_batch_device launch per case, HIP events around the launch,
+`warmup` untimed launches, the median of `reps` with min–max.  All at T = 600 on the N = 30 grid:
+  (a) one window's try_initializations grid — the start and its 256 trials, 257 candidates — for 1SD-NNS, 3SD-NNS
+      and 3SSD-NNS;
+  (b) the rolling driver's grid of 1RWSD-NNS: 240 T_use windows × 17 candidates = 4,080;
+  (c) 65,536 candidates of 1SD-NNS (the launch picks L = 4 there);
+  (d) NNS at 7,440 candidates.
+Each beside the SD-NS λ launch (csrc/yfm_msed.hip) at the same B, in the same visit; and, for scale, the Float64 NumPy
+restatement (tests/msedn_reference.py) timed on a few candidates and quoted per candidate.  Prints one JSON line.
+Not part of bench.py.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT / "yieldfactormodels.jl_amd"))
+sys.path.insert(0, str(ROOT / "tests"))
+sys.path.insert(0, str(ROOT / "tools"))
+
+import msedn_reference as R  # noqa: E402
+from bench_msed import launch_stats  # noqa: E402
+from yfm_amd import Engine  # noqa: E402
+from yfm_amd import params as P  # noqa: E402
+from yfm_amd import synthetic as S  # noqa: E402
+
+
+def grid(kind):
+    """The start and every trial of get_new_initial_params' two-half walk, constrained (P × 257, or P × 17)."""
+    start = S.theta0_constrained(kind)
+    cols, p, k = [start], start, 1
+    while (p := R.trial_params(kind, p, k)) is not None:
+        cols.append(p)
+        k += 1
+    return np.asfortranarray(np.stack(cols, axis=1))
+
+
+def numpy_ms_per_candidate(kind, mats, Y, Th, space, n=3):
+    t0 = time.perf_counter()
+    for b in range(n):
+        R.get_loss(kind, mats, Y, Th[:, b], space, R.FLOAT)
+    return 1e3 * (time.perf_counter() - t0) / n
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--T", type=int, default=600)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--big", type=int, default=65536)
+    ap.add_argument("--cases", default="abcd")
+    args = ap.parse_args()
+    torch.cuda.set_device(0)
+    eng = Engine(0)
+    mats = S.maturities_30()
+    Y = S.simulate_panel(P.KIND_NNS, args.T, maturities=mats)
+    eng.set_panel(Y, mats)
+    res = {"T": args.T, "N": len(mats), "cases": {}}
+    windows = np.linspace(args.T - 239, args.T, 240).astype(np.int32)
+
+    def lam(B, tu=None):
+        """The SD-NS λ launch at the same B (and windows)."""
+        Th = S.theta_batch(P.KIND_SD_NS, B, seed=5, bad_frac=0.0)
+        return launch_stats(eng, P.KIND_SD_NS, Th, 0, tu, args.reps, args.warmup)
+
+    if "a" in args.cases:
+        for name in ("1SD-NNS", "3SD-NNS", "3SSD-NNS"):
+            kind = next(k for k in P.NEURAL_KINDS if P.KIND_NAMES[k] == name)
+            G = grid(kind)
+            r = launch_stats(eng, kind, G, 1, None, args.reps, args.warmup)
+            r["numpy_restatement_ms_per_candidate"] = numpy_ms_per_candidate(kind, mats, Y, G, 1)
+            res["cases"][f"a_grid_{name}"] = r
+        res["cases"]["a_grid_SD-NS"] = lam(257)
+    if "b" in args.cases:
+        kind = P.neural_kind("scalar", True)
+        G = grid(kind)
+        n = G.shape[1]
+        tu = np.repeat(windows, n)
+        res["cases"]["b_windows_1RWSD-NNS"] = launch_stats(eng, kind, np.asfortranarray(np.tile(G, (1, 240))), 1, tu,
+                                                           args.reps, args.warmup)
+        res["cases"]["b_windows_SD-NS"] = lam(240 * n, tu)
+    if "c" in args.cases:
+        kind = P.neural_kind("scalar")
+        Th = S.theta_batch(kind, args.big, seed=5, bad_frac=0.0, a_range=(1e-5, 1e-4))
+        res["cases"]["c_big_1SD-NNS"] = launch_stats(eng, kind, Th, 0, None, args.reps, args.warmup)
+        res["cases"]["c_big_SD-NS"] = lam(args.big)
+    if "d" in args.cases:
+        Th = S.theta_batch(P.KIND_NNS, 7440, seed=5, bad_frac=0.0)
+        r = launch_stats(eng, P.KIND_NNS, Th, 0, None, args.reps, args.warmup)
+        r["numpy_restatement_ms_per_candidate"] = numpy_ms_per_candidate(P.KIND_NNS, mats, Y, Th, 0)
+        res["cases"]["d_NNS_7440"] = r
+        res["cases"]["d_SD-NS_7440"] = lam(7440)
+    print(json.dumps(res), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -45,7 +45,11 @@ int state_dim(int kind) {
 int n_lead(int kind) { return kind == YFM_MODEL_DNS ? 1 : kind == YFM_MODEL_TVL ? 0 : 2; }
 // L = length of base.gamma (kalmanbasemodel.jl:58): DNS 1 (dns.jl:18), TVλ 1 (tvλdns.jl:19, never set), GNS5 2,
 // the λ models 1 (mselambda.jl:29, staticlambda.jl:20)
-int gamma_dim(int kind) { return kind == YFM_MODEL_GNS5 ? 2 : (state_dim(kind) < 0 ? -1 : 1); }
+// the neural kinds 18 (mseneural.jl:29-30)
+int gamma_dim(int kind) {
+  if (yfm::msedn_kind(kind)) return 18;
+  return kind == YFM_MODEL_GNS5 ? 2 : (state_dim(kind) < 0 ? -1 : 1);
+}
 int param_count(int kind) {
   if (yfm::msed_kind(kind)) return yfm::msed_param_count(kind);
   const int M = state_dim(kind);
@@ -125,6 +129,15 @@ int check_batch(yfm_ctx* ctx, int kind, int space, int P, int B) {
     return set_error(YFM_EINVAL, "P = %d but model_kind %d has %d parameters", P, kind, param_count(kind));
   if (B < 0) return set_error(YFM_EINVAL, "B = %d < 0", B);
   if (ctx->T <= 0) return set_error(YFM_ENOPANEL, "no panel: call yfm_set_panel first");
+  if (yfm::msedn_kind(kind)) {
+    if (ctx->N < yfm::msedn_min_n())
+      return set_error(YFM_EUNSUPPORTED, "N = %d maturities: the neural kinds' transforms need N >= %d (below it their "
+                       "anchor slots alias)", ctx->N, yfm::msedn_min_n());
+    if (ctx->N > yfm::msedn_max_n())
+      return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the neural-model kernel's %d", ctx->N,
+                       yfm::msedn_max_n());
+    return YFM_OK;
+  }
   if (yfm::msed_kind(kind)) {
     if (ctx->N > yfm::msed_max_n())
       return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the λ-model kernel's %d", ctx->N, yfm::msed_max_n());
@@ -434,6 +447,9 @@ int check_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
 
 // The λ gradient entry points' model check: the five kinds of yfm_msed.hip only.
 int check_lambda_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
+  if (yfm::msedn_kind(kind))
+    return set_error(YFM_EUNSUPPORTED, "the delta/Phi loss gradient is not built for the neural kinds (model_kind %d)",
+                     kind);
   if (state_dim(kind) >= 0 && !yfm::msed_kind(kind))
     return set_error(YFM_EUNSUPPORTED, "the δ/Φ loss gradient is built for the λ kinds only (model_kind %d: use "
                      "yfm_loglik_grad_batch)", kind);

@@ -147,6 +147,15 @@ struct MsedRecord {
   double* load2 = nullptr;
 };
 hipError_t launch_msed_record(int kind, const LaunchArgs& a, int lanes, const MsedRecord& r);
+// Neural Nelson–Siegel models (yfm_msedn.hip: NNS, NNS-Anchored and the score-driven NNS kinds; the same filter with
+// γ ∈ ℝ¹⁸ and the loadings of two tanh networks).  msed_kind and msed_param_count answer for them too, so every
+// caller of the λ launchers reaches them: launch_msed and launch_msed_record forward here (r == nullptr: the loss;
+// MsedRecord's states are 18×ncol×B and a forecast block has 3 + 18 + N rows).  msedn_min_n ≤ N ≤ msedn_max_n.
+bool msedn_kind(int kind);
+int msedn_param_count(int kind);
+int msedn_min_n();
+int msedn_max_n();
+hipError_t launch_msedn(int kind, const LaunchArgs& a, int lanes, const MsedRecord* r);
 // Trajectory outputs (yfm_predict.hip) from a recorded state trajectory.
 struct PredictArgs {
   int kind, M, L, N, P, B, T;

@@ -31,14 +31,13 @@
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
 #include "yfm_msed.hpp"
+#include "yfm_msed_tree.hpp"
 
 namespace yfm {
 
 namespace {
 
-constexpr int kMsedBlock = 256;
-constexpr int kMsedPre = 8;      // panel doubles prefetched per thread per chunk
-constexpr int kMsedClasses = 16;  // residue classes of the summation tree (the largest L)
+using namespace msedtree;  // the mapping's constants and the summation tree (yfm_msed_tree.hpp)
 
 using namespace msed;
 
@@ -90,53 +89,6 @@ struct Refine {
     for (int k = 0; k < NREFINE; ++k) r[k] = a.r[k] + b.r[k];
   }
 };
-
-// x + (x of lane ^ 2^LVL): quad_perm for 1 and 2, ds_swizzle (the LDS crossbar, no memory) for 4, row_ror:8 for 8
-template <int LVL>
-__device__ __forceinline__ double xor_sum(double x) {
-  const int lo = __double2loint(x), hi = __double2hiint(x);
-  int plo, phi;
-  if constexpr (LVL == 2) {
-    constexpr int pat = (4 << 10) | 0x1f;  // bit-mask mode: and 0x1f, or 0, xor 4
-    plo = __builtin_amdgcn_ds_swizzle(lo, pat);
-    phi = __builtin_amdgcn_ds_swizzle(hi, pat);
-  } else {
-    constexpr int ctrl = LVL == 0 ? 0xB1 : LVL == 1 ? 0x4E : 0x128;
-    plo = __builtin_amdgcn_mov_dpp(lo, ctrl, 0xf, 0xf, true);
-    phi = __builtin_amdgcn_mov_dpp(hi, ctrl, 0xf, 0xf, true);
-  }
-  return x + __hiloint2double(phi, plo);
-}
-
-// the group's part of the tree: lane bits in descending order
-template <int L>
-__device__ __forceinline__ double group_sum_desc(double x) {
-  if constexpr (L >= 16) x = xor_sum<3>(x);
-  if constexpr (L >= 8) x = xor_sum<2>(x);
-  if constexpr (L >= 4) x = xor_sum<1>(x);
-  if constexpr (L >= 2) x = xor_sum<0>(x);
-  return x;
-}
-
-// a lane's part: the classes that agree with c in the bits below 4 − K; the node's last addition joins the
-// lowest of its free bits
-template <int K, class S, class Leaf>
-__device__ __forceinline__ void class_tree(int c, Leaf& leaf, S& s) {
-  if constexpr (K == 0) {
-    leaf(c, s);
-  } else {
-    S a, b;
-    class_tree<K - 1>(c, leaf, a);
-    class_tree<K - 1>(c | (kMsedClasses >> K), leaf, b);
-    s.add(a, b);
-  }
-}
-
-template <int L>
-constexpr int log_classes_per_lane() {
-  static_assert(L == 16 || L == 4, "lane counts the summation tree is built for");
-  return L == 16 ? 0 : 2;
-}
 
 struct MsedOut {
   int mode;          // 0 loss, 1 predict, 2 forecast blocks, 3 loss array
@@ -663,13 +615,6 @@ hipError_t launch_lanes(int kind, const LaunchArgs& a, int TC, const MsedOut* ro
   return hipErrorInvalidValue;
 }
 
-// columns per chunk: the prefetch registers hold ≤ kMsedPre·256 yields (0: N is out of range)
-int chunk_columns(int N) {
-  if (N < 1) return 0;
-  const int TC = (kMsedPre * kMsedBlock) / N;
-  return TC > 32 ? 32 : TC;
-}
-
 hipError_t launch_any(int kind, const LaunchArgs& a, int lanes, const MsedOut* ro) {
   const int TC = chunk_columns(a.N);
   if (TC < 1) return hipErrorInvalidValue;
@@ -682,9 +627,13 @@ hipError_t launch_any(int kind, const LaunchArgs& a, int lanes, const MsedOut* r
 
 }  // namespace
 
-bool msed_kind(int kind) { return msed::kind_known(kind); }
+// the neural kinds (yfm_msedn.hip) run the same filter through the same entry points
+bool msed_kind(int kind) { return msed::kind_known(kind) || msedn_kind(kind); }
 
-int msed_param_count(int kind) { return msed::kind_known(kind) ? msed::kind_params(kind) : -1; }
+int msed_param_count(int kind) {
+  if (msedn_kind(kind)) return msedn_param_count(kind);
+  return msed::kind_known(kind) ? msed::kind_params(kind) : -1;
+}
 
 int msed_max_n() { return kMsedPre * kMsedBlock - 1; }
 
@@ -700,7 +649,10 @@ int msed_lanes_for(int B) {
   return B <= 8192 ? 16 : 4;
 }
 
-hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes) { return launch_any(kind, a, lanes, nullptr); }
+hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes) {
+  if (msedn_kind(kind)) return launch_msedn(kind, a, lanes, nullptr);
+  return launch_any(kind, a, lanes, nullptr);
+}
 
 hipError_t launch_msed_grad(int kind, const LaunchArgs& a, int lanes, double* grad) {
   const int TC = chunk_columns(a.N);
@@ -713,6 +665,7 @@ hipError_t launch_msed_grad(int kind, const LaunchArgs& a, int lanes, double* gr
 }
 
 hipError_t launch_msed_record(int kind, const LaunchArgs& a, int lanes, const MsedRecord& r) {
+  if (msedn_kind(kind)) return launch_msedn(kind, a, lanes, &r);
   MsedOut ro;
   ro.mode = r.mode;
   ro.horizon = r.horizon;

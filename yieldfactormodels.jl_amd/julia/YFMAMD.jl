@@ -7,6 +7,10 @@ const YFM_MODEL_DNS, YFM_MODEL_TVL, YFM_MODEL_GNS5 = Cint(0), Cint(1), Cint(2)
 # the static and score-driven λ models of src/models/filter.jl:52-110 (7 is not a kind)
 const YFM_MODEL_NS, YFM_MODEL_SD_NS, YFM_MODEL_RWSD_NS, YFM_MODEL_SSD_NS, YFM_MODEL_SRWSD_NS =
     Cint(3), Cint(4), Cint(5), Cint(6), Cint(8)
+# the neural Nelson–Siegel models (ABI 5): static, and score-driven = YFM_MODEL_SD_NNS | dynamics | flags with
+# dynamics 0 "scalar", 1 "block_diag", 2 "diag"
+const YFM_MODEL_NNS, YFM_MODEL_NNS_ANCHORED, YFM_MODEL_SD_NNS = Cint(16), Cint(17), Cint(32)
+const YFM_NNS_RW, YFM_NNS_SCALED, YFM_NNS_ANCHORED = Cint(4), Cint(8), Cint(16)
 const UNCONSTRAINED, CONSTRAINED = Cint(0), Cint(1)
 const PREC_CERTIFIED, PREC_FP64 = Cint(0), Cint(1)     # TVλ arithmetic (yfm_set_precision)
 
@@ -67,6 +71,12 @@ kind(::YieldFactorModels.AbstractStaticλModel) = YFM_MODEL_NS
 kind(m::YieldFactorModels.AbstractλMSEDrivenModel) =
     isempty(m.base.B) ? (m.base.scale_grad ? YFM_MODEL_SRWSD_NS : YFM_MODEL_RWSD_NS) :
                         (m.base.scale_grad ? YFM_MODEL_SSD_NS : YFM_MODEL_SD_NS)
+kind(m::YieldFactorModels.AbstractStaticNeuralModel) = m.transform_bool ? YFM_MODEL_NNS : YFM_MODEL_NNS_ANCHORED
+# MSEDNeuralModel: the duplicator's largest entry tells the dynamics (2 scalar, 6 block_diag, 18 diag; mseneural.jl:33-48)
+kind(m::YieldFactorModels.AbstractNeuralMSEDrivenModel) =
+    YFM_MODEL_SD_NNS | Cint(maximum(m.base.duplicator) == 2 ? 0 : maximum(m.base.duplicator) == 6 ? 1 : 2) |
+    (isempty(m.base.B) ? YFM_NNS_RW : Cint(0)) | (m.base.scale_grad ? YFM_NNS_SCALED : Cint(0)) |
+    (m.transform_bool ? Cint(0) : YFM_NNS_ANCHORED)
 tuse_ptr(T_use) = T_use === nothing ? C_NULL : pointer(T_use)
 
 "Batched loglik: Θ is P×B (one candidate per column).  space: UNCONSTRAINED (compute_loss input) or CONSTRAINED (set_params! input)."

@@ -12,6 +12,8 @@ from .models import (DNSModel, EstimationError, GNS5Model, SingularException, TV
                      get_params, predict, set_params_, transform_params, untransform_params)
 from .models import (MSEDLambdaModel, StaticLambdaModel, compute_loss_grad_block, estimate_steps_batch,
                      get_param_groups, try_initializations, try_initializations_batch)
+from .models import MSEDNeuralModel, StaticNeuralModel, create_neural_model
+from .params import KIND_NNS, KIND_NNS_ANCHORED, NEURAL_KINDS, is_neural_kind, neural_kind
 from .engine import Engine, get_engine
 from .driver import load_initial_parameters_, run
 from . import lbfgs
@@ -24,5 +26,6 @@ __all__ = [
     "get_engine", "run", "load_initial_parameters_", "compute_loss_grad_batch", "estimate_", "estimate_lbfgs_batch",
     "EstimationError", "lbfgs", "KIND_NS", "KIND_SD_NS", "KIND_RWSD_NS", "KIND_SSD_NS", "KIND_SRWSD_NS", "LAMBDA_KINDS",
     "StaticLambdaModel", "MSEDLambdaModel", "get_param_groups", "try_initializations", "try_initializations_batch",
-    "compute_loss_grad_block", "estimate_steps_batch",
+    "compute_loss_grad_block", "estimate_steps_batch", "StaticNeuralModel", "MSEDNeuralModel", "create_neural_model", "KIND_NNS",
+    "KIND_NNS_ANCHORED", "NEURAL_KINDS", "is_neural_kind", "neural_kind",
 ]

@@ -61,7 +61,7 @@ SIGNATURES = {
                                                          ctypes.c_int, _V, _V, _V, _V]),
 }
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 # precision modes (include/yfm.h: enum yfm_precision)
 PREC_CERTIFIED, PREC_FP64 = 0, 1

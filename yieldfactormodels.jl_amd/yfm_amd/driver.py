@@ -25,6 +25,7 @@ import os
 import numpy as np
 
 from . import io as _io
+from . import params as _p
 from .forecasting import run_rolling_forecasts
 from .models import (AbstractKalmanModel, DNSModel, TVLambdaDNSModel, create_model, estimate_steps_, get_loss,
                      get_loss_array, get_params, predict, set_params_)
@@ -123,6 +124,9 @@ def run_estimation_(model: AbstractKalmanModel, data, in_sample_end: int, all_pa
     """YieldFactorModels.jl:162-186 (Kalman models: grouped estimation, estimate_steps! on
     data[:, 1:in_sample_end]).  Like the reference's last compute_loss call, the model is left holding
     the estimated parameters."""
+    if _p.is_neural_kind(model.kind):
+        raise NotImplementedError("run_estimation! is not built for the neural kinds: their estimation groups and the "
+                                  "δ/Φ gradient are what remains (DESIGN.md §7)")
     if not param_groups:
         raise NotImplementedError("estimate! (LBFGS, ungrouped) is not used by the Kalman models")
     if any(g != "1" for g in param_groups):

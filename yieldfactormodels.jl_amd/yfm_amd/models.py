@@ -35,6 +35,12 @@ forecast blocks forecasting.jl:236-250      :func:`forecast_batch`
 ``get_param_groups`` msebasemodel.jl:153-162  :func:`get_param_groups`
 ``try_initializations``                     :func:`try_initializations` (+ batched
 optimization.jl:73-114                      :func:`try_initializations_batch`): the (A, B) grid in one launch
+``create_model`` model_dictionary.jl:20-112  :func:`create_neural_model` (the 26 neural codes; `create_model`
+                                            keeps refusing them)
+``StaticNeuralModel`` staticneural.jl:3-60   :class:`StaticNeuralModel` ("NNS" / "3", "NNS-Anchored" / "20")
+``MSEDNeuralModel`` mseneural.jl:3-102       :class:`MSEDNeuralModel` ("1SD-NNS" / "8" … "3SRWSD-NNS-Anchored" /
+                                            "32"): loss, predict, get_loss_array, forecast blocks and the two-half
+                                            (A₁, A₂, B₁, B₂) grid of try_initializations; estimation is not built
 =======================================  =================================================
 
 plus the batched forms the device boundary exists for: :func:`get_loss_batch` and
@@ -162,6 +168,88 @@ class MSEDLambdaModel(AbstractKalmanModel):
         self.device = device
 
 
+_NEURAL_GAP = ("not built for the neural kinds (NNS, …SD-NNS): their estimation groups, the δ/Φ gradient and the rolling "
+               "driver are what remains (DESIGN.md §7); the loss, predict, get_loss_array, forecast blocks and "
+               "try_initializations are built")
+
+
+_NEURAL_RESTARTS = ("try_initializations of the static neural models draws its restarts from Julia's seeded generator "
+                    "(Random.seed!(trial); randn, static/paramteroperations.jl:99-113), which is not restated here")
+
+
+class StaticNeuralModel(AbstractKalmanModel):
+    """staticneural.jl:3-60: static neural Nelson–Siegel, θ_c = [γ(18), δ, vec Φ], P = 30; ``transform_bool = False``
+    is NNS-Anchored."""
+
+    def __init__(self, maturities, N: int, M: int = 3, model_string: str = "NNS", results_location: str = "results/",
+                 transform_bool: bool = True, device: int = 0):
+        if M != 3:
+            raise ValueError("StaticNeuralModel is a 3-factor model (M = 3)")
+        self.transform_bool = bool(transform_bool)
+        kind = _p.KIND_NNS if transform_bool else _p.KIND_NNS_ANCHORED
+        self.base = KalmanBaseModel(np.asarray(maturities, dtype=np.float64), N, 3, _p.NEURAL_GAMMA, kind, model_string,
+                                    results_location)
+        self.device = device
+
+
+class MSEDNeuralModel(AbstractKalmanModel):
+    """mseneural.jl:3-102: score-driven neural Nelson–Siegel, θ_c = [A_unique, B_unique, ω(18), δ, vec Φ] (no B when
+    ``random_walk``); ``dynamics`` ("scalar", "block_diag", "diag") is the duplicator that expands 2, 6 or 18 unique
+    values of A and of B over the 18 components of γ.  ``scale_grad`` divides every component of the score by the
+    bias-corrected root of its own EWMA, forget factor 0.9."""
+
+    A_guesses = (1e-6, 1e-5, 1e-4, 1e-3)      # mseneural.jl:59
+    B_guesses = (0.97, 0.98, 0.99, 0.999)     # mseneural.jl:60
+    forget_factor = 0.9
+
+    def __init__(self, maturities, N: int, M: int = 3, dynamics: str = "scalar", random_walk: bool = False,
+                 model_string: str = "MSEDNeural", results_location: str = "results/", scale_grad: bool = False,
+                 transform_bool: bool = True, device: int = 0):
+        if M != 3:
+            raise ValueError("MSEDNeuralModel is a 3-factor model (M = 3)")
+        kind = _p.neural_kind(dynamics, random_walk, scale_grad, transform_bool)
+        self.dynamics = _p.NEURAL_DYNAMICS[kind & 3]
+        self.random_walk = bool(random_walk)
+        self.scale_grad = bool(scale_grad)
+        self.transform_bool = bool(transform_bool)
+        self.duplicator = _p.neural_duplicator(kind) + 1  # 1-based, as the reference's
+        self.base = KalmanBaseModel(np.asarray(maturities, dtype=np.float64), N, 3, _p.NEURAL_GAMMA, kind, model_string,
+                                    results_location)
+        self.device = device
+
+
+def _nns(transform_bool):
+    def make(mats, N, M, model_string, results_location, device):
+        return StaticNeuralModel(mats, N, M, model_string=model_string, results_location=results_location,
+                                 transform_bool=transform_bool, device=device)
+    return make
+
+
+def _msedn(dynamics, random_walk, scale_grad, transform_bool):
+    def make(mats, N, M, model_string, results_location, device):
+        return MSEDNeuralModel(mats, N, M, dynamics, random_walk, model_string=model_string,
+                               results_location=results_location, scale_grad=scale_grad,
+                               transform_bool=transform_bool, device=device)
+    return make
+
+
+def _neural_codes() -> dict:
+    """model_dictionary.jl:20-112: "NNS" / "3", "1SD-NNS" / "8" … "3SRWSD-NNS" / "19", "NNS-Anchored" / "20",
+    "1SD-NNS-Anchored" / "21" … "3SRWSD-NNS-Anchored" / "32"."""
+    codes = {}
+    for anchored, code in ((False, 3), (True, 20)):
+        name = _p.neural_name(_p.KIND_NNS_ANCHORED if anchored else _p.KIND_NNS)
+        codes[name] = codes[str(code)] = (name, _nns(not anchored))
+        code = 8 if not anchored else 21
+        for scaled in (False, True):
+            for dyn in (0, 1, 2):
+                for rw in (False, True):
+                    name = _p.neural_name(_p.neural_kind(dyn, rw, scaled, not anchored))
+                    codes[name] = codes[str(code)] = (name, _msedn(_p.NEURAL_DYNAMICS[dyn], rw, scaled, not anchored))
+                    code += 1
+    return codes
+
+
 def _msed(random_walk, scale_grad):
     def make(mats, N, M, model_string, results_location, device):
         return MSEDLambdaModel(mats, N, M, random_walk, model_string=model_string, results_location=results_location,
@@ -180,17 +268,34 @@ _CODES = {
     "SSD-NS": ("SSD-NS", _msed(False, True)), "6": ("SSD-NS", _msed(False, True)),
     "SRWSD-NS": ("SRWSD-NS", _msed(True, True)), "7": ("SRWSD-NS", _msed(True, True)),
 }
+# model_dictionary.jl:20-112 (codes "3" and "8" … "32"): the neural models, a table of their own —
+# :func:`create_neural_model`.  `create_model` keeps refusing these codes: the drivers built on it (estimation, the
+# rolling forecasts) are not built for them, and a caller that reaches a neural model says so by the call it makes.
+_NEURAL_CODES = _neural_codes()
 
 
 def create_model(model_type: str, maturities, N: int, M: int = 3, float_type=np.float64,
                  results_location: str = "results/", device: int = 0):
     """model_dictionary.jl:7-35 for the Kalman codes and the static / score-driven λ codes; returns
     (model, standardized model_type)."""
+    return _create(_CODES, model_type, maturities, N, M, float_type, results_location, device,
+                   " — the neural codes are create_neural_model's" if model_type in _NEURAL_CODES else "")
+
+
+def create_neural_model(model_type: str, maturities, N: int, M: int = 3, float_type=np.float64,
+                        results_location: str = "results/", device: int = 0):
+    """model_dictionary.jl:20-112 for the neural codes — "NNS" / "3", "1SD-NNS" / "8" … "3SRWSD-NNS" / "19",
+    "NNS-Anchored" / "20", "1SD-NNS-Anchored" / "21" … "3SRWSD-NNS-Anchored" / "32" — with create_model's arguments
+    and result: (model, standardized model_type)."""
+    return _create(_NEURAL_CODES, model_type, maturities, N, M, float_type, results_location, device)
+
+
+def _create(codes, model_type, maturities, N, M, float_type, results_location, device, hint=""):
     if np.dtype(float_type) != np.float64:
         raise ValueError("the MI355X path computes in Float64 only (the reference's Float64 path, test.jl:25)")
-    if model_type not in _CODES:
-        raise ValueError(f"Invalid model type: {model_type} (codes: {sorted(_CODES)})")
-    std, cls = _CODES[model_type]
+    if model_type not in codes:
+        raise ValueError(f"Invalid model type: {model_type} (codes: {sorted(codes)}){hint}")
+    std, cls = codes[model_type]
     mats = np.asarray(maturities, dtype=np.float64)
     if len(mats) != N:
         raise ValueError("len(maturities) != N")
@@ -220,7 +325,7 @@ def untransform_params(model: AbstractKalmanModel, params) -> np.ndarray:
 def get_param_groups(model: AbstractKalmanModel, param_groups=()) -> list:
     """msebasemodel.jl:153-162 / staticbasemodel.jl:103-112: the caller's groups when there is one per parameter,
     else the defaults — "1" for the leading parameters, "2" for the M(M + 1) entries of δ and Φ."""
-    if not _p.is_lambda_kind(model.kind):
+    if not (_p.is_lambda_kind(model.kind) or _p.is_neural_kind(model.kind)):
         raise NotImplementedError("Kalman models estimate every parameter in group \"1\"")
     P, M = _p.n_params(model.kind), model.base.M
     groups = list(param_groups)
@@ -233,10 +338,37 @@ def _trial_grid(model) -> np.ndarray:
     """get_new_initial_params (msedriven/paramteroperations.jl:132-187, the n_unique == 1 branch): the (A, B)
     of trial 1, 2, … — B cycles fastest; the random-walk variants have the A trials only.  2×n_trials (row 2 NaN
     without B)."""
+    if isinstance(model, MSEDNeuralModel):
+        return _neural_trial_grid(model)
     A, Bg = MSEDLambdaModel.A_guesses, MSEDLambdaModel.B_guesses
     if _p.lambda_has_b(model.kind):
         return np.array([[a, b] for a in A for b in Bg]).T
     return np.array([[a, np.nan] for a in A]).T
+
+
+def _neural_trial_grid(model) -> np.ndarray:
+    """get_new_initial_params, the multi-unique branch (msedriven/paramteroperations.jl:161-184): trial k writes
+    A₁ to the first half of the unique A values, A₂ to the second, and B₁, B₂ likewise; B₂ cycles fastest, then B₁,
+    A₂, A₁ (random walk: A₂, then A₁).  n_lead×n_trials: the leading rows of θ_c for trial 1, 2, … (256, or 16)."""
+    A, Bg = MSEDNeuralModel.A_guesses, MSEDNeuralModel.B_guesses
+    nu = _p.neural_unique(model.kind)
+    half = nu // 2
+    has_b = _p.neural_has_b(model.kind)
+    nA, nB = len(A), (len(Bg) if has_b else 0)
+    total = nA ** 2 * nB ** 2 if has_b else nA ** 2
+    grid = np.empty((nu * (2 if has_b else 1), total))
+    for k in range(total):
+        if has_b:
+            a1, rem = divmod(k, nA * nB ** 2)
+            a2, rem = divmod(rem, nB ** 2)
+            b1, b2 = divmod(rem, nB)
+            grid[nu:nu + half, k] = Bg[b1]
+            grid[nu + half:, k] = Bg[b2]
+        else:
+            a1, a2 = divmod(k, nA)
+        grid[:half, k] = A[a1]
+        grid[half:nu, k] = A[a2]
+    return grid
 
 
 def try_initializations_batch(best_params, model: AbstractKalmanModel, data, T_use=None):
@@ -244,7 +376,9 @@ def try_initializations_batch(best_params, model: AbstractKalmanModel, data, T_u
     ``data[:, :T_use[w]]``.  The start and its 30 (A, B) trials (6 for the random-walk variants) of every window go
     through ONE launch; the winner is the reference's: a trial replaces the running best only on a strict
     improvement, in trial order.  Returns (P×W winners, W losses, the loss being −get_loss)."""
-    if not isinstance(model, MSEDLambdaModel):
+    if isinstance(model, StaticNeuralModel):
+        raise NotImplementedError(_NEURAL_RESTARTS)
+    if not isinstance(model, (MSEDLambdaModel, MSEDNeuralModel)):
         raise TypeError("try_initializations walks the (A, B) grid of a score-driven model")
     best = np.asarray(best_params, dtype=np.float64)
     best = best.reshape(best.shape[0], -1)
@@ -252,9 +386,13 @@ def try_initializations_batch(best_params, model: AbstractKalmanModel, data, T_u
     grid = _trial_grid(model)
     n = grid.shape[1]
     cand = np.repeat(best[:, :, None], n + 1, axis=2)  # P × W × (1 + n): the start, then the trials
-    cand[0, :, 1:] = grid[0]
-    if _p.lambda_has_b(model.kind):
-        cand[1, :, 1:] = grid[1]
+    if isinstance(model, MSEDNeuralModel):
+        # the two-half (A₁, A₂, B₁, B₂) grid: 256 trials, 16 for the random-walk kinds
+        cand[:grid.shape[0], :, 1:] = grid[:, None, :]
+    else:
+        cand[0, :, 1:] = grid[0]
+        if _p.lambda_has_b(model.kind):
+            cand[1, :, 1:] = grid[1]
     tu = None if T_use is None else np.repeat(np.broadcast_to(T_use, (W,)), n + 1)
     loss = -get_loss_batch(model, data, cand.reshape(P, W * (n + 1)), space=_p.SPACE_CONSTRAINED, T_use=tu)
     loss = loss.reshape(W, n + 1)
@@ -274,11 +412,17 @@ def try_initializations(best_params, model: AbstractKalmanModel, data):
     """optimization.jl:73-114: the P×1 winner among the start and the (A, B) trials.  Other models return the
     start unchanged (optimization.jl:33-35)."""
     best = np.asarray(best_params, dtype=np.float64).reshape(-1)
-    if not isinstance(model, MSEDLambdaModel):
+    if isinstance(model, StaticNeuralModel):
+        raise NotImplementedError(_NEURAL_RESTARTS)
+    if not isinstance(model, (MSEDLambdaModel, MSEDNeuralModel)):
         return best.reshape(-1, 1).copy()
     out, _ = try_initializations_batch(best[:, None], model, data)
     set_params_(model, out[:, 0])  # the reference leaves the model at the last trial; the winner is the useful state
     return out
+
+
+def _is_kalman(kind: int) -> bool:
+    return not (_p.is_lambda_kind(kind) or _p.is_neural_kind(kind))
 
 
 def _engine(model, data):
@@ -291,7 +435,7 @@ def get_loss(model: AbstractKalmanModel, data) -> float:
     """filter.jl:182-209 for the model's current (constrained) parameters."""
     eng = _engine(model, data)
     ll = float(eng.loglik(model.kind, model.base.flat_params, space=_p.SPACE_CONSTRAINED)[0])
-    if np.isnan(ll) and not _p.is_lambda_kind(model.kind):
+    if np.isnan(ll) and _is_kalman(model.kind):
         raise SingularException("initialize_filter: singular I - Φ or I - Φ⊗Φ")
     return ll
 
@@ -336,7 +480,7 @@ def predict(model: AbstractKalmanModel, data, horizon: int = 1, Theta=None, spac
     out = eng.predict(model.kind, Theta, space=space, T_use=T_use, horizon=horizon)
     if single:
         out = {k: v[:, :, 0] for k, v in out.items()}
-        if np.isnan(out["factors"]).all() and not _p.is_lambda_kind(model.kind):
+        if np.isnan(out["factors"]).all() and _is_kalman(model.kind):
             raise SingularException("initialize_filter: singular I - Φ or I - Φ⊗Φ")
     return out
 
@@ -349,7 +493,7 @@ def get_loss_array(model: AbstractKalmanModel, data, K: int = 1, Theta=None, spa
     out = eng.loss_array(model.kind, model.base.flat_params if single else Theta, space=space, T_use=T_use, K=K)
     if single:
         row = out[:, 0]
-        if np.isnan(row).all() and row.size and not _p.is_lambda_kind(model.kind):
+        if np.isnan(row).all() and row.size and _is_kalman(model.kind):
             raise SingularException("initialize_filter: singular I - Φ or I - Φ⊗Φ")
         if row.size and np.isneginf(row).all():
             return -np.inf
@@ -374,6 +518,8 @@ def estimate_steps_(model: AbstractKalmanModel, data, all_params, param_groups=N
     Kalman models: parameter groups other than all-"1" are not supported (their default, kalmanbasemodel.jl:150-159).
     λ models: :func:`estimate_steps_batch` with one chain.
     `iterations`: the NelderMead budget per group (opt1, optimization.jl:442-451: 500)."""
+    if _p.is_neural_kind(model.kind):
+        raise NotImplementedError("estimate_steps_ is " + _NEURAL_GAP)
     A = np.asarray(all_params, dtype=np.float64)
     start = A[:, 0] if A.ndim == 2 else A
     if _p.is_lambda_kind(model.kind):
@@ -397,6 +543,8 @@ def estimate_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, space: 
                    g_tol: float = 1e-6, max_group_iters: int = 10, tol: float = 1e-8) -> dict:
     """R independent estimate_steps! chains (windows × starts) whose objective evaluations share one device
     launch per round (libyfm_hip.so: yfm_estimate).  Θ₀: P×R starts (constrained by default, as all_params)."""
+    if _p.is_neural_kind(model.kind):
+        raise NotImplementedError("estimate_batch is " + _NEURAL_GAP)
     eng = _engine(model, data)
     return eng.estimate(model.kind, Theta0, space=space, T_use=T_use, iterations=iterations, g_tol=g_tol,
                         max_group_iters=max_group_iters, tol=tol)
@@ -419,6 +567,8 @@ def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, p
     `iterations` caps both optimisers' budgets (None: the reference's 500 and 250).  Returns what
     :func:`estimate_batch` returns — theta_c, p, init_c (the reference's init_p), ll, status, n_evals — plus
     evals_by_group, rounds_by_group and group_iters."""
+    if _p.is_neural_kind(model.kind):
+        raise NotImplementedError("estimate_steps_batch is " + _NEURAL_GAP)
     if not _p.is_lambda_kind(model.kind):
         raise NotImplementedError("estimate_steps_batch is the λ models' driver; Kalman models use estimate_batch")
     kind = model.kind
@@ -472,6 +622,8 @@ def compute_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_use=None)
     in estimate_steps! for the δ/Φ block (optimization.jl:442-479): (−loss[B], −∂loss/∂θ[12, B]) for every
     unconstrained θ_b, the rows being θ's last 12 (δ, then vec Φ column-major).  NaN gradient columns where the
     loss is −Inf."""
+    if _p.is_neural_kind(model.kind):
+        raise NotImplementedError("compute_loss_grad_block is " + _NEURAL_GAP)
     if not _p.is_lambda_kind(model.kind):
         raise NotImplementedError("the δ/Φ block gradient is the λ models'; Kalman models use compute_loss_grad_batch")
     loss, g = _engine(model, data).lambda_loss_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
@@ -485,6 +637,8 @@ def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 
     p (P×R unconstrained optimum), init_c (P×R: the start, constrained), ll (R), ll0 (R: the loglik at the
     start), status (R: lbfgs status; 0 = converged), iterations (R), n_evals, rounds."""
     from . import lbfgs as _lbfgs
+    if _p.is_neural_kind(model.kind):
+        raise NotImplementedError("estimate_ (the L-BFGS multistart) is " + _NEURAL_GAP)
     Th = np.asarray(Theta0, dtype=np.float64)
     if Th.ndim == 1:
         Th = Th[:, None]

@@ -15,11 +15,13 @@ import math
 
 import numpy as np
 
-from .params import (KIND_DNS, KIND_GNS, KIND_NS, KIND_TVL, is_lambda_kind, lambda_has_b, lambda_layout, n_params,
-                     param_layout, untransform_params)
+from .params import (KIND_DNS, KIND_GNS, KIND_NS, KIND_TVL, NEURAL_GAMMA, is_lambda_kind, is_neural_kind, lambda_has_b,
+                     lambda_layout, n_params, neural_has_b, neural_layout, neural_unique, param_layout,
+                     untransform_params)
 
 PANEL_SEED = 20260227
 BATCH_SEED = 20260228
+NEURAL_SEED = 20260301  # the network weights of the neural kinds' θ₀
 
 
 def maturities_30() -> np.ndarray:
@@ -35,6 +37,16 @@ def maturities_360() -> np.ndarray:
 
 def theta0_constrained(kind: int = KIND_DNS) -> np.ndarray:
     """θ₀ in the constrained space (as ``set_params!`` consumes it)."""
+    if is_neural_kind(kind):
+        # [A_unique, B_unique, ω(18), δ, vec Φ] (msedriven/paramteroperations.jl:25-65) with the DNS δ and Φ; the
+        # weights of the two networks are 0.1·N(0, 1) from a generator of their own, the biases 0
+        tail = theta0_constrained(KIND_NS)[1:]
+        w = 0.1 * np.random.Generator(np.random.PCG64(NEURAL_SEED)).standard_normal(NEURAL_GAMMA)
+        w[3:6] = 0.0
+        w[12:15] = 0.0
+        nu = neural_unique(kind)
+        lead = [3e-4] * nu + ([0.98] * nu if neural_has_b(kind) else [])
+        return np.asarray(lead + list(w) + list(tail), dtype=np.float64)
     if is_lambda_kind(kind):
         # [A, B, ω, δ, vec Φ] (msedriven/paramteroperations.jl:25-65) with the DNS δ and Φ; Φ column-major
         dns = theta0_constrained(KIND_DNS)
@@ -119,8 +131,8 @@ def _loadings(gammas, maturities, M):
 
 def simulate_panel(kind: int = KIND_DNS, T: int = 600, maturities=None, seed: int = PANEL_SEED) -> np.ndarray:
     """Simulate y_t = Z β_t + ε_t, β_{t+1} = δ + Φ β_t + η_t at θ₀ (yields in percent). Returns N×T (F-order)."""
-    if is_lambda_kind(kind):
-        kind = KIND_DNS  # the λ models are fitted to the same data: the DNS panel at the DNS θ₀
+    if is_lambda_kind(kind) or is_neural_kind(kind):
+        kind = KIND_DNS  # the λ and neural models are fitted to the same data: the DNS panel at the DNS θ₀
     if maturities is None:
         maturities = maturities_360() if kind == KIND_TVL else maturities_30()
     maturities = np.asarray(maturities, dtype=np.float64)
@@ -146,17 +158,32 @@ def simulate_panel(kind: int = KIND_DNS, T: int = 600, maturities=None, seed: in
 
 
 def theta_batch(kind: int = KIND_DNS, B: int = 65536, scale: float = 0.1, seed: int = BATCH_SEED,
-                bad_frac: float = 0.01) -> np.ndarray:
+                bad_frac: float = 0.01, a_range=(1e-4, 1e-3)) -> np.ndarray:
     """Θ (P×B, F-order): θ_b = θ₀ + scale·N(0,I) in unconstrained space; `bad_frac` of columns get a
     non-stationary Φ to exercise the indefinite-P / -Inf paths: alternately Φ₁₂ = Φ₂₁ = 0.8 (real
-    eigenvalue ≈ 1.8) and Φ₁₂ = 3, Φ₂₁ = -3 (complex pair of modulus ≈ 3)."""
+    eigenvalue ≈ 1.8) and Φ₁₂ = 3, Φ₂₁ = -3 (complex pair of modulus ≈ 3).
+
+    The neural kinds draw, after everything else, their step sizes A log-uniformly over `a_range` (B stays around
+    0.98) and networks of their own per candidate: weights 0.1·N(0, 1), biases 0.  The step is A∘score and the score
+    grows with N, so the filter's sensitivity to rounding grows with both: over 1e-4 … 1e-3 the Float64 restatement
+    of some candidates is itself 1e-7 from the 40-digit value at N = 90, over 1e-5 … 1e-4 no more than 1e-12
+    (tests/golden/msedn/make_msedn.py)."""
     P = n_params(kind)
     rng = np.random.Generator(np.random.PCG64(seed))
     th0 = theta0(kind)
     Theta = np.asfortranarray(th0[:, None] + scale * rng.standard_normal((P, B)))
+    if is_neural_kind(kind):
+        lay = neural_layout(kind)
+        nu = lay.n_unique
+        Theta[:nu] = np.log(a_range[0]) + np.log(a_range[1] / a_range[0]) * rng.random((nu, B))
+        w = 0.1 * rng.standard_normal((NEURAL_GAMMA, B))
+        w[3:6] = 0.0
+        w[12:15] = 0.0
+        Theta[lay.gamma_offset:lay.gamma_offset + NEURAL_GAMMA] = w
     nbad = int(round(bad_frac * B))
     if nbad:
-        lay = lambda_layout(kind) if is_lambda_kind(kind) else param_layout(kind)
+        lay = (lambda_layout(kind) if is_lambda_kind(kind) else neural_layout(kind) if is_neural_kind(kind)
+               else param_layout(kind))
         idx = rng.choice(B, size=nbad, replace=False)
         a = np.where(np.arange(nbad) % 2 == 0, 0.8, 3.0)
         Theta[lay.phi_offset + 1, idx] = a  # Φ[1,2] (row-major)

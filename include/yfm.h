@@ -69,7 +69,8 @@ enum yfm_model_kind {
    * (diag) unique values: P = 34 / 42 / 66, random walk 32 / 36 / 48.  Unconstrained space: A → exp,
    * B → 1/(1 + e^−x), the diagonal of Φ → from_R_to_11.  The scaled kinds' EWMA is per component with f = 0.9.
    * 4 ≤ N ≤ 1024 (below 4 the transforms' anchor slots alias): other N return YFM_EUNSUPPORTED, as do
-   * yfm_estimate, yfm_filter_states, yfm_loglik_grad_batch and yfm_lambda_loss_grad_batch for these kinds.
+   * yfm_estimate, yfm_filter_states, yfm_loglik_grad_batch and yfm_lambda_loss_grad_batch for these kinds (their
+   * δ/Φ loss gradient is yfm_neural_loss_grad_batch).
    * yfm_predict's states are 18×n per candidate and a yfm_forecast block has 3 + 18 + N rows. */
   YFM_MODEL_NNS = 16,          /* "NNS" / "3": StaticNeuralModel */
   YFM_MODEL_NNS_ANCHORED = 17, /* "NNS-Anchored" / "20" */
@@ -309,6 +310,19 @@ int yfm_lambda_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, co
 /* Same (optimization.jl:442-479, filter.jl:209-243) with DEVICE pointers on the caller's HIP stream;
  * asynchronous, with the ordering rules of yfm_loglik_batch_device. */
 int yfm_lambda_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                      int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                                      void* hip_stream);
+
+/* The same for the neural kinds (YFM_MODEL_NNS, NNS_ANCHORED and the 24 score-driven NNS kinds): their parameter
+ * group "2" is the same last 12 rows of θ, and δ and Φ enter their filter through the prediction only as well, so
+ * the signatures, the layout of grad_out, the spaces, the NaN gradient of a −Inf loss and the batch independence
+ * are those of yfm_lambda_loss_grad_batch(_device); loss_out[b] is bitwise what yfm_loglik_batch returns for the
+ * kind.  Every other kind returns YFM_EUNSUPPORTED, and so does a panel with fewer than 4 maturities or more than
+ * the gradient kernel's maximum (1024, the loss kernel's).  Additive: YFM_ABI_VERSION stays 5, a library that has
+ * these two symbols differs from one that has not in nothing else. */
+int yfm_neural_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                               const int* T_use, double* loss_out, double* grad_out);
+int yfm_neural_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
                                       int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                       void* hip_stream);
 

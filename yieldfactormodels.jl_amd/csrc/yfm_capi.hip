@@ -287,7 +287,7 @@ struct Launch {
   bool continues = false;  // a later chunk of a pipelined batch: accumulates into the previous chunk's counters
   int share = 1;           // launches of this size the caller keeps in flight at once (yfm::loglik_device_ws)
   const yfm::MsedRecord* msed_rec = nullptr;  // λ models: the trajectory outputs this launch writes (nullptr: the loss)
-  double* msed_grad = nullptr;  // λ models: 12×B device, ∂loss/∂(δ, Φ) written with the loss (yfm_lambda_loss_grad_batch)
+  double* msed_grad = nullptr;  // λ and neural models: 12×B device, ∂loss/∂(δ, Φ) written with the loss
 };
 
 // The plain log-likelihood launch, in the argument order of yfm_loglik_batch_device.
@@ -448,12 +448,24 @@ int check_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
 // The λ gradient entry points' model check: the five kinds of yfm_msed.hip only.
 int check_lambda_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
   if (yfm::msedn_kind(kind))
-    return set_error(YFM_EUNSUPPORTED, "the delta/Phi loss gradient is not built for the neural kinds (model_kind %d)",
-                     kind);
+    return set_error(YFM_EUNSUPPORTED, "yfm_lambda_loss_grad_batch serves the λ kinds: the neural kinds' delta/Phi loss "
+                     "gradient is yfm_neural_loss_grad_batch (model_kind %d)", kind);
   if (state_dim(kind) >= 0 && !yfm::msed_kind(kind))
     return set_error(YFM_EUNSUPPORTED, "the δ/Φ loss gradient is built for the λ kinds only (model_kind %d: use "
                      "yfm_loglik_grad_batch)", kind);
   return check_batch(ctx, kind, space, P, B);
+}
+
+// The neural gradient entry points' model check: the 26 kinds of yfm_msedn.hip only.
+int check_neural_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
+  if (state_dim(kind) >= 0 && !yfm::msedn_kind(kind))
+    return set_error(YFM_EUNSUPPORTED, "yfm_neural_loss_grad_batch is built for the neural kinds only (model_kind %d: "
+                     "use yfm_lambda_loss_grad_batch or yfm_loglik_grad_batch)", kind);
+  if (int r = check_batch(ctx, kind, space, P, B)) return r;
+  if (ctx->N > yfm::msedn_grad_max_n())
+    return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the neural gradient kernel's %d", ctx->N,
+                     yfm::msedn_grad_max_n());
+  return YFM_OK;
 }
 
 // The loglik launch q on the context's own workspace, then the tangent kernel on the same stream: it reads the
@@ -552,6 +564,43 @@ int validate_tuse(const int* T_use, int B, int T) {
     if (T_use[b] < 1 || T_use[b] > T)
       return set_error(YFM_EINVAL, "T_use[%d] = %d outside [1, %d]", b, T_use[b], T);
   return YFM_OK;
+}
+
+using GradCheck = int (*)(yfm_ctx*, int, int, int, int);
+
+// yfm_lambda_loss_grad_batch and yfm_neural_loss_grad_batch: one launch path, each with its own model check
+int loss_grad_batch(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                    const int* T_use, double* loss_out, double* grad_out) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !loss_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loss_out or grad_out");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  const size_t gb = sizeof(double) * yfm::kMsedGrad * (size_t)(B > 0 ? B : 1);
+  YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
+  q.msed_grad = static_cast<double*>(ctx->own.grad.p);
+  if (int r = launch(ctx, q)) return r;
+  if (B > 0) {
+    YFM_HIP_CHECK(hipMemcpyAsync(loss_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, q.msed_grad, sizeof(double) * yfm::kMsedGrad * (size_t)B,
+                                 hipMemcpyDeviceToHost, ctx->stream));
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+int loss_grad_batch_device(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta,
+                           int P, int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                           void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_loss_out || !d_grad_out))
+    return set_error(YFM_EINVAL, "null d_theta, d_loss_out or d_grad_out");
+  Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
+                           static_cast<hipStream_t>(hip_stream));
+  q.msed_grad = d_grad_out;
+  return launch(ctx, q);
 }
 
 }  // namespace
@@ -774,36 +823,26 @@ int yfm_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, 
 
 int yfm_lambda_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                                const int* T_use, double* loss_out, double* grad_out) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_lambda_grad(ctx, model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!theta || !loss_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loss_out or grad_out");
-  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
-  Launch q;
-  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  const size_t gb = sizeof(double) * yfm::kMsedGrad * (size_t)(B > 0 ? B : 1);
-  YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
-  q.msed_grad = static_cast<double*>(ctx->own.grad.p);
-  if (int r = launch(ctx, q)) return r;
-  if (B > 0) {
-    YFM_HIP_CHECK(hipMemcpyAsync(loss_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
-    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, q.msed_grad, sizeof(double) * yfm::kMsedGrad * (size_t)B,
-                                 hipMemcpyDeviceToHost, ctx->stream));
-  }
-  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return YFM_OK;
+  return loss_grad_batch(check_lambda_grad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out);
 }
 
 int yfm_lambda_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
                                       int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                       void* hip_stream) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_lambda_grad(ctx, model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!d_theta || !d_loss_out || !d_grad_out))
-    return set_error(YFM_EINVAL, "null d_theta, d_loss_out or d_grad_out");
-  Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
-                           static_cast<hipStream_t>(hip_stream));
-  q.msed_grad = d_grad_out;
-  return launch(ctx, q);
+  return loss_grad_batch_device(check_lambda_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
+                                d_grad_out, hip_stream);
+}
+
+int yfm_neural_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                               const int* T_use, double* loss_out, double* grad_out) {
+  return loss_grad_batch(check_neural_grad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out);
+}
+
+int yfm_neural_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                      int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                                      void* hip_stream) {
+  return loss_grad_batch_device(check_neural_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
+                                d_grad_out, hip_stream);
 }
 
 int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n) {

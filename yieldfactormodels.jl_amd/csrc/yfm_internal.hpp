@@ -156,6 +156,10 @@ int msedn_param_count(int kind);
 int msedn_min_n();
 int msedn_max_n();
 hipError_t launch_msedn(int kind, const LaunchArgs& a, int lanes, const MsedRecord* r);
+// launch_msed_grad for these kinds (it forwards here): the loss is launch_msedn's bit for bit.
+// msedn_min_n ≤ N ≤ msedn_grad_max_n.
+int msedn_grad_max_n();
+hipError_t launch_msedn_grad(int kind, const LaunchArgs& a, int lanes, double* grad);
 // Trajectory outputs (yfm_predict.hip) from a recorded state trajectory.
 struct PredictArgs {
   int kind, M, L, N, P, B, T;

@@ -655,6 +655,7 @@ hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes) {
 }
 
 hipError_t launch_msed_grad(int kind, const LaunchArgs& a, int lanes, double* grad) {
+  if (msedn_kind(kind)) return launch_msedn_grad(kind, a, lanes, grad);
   const int TC = chunk_columns(a.N);
   if (TC < 1) return hipErrorInvalidValue;
   switch (lanes) {

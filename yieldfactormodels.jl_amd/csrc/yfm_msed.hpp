@@ -320,8 +320,9 @@ YFM_MHD void accum_zv(double (&s)[kM], double z2, double z3, double v) {
 }
 
 // One compared prediction: s = Z'v; bpost the β the prediction advanced from (unused where pred_only, the
-// prediction-only first step)
-YFM_MHD void grad_accum(const Model& m, bool pred_only, const double (&s)[kM], const double (&bpost)[kM], Grad& g) {
+// prediction-only first step).  MODEL: anything with Φ and β₀ = δ (this file's Model, msedn::Model)
+template <class MODEL>
+YFM_MHD void grad_accum(const MODEL& m, bool pred_only, const double (&s)[kM], const double (&bpost)[kM], Grad& g) {
   if (pred_only) {
     for (int c = 0; c < kM; ++c) g.d[c] += s[c];
     return;

@@ -331,6 +331,220 @@ __global__ __launch_bounds__(kMsedBlock) void msedn_kernel(const double* __restr
   out[b] = ll;
 }
 
+// The statistics of pass A with Z'v of the comparison (yfm_msed.hpp, ∂loss/∂(δ, Φ)) through the same tree.
+struct GradPassStats {
+  PassStats s;
+  double zv[kM];
+  __device__ __forceinline__ void zero() {
+    s.zero();
+#pragma unroll
+    for (int k = 0; k < kM; ++k) zv[k] = 0.0;
+  }
+  __device__ __forceinline__ void add(const GradPassStats& a, const GradPassStats& b) {
+    s.add(a.s, b.s);
+#pragma unroll
+    for (int k = 0; k < kM; ++k) zv[k] = a.zv[k] + b.zv[k];
+  }
+};
+
+// get_loss and its gradient with respect to δ and Φ in one pass: msedn_kernel's loss mode — the same mapping, LDS
+// record, staging, passes and sums, so the loss is the same bits — whose pass A also forms s = Z'v at the loadings
+// the prediction of step t − 1 used, from which every lane of the group updates the 12 accumulators (replicated like
+// the state; the algebra is msed::grad_accum / grad_finish).  Writes the loss to out[b] and the
+// gradient, in the caller's space, to grad[12·b ..]; NaN where the loss is −Inf.
+template <int L, bool STATIC, bool HASB, bool SCALED>
+__global__ __launch_bounds__(kMsedBlock) void neural_grad_kernel(const double* __restrict__ theta, int P, int B,
+                                                                  int space, int kind, const double* __restrict__ Y,
+                                                                  int T, int N, int TC,
+                                                                  const double* __restrict__ mats,
+                                                                  const int* __restrict__ T_use,
+                                                                  double* __restrict__ out, double* __restrict__ grad,
+                                                                  unsigned int* __restrict__ flags,
+                                                                  unsigned int* __restrict__ flags_next) {
+  constexpr int GPB = kMsedBlock / L;
+  constexpr int KQ = log_classes_per_lane<L>();
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double* s_m = smem;               // N maturities
+  double* s_y = smem + N;           // TC columns of N yields
+  double* s_c = s_y + TC * N;       // GPB records [A(18), B(18), ν(18), EWMA(18)]
+  __shared__ int s_iters_max;
+
+  const int tid = threadIdx.x;
+  if (flags_next && blockIdx.x == 0 && tid < kFlagsPerBank) flags_next[tid] = 0u;  // the next launch's counters
+  const int j = tid % L;
+  const int grp = tid / L;
+  const int b = blockIdx.x * GPB + grp;
+  const bool live = b < B;
+  const int bb = live ? b : (B - 1);
+  const int nobs = T_use ? T_use[bb] : T;
+
+  if (tid == 0) s_iters_max = 0;
+  for (int i = tid; i < N; i += kMsedBlock) s_m[i] = mats[i];
+  __syncthreads();
+  const int my_steps = nobs - 1;
+  const int my_iters = my_steps + 1;  // iteration t: the comparison of step t − 1, then step t
+  atomicMax(&s_iters_max, live ? my_iters : 0);
+
+  double* const cA = s_c + grp * kConsts;
+  double* const cB = cA + kG;
+  double* const cNu = cB + kG;
+  double* const cEw = cNu + kG;
+  const double* th = theta + (size_t)bb * P;
+  Model mdl;
+  State st;
+  {
+    double g0[kG];
+    decode(th, space, kind, mdl, cA, cB, cNu, g0);
+#pragma unroll
+    for (int k = 0; k < kM; ++k) st.beta[k] = mdl.beta0[k];
+#pragma unroll
+    for (int k = 0; k < kG; ++k) {
+      st.gamma[k] = g0[k];
+      cEw[k] = 0.0;
+    }
+    st.fpow = 1.0;
+  }
+  const bool anchored = mdl.anchored;
+  const Ends ends = {s_m[0], s_m[N - 2], s_m[N - 1]};
+  const double fN = (double)N;
+
+  double mse = 0.0;
+  bool fail = false;
+  bool pred_fail = false;
+  msed::Grad g;
+  msed::grad_zero(g);
+  double bpost[kM] = {0.0, 0.0, 0.0};  // the β step t − 1 predicted from
+  bool pred_only = false;              // step t − 1 was prediction-only
+
+  __syncthreads();
+  const int niter = s_iters_max;
+  const int CHY = TC * N;
+  if (live) prepare_group<L, !STATIC>(st, anchored, ends, s_m, N, j);
+
+  // ---- panel staging, as msedn_kernel ----
+  auto stage_chunk = [&](int c) {
+    const size_t base = (size_t)c * CHY;
+    const size_t lim = (size_t)T * N;
+#pragma unroll
+    for (int r = 0; r < kMsedPre; ++r) {
+      const int e = r * kMsedBlock + tid;
+      const size_t gi = base + e;
+      if (e < CHY) s_y[e] = gi < lim ? Y[gi] : 0.0;
+    }
+  };
+  if (niter > 0) {
+    stage_chunk(0);
+    __syncthreads();
+  }
+
+  for (int t = 0; t < niter; ++t) {
+    const int tt = t % TC;
+    const bool act = live && t < my_iters;
+    if (act) {
+      const double* col = s_y + tt * N;  // t < nobs: always a data column here
+      // ---- pass A: the loadings at γ ----
+      GradPassStats sa;
+      auto leaf_a = [&](int c, GradPassStats& s) {
+        s.zero();
+        for (int i = c; i < N; i += kMsedClasses) {
+          double z2, z3;
+          Point p;
+          loadings(st.gamma, st.sc, i, N, s_m[i], z2, z3, p);
+          const double y = col[i];
+          msed::accum_ols(s.s.o, z2, z3, y);
+          const double pr = msed::fitted(st.beta, z2, z3);
+          const double v = y - pr;
+          s.s.vv = mfma(v, v, s.s.vv);
+          msed::accum_zv(s.zv, z2, z3, v);
+        }
+      };
+      class_tree<KQ>(j, leaf_a, sa);
+#pragma unroll
+      for (int k = 0; k < NOLS; ++k) sa.s.o[k] = group_sum_desc<L>(sa.s.o[k]);
+      sa.s.vv = group_sum_desc<L>(sa.s.vv);
+#pragma unroll
+      for (int k = 0; k < kM; ++k) sa.zv[k] = group_sum_desc<L>(sa.zv[k]);
+
+      if (t >= 1) {
+        // v = y_t − ŷ_t; mse −= v'v; a non-finite running sum returns −Inf (filter.jl:226-234)
+        mse += pred_fail ? -__builtin_inf() : -sa.s.vv;
+        fail = fail || !(fabs(mse) <= __DBL_MAX__);
+        msed::grad_accum(mdl, pred_only, sa.zv, bpost, g);
+      }
+
+      if (t < my_steps) {
+        // ---- step t (filter.jl:52-110), as msedn_kernel ----
+        pred_only = col[0] != col[0];
+        pred_fail = false;
+        if (pred_only) {
+          advance<HASB>(mdl, cB, cNu, st);
+          if constexpr (HASB) prepare_group<L, true>(st, anchored, ends, s_m, N, j);
+        } else if (!msed::ols(sa.s.o, fN, st.beta)) {
+          pred_fail = true;
+        } else {
+          bool ok = true;
+          if constexpr (!STATIC) {
+            // ---- the score at β: v per maturity, the 23 sums, the 18-vector on every lane ----
+            Sums<NSCORE> sc;
+            auto leaf_s = [&](int c, Sums<NSCORE>& s) {
+              s.zero();
+              for (int i = c; i < N; i += kMsedClasses) accum_score(s.v, st.gamma, st.sc, st.beta, i, N, s_m[i], col[i]);
+            };
+            class_tree<KQ>(j, leaf_s, sc);
+            sc.template reduce<L>();
+            {
+              double gg[kG];
+              finish_score(sc.v, st.aux, st.gamma, st.sc, anchored, ends, gg);
+              update_gamma<SCALED>(cA, cEw, st, gg);
+            }
+            prepare_group<L, !HASB>(st, anchored, ends, s_m, N, j);
+            // ---- pass C: the loadings at the updated γ ----
+            Sums<NOLS> sb;
+            auto leaf_b = [&](int c, Sums<NOLS>& s) {
+              s.zero();
+              for (int i = c; i < N; i += kMsedClasses) {
+                double z2, z3;
+                Point p;
+                loadings(st.gamma, st.sc, i, N, s_m[i], z2, z3, p);
+                msed::accum_ols(s.v, z2, z3, col[i]);
+              }
+            };
+            class_tree<KQ>(j, leaf_b, sb);
+            sb.template reduce<L>();
+            ok = msed::ols(sb.v, fN, st.beta);
+          }
+          if (ok) {
+#pragma unroll
+            for (int k = 0; k < kM; ++k) bpost[k] = st.beta[k];
+            advance<HASB>(mdl, cB, cNu, st);
+            if constexpr (HASB) prepare_group<L, true>(st, anchored, ends, s_m, N, j);
+          } else {
+            pred_fail = true;  // the state stays as the failing call left it: γ updated, β not
+            if constexpr (HASB) prepare_group<L, true>(st, anchored, ends, s_m, N, j);
+          }
+        }
+      }
+    }
+    if (tt == TC - 1) {  // chunk done: its buffer takes the next one
+      __syncthreads();
+      stage_chunk(t / TC + 1);
+      __syncthreads();
+    }
+  }
+
+  if (!live || j != 0) return;
+  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
+  if (fail) {
+    ll = -__builtin_inf();
+    atomicAdd(&flags[1], 1u);
+  }
+  out[b] = ll;
+  double go[msed::kGrad];
+  msed::grad_finish(g, th, P, space, fN, nobs, fail, go);
+#pragma unroll
+  for (int k = 0; k < msed::kGrad; ++k) grad[(size_t)b * msed::kGrad + k] = go[k];
+}
+
 size_t shmem_bytes(int L, int N, int TC) {
   return sizeof(double) * ((size_t)N + (size_t)TC * N + (size_t)(kMsedBlock / L) * kConsts);
 }
@@ -362,6 +576,26 @@ hipError_t launch_lanes(int kind, const LaunchArgs& a, int TC, const MsedRecord*
   return launch_variant<L, false, false, false>(kind, a, TC, ro);
 }
 
+template <int L, bool STATIC, bool HASB, bool SCALED>
+hipError_t launch_grad_variant(int kind, const LaunchArgs& a, int TC, double* grad) {
+  constexpr int GPB = kMsedBlock / L;
+  const int grid = (a.B + GPB - 1) / GPB;
+  hipLaunchKernelGGL((neural_grad_kernel<L, STATIC, HASB, SCALED>), dim3(grid), dim3(kMsedBlock),
+                     shmem_bytes(L, a.N, TC), a.stream, a.theta, a.P, a.B, a.space, kind, a.raw, a.T, a.N, TC, a.mats,
+                     a.T_use, a.out, grad, a.flags, a.flags_next);
+  return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_grad_lanes(int kind, const LaunchArgs& a, int TC, double* grad) {
+  if (kind_static(kind)) return launch_grad_variant<L, true, false, false>(kind, a, TC, grad);
+  const bool hb = kind_has_b(kind), sc = kind_scaled(kind);
+  if (hb && sc) return launch_grad_variant<L, false, true, true>(kind, a, TC, grad);
+  if (hb) return launch_grad_variant<L, false, true, false>(kind, a, TC, grad);
+  if (sc) return launch_grad_variant<L, false, false, true>(kind, a, TC, grad);
+  return launch_grad_variant<L, false, false, false>(kind, a, TC, grad);
+}
+
 }  // namespace
 
 bool msedn_kind(int kind) { return msedn::kind_known(kind); }
@@ -373,6 +607,9 @@ int msedn_min_n() { return msedn::kMinN; }
 // the panel chunk, the maturities and the 64 constant records of an L = 4 block stay within 64 KiB of LDS
 int msedn_max_n() { return 1024; }
 
+// the gradient kernel's block has the loss kernel's LDS layout: the same limit
+int msedn_grad_max_n() { return msedn_max_n(); }
+
 hipError_t launch_msedn(int kind, const LaunchArgs& a, int lanes, const MsedRecord* r) {
   if (!msedn::kind_known(kind) || a.N < msedn_min_n() || a.N > msedn_max_n()) return hipErrorInvalidValue;
   const int TC = chunk_columns(a.N);
@@ -380,6 +617,17 @@ hipError_t launch_msedn(int kind, const LaunchArgs& a, int lanes, const MsedReco
   switch (lanes) {
     case 4: return launch_lanes<4>(kind, a, TC, r);
     case 16: return launch_lanes<16>(kind, a, TC, r);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_msedn_grad(int kind, const LaunchArgs& a, int lanes, double* grad) {
+  if (!msedn::kind_known(kind) || a.N < msedn_min_n() || a.N > msedn_grad_max_n()) return hipErrorInvalidValue;
+  const int TC = chunk_columns(a.N);
+  if (TC < 1) return hipErrorInvalidValue;
+  switch (lanes) {
+    case 4: return launch_grad_lanes<4>(kind, a, TC, grad);
+    case 16: return launch_grad_lanes<16>(kind, a, TC, grad);
   }
   return hipErrorInvalidValue;
 }

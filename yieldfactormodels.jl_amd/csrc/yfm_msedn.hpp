@@ -1,6 +1,6 @@
 // yfm_msedn.hpp — the algebra of the neural Nelson–Siegel models (NNS, NNS-Anchored and the score-driven
 // 1/2/3[S][RW]SD-NNS[-Anchored] kinds), as plain functions that compile for the device (yfm_msedn.hip) and for the
-// host (tests/msedn_host_check.cpp).
+// host (tests/msedn_host_check.cpp, tests/msedn_grad_host_check.cpp).
 //
 // Restates, per candidate θ_b (paths relative to the reference root):
 //   set_params!              src/models/msedriven/paramteroperations.jl:25-65, src/models/static/paramteroperations.jl:19-43
@@ -331,10 +331,11 @@ YFM_MHD void ols_pass(const State& s, const double* mats, const double* y, int N
   }
 }
 
-// One filter step (filter.jl:52-110); false where the reference's step returns −Inf.
+// One filter step (filter.jl:52-110); false where the reference's step returns −Inf.  bpost, where given, receives
+// the β a data step predicts from (a prediction-only step leaves it alone).
 template <bool STATIC, bool HASB, bool SCALED>
 YFM_MHD bool filter_step(const Model& m, const double* A, const double* B, const double* nu, double* ewma, State& s,
-                         const double* mats, const double* y, int N) {
+                         const double* mats, const double* y, int N, double* bpost = nullptr) {
   if (y[0] != y[0]) {  // isnan(y[1]): prediction only
     advance<HASB>(m, B, nu, s);
     if (HASB) prepare<true>(m, s, mats, N);
@@ -353,6 +354,8 @@ YFM_MHD bool filter_step(const Model& m, const double* A, const double* B, const
     ols_pass(s, mats, y, N, o);
     if (!msed::ols(o, (double)N, s.beta)) return false;
   }
+  if (bpost)
+    for (int r = 0; r < kM; ++r) bpost[r] = s.beta[r];
   advance<HASB>(m, B, nu, s);
   if (HASB) prepare<true>(m, s, mats, N);
   return true;
@@ -381,6 +384,45 @@ YFM_MHD double get_loss(const double* th, int space, int kind, const double* mat
     if (!(fabs(mse) <= 1.79769313486231570815e308)) return -HUGE_VAL;
   }
   return mse / (double)N / (double)nobs;
+}
+
+// get_loss with ∂loss/∂(δ, Φ) in the caller's space (grad: msed::kGrad entries; the algebra and its argument are
+// yfm_msed.hpp's: γ, the loadings and β_post never see δ or Φ here either).  The loss is get_loss's, sum for sum.
+template <bool STATIC, bool HASB, bool SCALED>
+YFM_MHD double loss_and_grad(const double* th, int space, int kind, const double* mats, const double* Y, int N,
+                             int nobs, double (&grad)[msed::kGrad]) {
+  Model m;
+  State s;
+  double A[kG], B[kG], nu[kG], g0[kG], ewma[kG];
+  decode(th, space, kind, m, A, B, nu, g0);
+  init_state<STATIC>(m, g0, s, ewma, mats, N);
+  msed::Grad g;
+  msed::grad_zero(g);
+  double mse = 0.0;
+  bool fail = false;
+  for (int t = 0; t + 1 < nobs && !fail; ++t) {
+    const double* y = Y + (size_t)t * N;
+    const bool pred_only = y[0] != y[0];
+    double bpost[kM] = {0.0, 0.0, 0.0};
+    if (!filter_step<STATIC, HASB, SCALED>(m, A, B, nu, ewma, s, mats, y, N, bpost)) {
+      fail = true;
+      break;
+    }
+    double vv = 0.0, zv[kM] = {0.0, 0.0, 0.0};
+    for (int i = 0; i < N; ++i) {
+      double z2, z3;
+      Point p;
+      loadings(s.gamma, s.sc, i, N, mats[i], z2, z3, p);
+      const double v = y[N + i] - msed::fitted(s.beta, z2, z3);
+      vv = mfma(v, v, vv);
+      msed::accum_zv(zv, z2, z3, v);
+    }
+    mse -= vv;
+    fail = !(fabs(mse) <= 1.79769313486231570815e308);
+    msed::grad_accum(m, pred_only, zv, bpost, g);  // pred_only: t = 0 (a later missing column was compared: fail)
+  }
+  msed::grad_finish(g, th, kind_params(kind), space, (double)N, nobs, fail, grad);
+  return fail ? -HUGE_VAL : mse / (double)N / (double)nobs;
 }
 
 }  // namespace msedn

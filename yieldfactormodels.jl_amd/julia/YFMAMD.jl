@@ -118,6 +118,19 @@ function lambda_loss_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64
     loss, grad
 end
 
+"The same for the neural models (NNS, NNS-Anchored and the score-driven NNS kinds): (loss[B], grad[12, B]) with
+lambda_loss_grad_batch's layout, spaces and NaN columns; binds yfm_neural_loss_grad_batch."
+function neural_loss_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,
+                                T_use::Union{Nothing,Vector{Cint}} = nothing)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    loss, grad = Vector{Float64}(undef, B), Matrix{Float64}(undef, 12, B)
+    GC.@preserve Θ loss grad T_use check(@ccall LIB.yfm_neural_loss_grad_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, loss::Ptr{Cdouble},
+        grad::Ptr{Cdouble})::Cint)
+    loss, grad
+end
+
 "One Optim.NelderMead run (opt1, optimization.jl:442-451) per column of p (P×R, unconstrained) on the coordinates
 `inds` (1-based, as findall(param_groups .== g) gives them, optimization.jl:229), the others held: what estimate_steps!
 does for one NelderMead group of one group iteration (:218-247), all chains sharing one launch per round.  Returns

@@ -13,9 +13,10 @@ from .models import (DNSModel, EstimationError, GNS5Model, SingularException, TV
 from .models import (MSEDLambdaModel, StaticLambdaModel, compute_loss_grad_block, estimate_steps_batch,
                      get_param_groups, try_initializations, try_initializations_batch)
 from .models import MSEDNeuralModel, StaticNeuralModel, create_neural_model
+from .models import compute_neural_loss_grad_block, estimate_neural_steps_, estimate_neural_steps_batch
 from .params import KIND_NNS, KIND_NNS_ANCHORED, NEURAL_KINDS, is_neural_kind, neural_kind
 from .engine import Engine, get_engine
-from .driver import load_initial_parameters_, run
+from .driver import load_initial_parameters_, run, run_neural_estimation_
 from . import lbfgs
 
 __all__ = [
@@ -28,4 +29,5 @@ __all__ = [
     "StaticLambdaModel", "MSEDLambdaModel", "get_param_groups", "try_initializations", "try_initializations_batch",
     "compute_loss_grad_block", "estimate_steps_batch", "StaticNeuralModel", "MSEDNeuralModel", "create_neural_model", "KIND_NNS",
     "KIND_NNS_ANCHORED", "NEURAL_KINDS", "is_neural_kind", "neural_kind",
+    "compute_neural_loss_grad_block", "estimate_neural_steps_", "estimate_neural_steps_batch", "run_neural_estimation_",
 ]

@@ -27,8 +27,8 @@ import numpy as np
 from . import io as _io
 from . import params as _p
 from .forecasting import run_rolling_forecasts
-from .models import (AbstractKalmanModel, DNSModel, TVLambdaDNSModel, create_model, estimate_steps_, get_loss,
-                     get_loss_array, get_params, predict, set_params_)
+from .models import (AbstractKalmanModel, DNSModel, TVLambdaDNSModel, create_model, estimate_neural_steps_,
+                     estimate_steps_, get_loss, get_loss_array, get_params, predict, set_params_)
 
 
 def setup_data_paths(model_type: str, simulation: bool, scratch_dir: str, thread_id: str):
@@ -125,8 +125,8 @@ def run_estimation_(model: AbstractKalmanModel, data, in_sample_end: int, all_pa
     data[:, 1:in_sample_end]).  Like the reference's last compute_loss call, the model is left holding
     the estimated parameters."""
     if _p.is_neural_kind(model.kind):
-        raise NotImplementedError("run_estimation! is not built for the neural kinds: their estimation groups and the "
-                                  "δ/Φ gradient are what remains (DESIGN.md §7)")
+        raise NotImplementedError("run_estimation_ is the Kalman models' driver: a neural model goes through "
+                                  "run_neural_estimation_")
     if not param_groups:
         raise NotImplementedError("estimate! (LBFGS, ungrouped) is not used by the Kalman models")
     if any(g != "1" for g in param_groups):
@@ -134,6 +134,21 @@ def run_estimation_(model: AbstractKalmanModel, data, in_sample_end: int, all_pa
     init_p, ll, best_p, ir = estimate_steps_(model, data[:, :in_sample_end], np.asarray(all_params, dtype=np.float64),
                                              param_groups, max_group_iters=max_group_iters, tol=group_tol,
                                              printing=printing, iterations=iterations)
+    set_params_(model, best_p)
+    return init_p, ll, best_p, ir
+
+
+def run_neural_estimation_(model: AbstractKalmanModel, data, in_sample_end: int, all_params, param_groups,
+                           max_group_iters: int, group_tol: float, printing: bool = True, iterations: int = 500):
+    """YieldFactorModels.jl:162-186 for a model from create_neural_model: estimate_steps! over its parameter groups
+    (empty: the defaults, "1" for A, B, ω or γ and "2" for δ and Φ) on data[:, 1:in_sample_end]; the model is left
+    holding the estimated parameters."""
+    if not _p.is_neural_kind(model.kind):
+        raise NotImplementedError("run_neural_estimation_ is the neural models' driver; the others use run_estimation_")
+    init_p, ll, best_p, ir = estimate_neural_steps_(model, np.asarray(data)[:, :in_sample_end],
+                                                    np.asarray(all_params, dtype=np.float64), param_groups or None,
+                                                    max_group_iters=max_group_iters, tol=group_tol, printing=printing,
+                                                    iterations=iterations)
     set_params_(model, best_p)
     return init_p, ll, best_p, ir
 

@@ -29,7 +29,7 @@ import numpy as np
 
 from . import io as _io
 from . import params as _p
-from .models import estimate_batch, estimate_steps_batch, _engine
+from .models import estimate_batch, estimate_neural_steps_batch, estimate_steps_batch, _engine
 
 
 def _tails(r: dict, T_b: np.ndarray, h: int) -> dict:
@@ -50,6 +50,8 @@ def _estimate_tasks(model, data, tasks, init_params, max_group_iters, group_tol,
 
     if group is not None and _p.is_lambda_kind(model.kind):
         raise NotImplementedError("the λ models' group estimation is not sharded over a process group (one GPU)")
+    if group is not None and _p.is_neural_kind(model.kind):
+        raise NotImplementedError("the neural models' group estimation is not sharded over a process group (one GPU)")
     if group is not None:  # one process per GPU: windows split over the ranks, results all-gathered
         import torch
         from . import distributed as D
@@ -62,7 +64,11 @@ def _estimate_tasks(model, data, tasks, init_params, max_group_iters, group_tol,
 
 def _estimate(model, data, Theta0, T_use, max_group_iters, group_tol, iterations) -> dict:
     """estimate_steps! for every column of Θ₀: the Kalman models' single Nelder–Mead group (yfm_estimate), the λ
-    models' block-coordinate descent over their default groups (estimate_steps_batch)."""
+    and neural models' block-coordinate descent over their default groups (estimate_steps_batch,
+    estimate_neural_steps_batch)."""
+    if _p.is_neural_kind(model.kind):
+        return estimate_neural_steps_batch(model, data, Theta0, T_use=T_use, max_group_iters=max_group_iters,
+                                           tol=group_tol, iterations=iterations)
     if _p.is_lambda_kind(model.kind):
         return estimate_steps_batch(model, data, Theta0, T_use=T_use, max_group_iters=max_group_iters,
                                     tol=group_tol, iterations=iterations)

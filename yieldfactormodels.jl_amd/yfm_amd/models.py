@@ -168,9 +168,10 @@ class MSEDLambdaModel(AbstractKalmanModel):
         self.device = device
 
 
-_NEURAL_GAP = ("not built for the neural kinds (NNS, …SD-NNS): their estimation groups, the δ/Φ gradient and the rolling "
-               "driver are what remains (DESIGN.md §7); the loss, predict, get_loss_array, forecast blocks and "
-               "try_initializations are built")
+_NEURAL_GAP = ("the λ and Kalman models' entry point; the neural kinds (NNS, …SD-NNS) are estimated through names of "
+               "their own: estimate_neural_steps_ / estimate_neural_steps_batch (groups \"1\" and \"2\"), "
+               "compute_neural_loss_grad_block (the δ/Φ gradient) and driver.run_neural_estimation_; the L-BFGS "
+               "multistart over every parameter and the Kalman Nelder–Mead driver are not built for them")
 
 
 _NEURAL_RESTARTS = ("try_initializations of the static neural models draws its restarts from Julia's seeded generator "
@@ -571,6 +572,14 @@ def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, p
         raise NotImplementedError("estimate_steps_batch is " + _NEURAL_GAP)
     if not _p.is_lambda_kind(model.kind):
         raise NotImplementedError("estimate_steps_batch is the λ models' driver; Kalman models use estimate_batch")
+    return _estimate_groups(model, data, Theta0, T_use, param_groups, max_group_iters, tol, iterations,
+                            searched=isinstance(model, MSEDLambdaModel), grad="lambda_loss_grad")
+
+
+def _estimate_groups(model, data, Theta0, T_use, param_groups, max_group_iters, tol, iterations, searched: bool,
+                     grad: str) -> dict:
+    """The body of :func:`estimate_steps_batch` and :func:`estimate_neural_steps_batch`: they differ in whether the
+    start is searched (try_initializations_batch) and in the engine method that returns the δ/Φ gradient."""
     kind = model.kind
     Th = np.asarray(Theta0, dtype=np.float64)
     Th = Th.reshape(Th.shape[0], -1)
@@ -579,9 +588,10 @@ def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, p
     n_lead = P - model.base.M * (model.base.M + 1)
     _groups.check_groups(groups, n_lead)  # before any launch
     tu = None if T_use is None else np.ascontiguousarray(np.broadcast_to(T_use, (R,)), dtype=np.int32)
-    if isinstance(model, MSEDLambdaModel):
+    if searched:
         Th, _ = try_initializations_batch(Th, model, data, T_use=tu)
     eng = _engine(model, data)
+    loss_grad = getattr(eng, grad)
 
     def win(cols):
         return None if tu is None else tu[cols]
@@ -590,7 +600,7 @@ def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, p
         return -eng.loglik(kind, X, space=_p.SPACE_UNCONSTRAINED, T_use=win(cols))
 
     def value_grad(X, cols, rows):
-        loss, g = eng.lambda_loss_grad(kind, X, space=_p.SPACE_UNCONSTRAINED, T_use=win(cols))
+        loss, g = loss_grad(kind, X, space=_p.SPACE_UNCONSTRAINED, T_use=win(cols))
         return -loss, -g[np.asarray(rows) - n_lead]
 
     def nelder_mead(X, cols, rows, its, g_tol):
@@ -607,6 +617,33 @@ def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, p
                 init_c=np.asfortranarray(_p.transform_params(kind, r["init"])), ll=r["ll"], status=r["status"],
                 n_evals=r["n_evals"], evals_by_group=r["evals_by_group"], rounds_by_group=r["rounds_by_group"],
                 group_iters=r["group_iters"])
+
+
+def estimate_neural_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, param_groups=None,
+                                max_group_iters: int = 10, tol: float = 1e-8, iterations=None) -> dict:
+    """:func:`estimate_steps_batch` for the neural kinds (a model from :func:`create_neural_model`): the same
+    arguments, descent and returned dict.  The start is :func:`try_initializations_batch` for the score-driven kinds
+    (the 256-trial grid, 16 for the random-walk kinds); NNS and NNS-Anchored keep their start, as the reference's
+    ``max_tries = 0`` does (optimization.jl:37-43).  Group "1" (A, B, ω; γ for the static kinds: 18–54 coordinates)
+    is ``yfm_nm_block``, group "2" is L-BFGS on value and gradient rows from ``yfm_neural_loss_grad_batch``."""
+    if not _p.is_neural_kind(model.kind):
+        raise NotImplementedError("estimate_neural_steps_batch is the neural models' driver; λ models use "
+                                  "estimate_steps_batch, Kalman models estimate_batch")
+    return _estimate_groups(model, data, Theta0, T_use, param_groups, max_group_iters, tol, iterations,
+                            searched=isinstance(model, MSEDNeuralModel), grad="neural_loss_grad")
+
+
+def estimate_neural_steps_(model: AbstractKalmanModel, data, all_params, param_groups=None, max_group_iters: int = 10,
+                           tol: float = 1e-8, printing: bool = False, iterations: int = 500):
+    """estimate_steps! (optimization.jl:137-312) for a neural model: all_params (P×n, constrained; column 1 only is
+    used, :153) → (init_p, ll, best_p, ir) — :func:`estimate_neural_steps_batch` with one chain."""
+    A = np.asarray(all_params, dtype=np.float64)
+    start = A[:, 0] if A.ndim == 2 else A
+    r = estimate_neural_steps_batch(model, data, start[:, None], param_groups=param_groups,
+                                    max_group_iters=max_group_iters, tol=tol, iterations=iterations)
+    if printing:
+        print(f"✓ Best overall LL = {r['ll'][0]} from start 1")
+    return r["init_c"][:, 0].copy(), float(r["ll"][0]), r["theta_c"][:, 0].copy(), 0
 
 
 def compute_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
@@ -627,6 +664,15 @@ def compute_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_use=None)
     if not _p.is_lambda_kind(model.kind):
         raise NotImplementedError("the δ/Φ block gradient is the λ models'; Kalman models use compute_loss_grad_batch")
     loss, g = _engine(model, data).lambda_loss_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
+    return -loss, -g
+
+
+def compute_neural_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_use=None):
+    """:func:`compute_loss_grad_block` for the neural kinds: (−loss[B], −∂loss/∂θ[12, B]) over θ's last 12 rows."""
+    if not _p.is_neural_kind(model.kind):
+        raise NotImplementedError("compute_neural_loss_grad_block is the neural models'; λ models use "
+                                  "compute_loss_grad_block")
+    loss, g = _engine(model, data).neural_loss_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
     return -loss, -g
 
 

@@ -270,7 +270,8 @@ int yfm_last_batch_steady(yfm_ctx* ctx, long long* steady_wave_steps);
  * (transformations.jl:2-4, :21-26); the constrained space is the derivative with respect to θ_c itself.
  * The gradient is exact (forward-mode tangents of the full filter recursion, quirks of filter.jl:190-206
  * included: t = 1 not accumulated, the last column unused, a NaN column a prediction-only step whose
- * stale F/v term — and its tangent — is added again).  YFM_MODEL_DNS with N ≤ 64 only: TVλ, GNS5 and
+ * stale F/v term — and its tangent — is added again).  YFM_MODEL_DNS with N ≤ 64 only: TVλ (served by
+ * yfm_tvl_loglik_grad_batch below), GNS5 and
  * larger N return YFM_EUNSUPPORTED.  grad_out[:, b] is NaN in all P entries where loglik_out[b] is −Inf
  * (n_neg_inf) or NaN (n_init_throw), and for the candidates of yfm_last_batch_deferred (their value comes
  * from the double-double path, which carries no tangents): those are counted by
@@ -288,6 +289,29 @@ int yfm_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, 
  * the dense path of optimization.jl:10-23 there).  0 after a batch that asked for no gradient.  For
  * yfm_loglik_grad_batch_device, synchronise the stream first. */
 int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n);
+
+/* The TVλ log-likelihood WITH its gradient — the value and the ForwardDiff gradient that estimate! asks for
+ * (optimization.jl:367) of compute_loss (optimization.jl:10-23) on the extended Kalman filter of filter.jl:12-80,
+ * with the argument lists, the sign, the layout of grad_out (P×B column-major, P = 31), the spaces and the
+ * ordering and synchrony rules of yfm_loglik_grad_batch(_device).  YFM_MODEL_TVL only: any other kind returns
+ * YFM_EUNSUPPORTED (yfm_loglik_grad_batch still serves DNS and still refuses TVλ).  Every N that yfm_loglik_batch
+ * takes for TVλ is accepted.
+ *   Value: loglik_out comes from the loglik launch, enqueued first on the same stream under the context's
+ * precision (yfm_set_precision; certified double-double by default): it is bitwise what yfm_loglik_batch returns,
+ * and yfm_last_batch_flags keeps its meaning.
+ *   Gradient: always the FP64 forward-mode tangent recursion of the function the reference computes — the Jacobian
+ * column as written at filter.jl:43, t = 1 not accumulated, the last column unused, a NaN column a prediction-only
+ * step whose stale F/v term and its tangent are added again — the same bits under either precision setting and
+ * whatever batch the candidate sits in.  A window with T_use ≤ 2 gives loglik 0 and an exactly zero gradient.
+ *   NaN rule: grad_out[:, b] is NaN in all 31 entries where (1) loglik_out[b] is −Inf or NaN; (2) the value is
+ * finite but the tangent recursion's own FP64 value is not, or it meets a negative determinant; (3) any tangent is
+ * non-finite (λ overflow, for example).  Cases (2) and (3) are counted by yfm_last_batch_grad_unavailable.
+ * Additive: YFM_ABI_VERSION stays 5; a library that has the symbols has the feature. */
+int yfm_tvl_loglik_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                              const int* T_use, double* loglik_out, double* grad_out);
+int yfm_tvl_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                     int B, const int* d_T_use, double* d_loglik_out, double* d_grad_out,
+                                     void* hip_stream);
 
 /* The λ kinds' loss WITH its gradient with respect to δ and Φ — replaces, per candidate, the value and the
  * gradient that Optim.LBFGS asks for in estimate_steps! when it optimises parameter group "2", the M(M+1) = 12

@@ -445,6 +445,18 @@ int check_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
   return YFM_OK;
 }
 
+// The TVλ gradient entry points' model check: the tangent kernel of yfm_tvl_grad.hip, every N the TVλ filter takes.
+int check_tvl_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
+  if (state_dim(kind) >= 0 && kind != YFM_MODEL_TVL)
+    return set_error(YFM_EUNSUPPORTED, "yfm_tvl_loglik_grad_batch is built for YFM_MODEL_TVL only (model_kind %d: use "
+                     "yfm_loglik_grad_batch for DNS)", kind);
+  if (int r = check_batch(ctx, kind, space, P, B)) return r;
+  if (ctx->N > yfm::tvl_grad_max_n())
+    return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the TVλ gradient kernel's %d", ctx->N,
+                     yfm::tvl_grad_max_n());
+  return YFM_OK;
+}
+
 // The λ gradient entry points' model check: the five kinds of yfm_msed.hip only.
 int check_lambda_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
   if (yfm::msedn_kind(kind))
@@ -469,7 +481,7 @@ int check_neural_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
 }
 
 // The loglik launch q on the context's own workspace, then the tangent kernel on the same stream: it reads the
-// logliks q.out and that launch's deferral list and adds n_grad_unavailable to its counter bank.
+// logliks q.out and (DNS) that launch's deferral list and adds n_grad_unavailable to its counter bank.
 int launch_grad(yfm_ctx* ctx, const Launch& q, double* d_grad) {
   if (int r = launch(ctx, q)) return r;
   if (q.B == 0) return YFM_OK;
@@ -480,6 +492,7 @@ int launch_grad(yfm_ctx* ctx, const Launch& q, double* d_grad) {
   a.B = q.B;
   a.space = q.space;
   a.panel = static_cast<const double*>(ctx->panel.p);
+  a.raw = static_cast<const double*>(ctx->raw.p);
   a.T = ctx->T;
   a.N = ctx->N;
   a.np = ctx->np;
@@ -489,7 +502,8 @@ int launch_grad(yfm_ctx* ctx, const Launch& q, double* d_grad) {
   a.flags = w.bank_ptr(w.bank);  // the bank of the loglik launch just enqueued
   a.defer_list = static_cast<int*>(w.defer.p);
   a.stream = q.stream;
-  const hipError_t e = yfm::launch_dns_grad(a, q.out, d_grad);
+  const hipError_t e = q.kind == YFM_MODEL_TVL ? yfm::launch_tvl_grad(a, q.out, d_grad)
+                                               : yfm::launch_dns_grad(a, q.out, d_grad);
   if (e != hipSuccess) {
     w.bank_dirty = true;
     return set_error(YFM_EHIP, "gradient kernel launch: %s", hipGetErrorString(e));
@@ -601,6 +615,38 @@ int loss_grad_batch_device(GradCheck check, yfm_ctx* ctx, int model_kind, int pa
                            static_cast<hipStream_t>(hip_stream));
   q.msed_grad = d_grad_out;
   return launch(ctx, q);
+}
+
+// yfm_loglik_grad_batch and yfm_tvl_loglik_grad_batch: one launch path, each with its own model check
+int loglik_grad_batch(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                      const int* T_use, double* loglik_out, double* grad_out) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !loglik_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loglik_out or grad_out");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  const size_t gb = sizeof(double) * (size_t)P * (size_t)(B > 0 ? B : 1);
+  YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
+  if (int r = launch_grad(ctx, q, static_cast<double*>(ctx->own.grad.p))) return r;
+  if (B > 0) {
+    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, ctx->own.grad.p, sizeof(double) * (size_t)P * B, hipMemcpyDeviceToHost,
+                                 ctx->stream));
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+int loglik_grad_batch_device(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta,
+                             int P, int B, const int* d_T_use, double* d_loglik_out, double* d_grad_out,
+                             void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_loglik_out || !d_grad_out))
+    return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_grad_out");
+  return launch_grad(ctx, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
+                                        static_cast<hipStream_t>(hip_stream)), d_grad_out);
 }
 
 }  // namespace
@@ -793,32 +839,25 @@ int yfm_loglik_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const
 
 int yfm_loglik_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                           const int* T_use, double* loglik_out, double* grad_out) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_grad(ctx, model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!theta || !loglik_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loglik_out or grad_out");
-  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
-  Launch q;
-  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  const size_t gb = sizeof(double) * (size_t)P * (size_t)(B > 0 ? B : 1);
-  YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
-  if (int r = launch_grad(ctx, q, static_cast<double*>(ctx->own.grad.p))) return r;
-  if (B > 0) {
-    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
-    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, ctx->own.grad.p, sizeof(double) * (size_t)P * B, hipMemcpyDeviceToHost,
-                                 ctx->stream));
-  }
-  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return YFM_OK;
+  return loglik_grad_batch(check_grad, ctx, model_kind, param_space, theta, P, B, T_use, loglik_out, grad_out);
 }
 
 int yfm_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
                                  const int* d_T_use, double* d_loglik_out, double* d_grad_out, void* hip_stream) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_grad(ctx, model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!d_theta || !d_loglik_out || !d_grad_out))
-    return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_grad_out");
-  return launch_grad(ctx, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
-                                        static_cast<hipStream_t>(hip_stream)), d_grad_out);
+  return loglik_grad_batch_device(check_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
+                                  d_grad_out, hip_stream);
+}
+
+int yfm_tvl_loglik_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                              const int* T_use, double* loglik_out, double* grad_out) {
+  return loglik_grad_batch(check_tvl_grad, ctx, model_kind, param_space, theta, P, B, T_use, loglik_out, grad_out);
+}
+
+int yfm_tvl_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                     int B, const int* d_T_use, double* d_loglik_out, double* d_grad_out,
+                                     void* hip_stream) {
+  return loglik_grad_batch_device(check_tvl_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
+                                  d_grad_out, hip_stream);
 }
 
 int yfm_lambda_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,

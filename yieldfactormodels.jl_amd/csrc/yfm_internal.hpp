@@ -82,6 +82,11 @@ hipError_t launch_fixedz_dd(int kind, const LaunchArgs& a, double* rec);
 // (counted in a.flags[5]).  grad_max_n: the largest N of its lane mapping.
 int grad_max_n();
 hipError_t launch_dns_grad(const LaunchArgs& a, const double* ll, double* grad_out);
+// TVλ loglik gradient (yfm_tvl_grad.hip), enqueued after the loglik launch whose counter bank a.flags it adds to:
+// ∂loglik/∂θ into grad_out (31×B) from the FP64 tangent recursion over a.raw (NaN flags from a.panel), NaN where
+// ll[b] is not finite or the recursion's own value or tangents are not usable (those counted in a.flags[5]).
+int tvl_grad_max_n();
+hipError_t launch_tvl_grad(const LaunchArgs& a, const double* ll, double* grad_out);
 // TVλ EKF kernel (yfm_tvl.hip): lanes per filter for a batch, largest N, launcher.  `share`: launches of this
 // size the caller runs concurrently on the device (the estimation driver's chain groups; 1 otherwise)
 int tvl_lanes_for(int B, int N, int share = 1);

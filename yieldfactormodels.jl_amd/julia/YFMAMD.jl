@@ -104,6 +104,21 @@ function loglik_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; sp
     ll, grad
 end
 
+"TVλ loglik and its gradient: (ll[B], grad[31, B]), grad[:, b] = ∂(+loglik)/∂Θ[:, b] in `space` — estimate!'s
+ForwardDiff gradient (optimization.jl:367, :10-23) of the EKF of filter.jl:12-80.  ll is bitwise loglik_batch's under the
+context's precision; the gradient is the FP64 tangent recursion.  NaN gradient columns where ll is -Inf / NaN or the
+recursion's own value or tangents are not usable (yfm.h; counted by yfm_last_batch_grad_unavailable).  TVλ only."
+function tvl_loglik_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,
+                               T_use::Union{Nothing,Vector{Cint}} = nothing)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    ll, grad = Vector{Float64}(undef, B), Matrix{Float64}(undef, P, B)
+    GC.@preserve Θ ll grad T_use check(@ccall LIB.yfm_tvl_loglik_grad_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, ll::Ptr{Cdouble},
+        grad::Ptr{Cdouble})::Cint)
+    ll, grad
+end
+
 "The λ models' loss and its gradient over parameter group \"2\" (optimization.jl:442-479): (loss[B], grad[12, B]),
 loss bitwise loglik_batch's (get_loss, filter.jl:209-243), grad[:, b] = ∂(+get_loss)/∂(δ, vec Φ) of Θ[:, b] in `space`
 — the rows are Θ's last 12.  NaN gradient columns where the loss is -Inf.  NS, SD-NS, RWSD-NS, SSD-NS, SRWSD-NS only."

@@ -131,6 +131,28 @@ class Engine:
                                                          ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
                                                          ctypes.c_void_p(stream) if stream else None))
 
+    def tvl_loglik_grad(self, kind: int, theta, space: int = 0, T_use=None):
+        """(ll[B], grad[31, B]) of the TVλ model: the logliks of :meth:`loglik`, bit for bit under the context's
+        precision, and ∂(+loglik)/∂θ in the space passed from the FP64 tangent recursion (include/yfm.h
+        yfm_tvl_loglik_grad_batch).  A candidate's gradient is NaN where its loglik is −Inf or NaN, and where the
+        tangent recursion's own value or tangents are not usable (:meth:`last_grad_unavailable`)."""
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        ll = np.empty(B, dtype=np.float64)
+        grad = np.empty((P, B), dtype=np.float64, order="F")
+        _lib.check(self.lib.yfm_tvl_loglik_grad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                                      _lib.iptr(self._tuse(T_use, B)), _lib.dptr(ll), _lib.dptr(grad)))
+        return ll, grad
+
+    def tvl_loglik_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int, space: int = 0,
+                               d_T_use: int | None = None, stream: int | None = None) -> None:
+        """Device-pointer variant of :meth:`tvl_loglik_grad` (raw addresses; d_grad: 31×B column-major); asynchronous
+        on `stream`, with the ordering rules of :meth:`loglik_device`."""
+        _lib.check(self.lib.yfm_tvl_loglik_grad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
+                                                             ctypes.c_void_p(d_T_use) if d_T_use else None,
+                                                             ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
+                                                             ctypes.c_void_p(stream) if stream else None))
+
     def lambda_loss_grad(self, kind: int, theta, space: int = 0, T_use=None):
         """(loss[B], grad[12, B]) of a λ model: get_loss as :meth:`loglik` returns it, bit for bit, and its
         derivative with respect to δ(3) and vec Φ(9, column-major) — θ's last 12 rows — in the space passed

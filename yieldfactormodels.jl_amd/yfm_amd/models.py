@@ -649,8 +649,11 @@ def estimate_neural_steps_(model: AbstractKalmanModel, data, all_params, param_g
 def compute_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
     """Batched compute_loss with its gradient — what estimate!'s TwiceDifferentiable(...; autodiff=:forward)
     evaluates (optimization.jl:367): (−loglik[B], −∂loglik/∂θ[P, B]) for every unconstrained θ_b, the
-    reference's loss sign.  DNS with N ≤ 64; NaN gradient columns as in :meth:`Engine.loglik_grad`."""
-    ll, g = _engine(model, data).loglik_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
+    reference's loss sign.  DNS with N ≤ 64 (:meth:`Engine.loglik_grad`) and TVλ (:meth:`Engine.tvl_loglik_grad`);
+    NaN gradient columns as there."""
+    eng = _engine(model, data)
+    fn = eng.tvl_loglik_grad if model.kind == _p.KIND_TVL else eng.loglik_grad
+    ll, g = fn(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
     return -ll, -g
 
 
@@ -676,12 +679,13 @@ def compute_neural_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_us
     return -loss, -g
 
 
-def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 1, **opts) -> dict:
+def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 1, T_use=None, **opts) -> dict:
     """One L-BFGS chain of estimate! (optimization.jl:329-410) per column of Θ₀ (P×R; constrained by default, as
     all_params), all chains advancing in lockstep with one gradient launch per round (:mod:`yfm_amd.lbfgs`;
     `opts`: iterations, g_tol, f_abstol, allow_f_increases).  Returns the per-start arrays: theta_c (P×R),
     p (P×R unconstrained optimum), init_c (P×R: the start, constrained), ll (R), ll0 (R: the loglik at the
-    start), status (R: lbfgs status; 0 = converged), iterations (R), n_evals, rounds."""
+    start), status (R: lbfgs status; 0 = converged), iterations (R), n_evals, rounds.  ``T_use`` (an int, or one per
+    column) runs chain r on the window ``data[:, :T_use[r]]``; None is the whole panel."""
     from . import lbfgs as _lbfgs
     if _p.is_neural_kind(model.kind):
         raise NotImplementedError("estimate_ (the L-BFGS multistart) is " + _NEURAL_GAP)
@@ -689,8 +693,13 @@ def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 
     if Th.ndim == 1:
         Th = Th[:, None]
     X0 = Th if space == _p.SPACE_UNCONSTRAINED else _p.untransform_params(model.kind, Th)
-    ll0 = -compute_loss_grad_batch(model, data, X0)[0]
-    r = _lbfgs.minimize_batch(lambda X: compute_loss_grad_batch(model, data, X), X0, **opts)
+    tu = None if T_use is None else np.ascontiguousarray(np.broadcast_to(T_use, (X0.shape[1],)), dtype=np.int32)
+    ll0 = -compute_loss_grad_batch(model, data, X0, T_use=tu)[0]
+    if tu is None:
+        r = _lbfgs.minimize_batch(lambda X: compute_loss_grad_batch(model, data, X), X0, **opts)
+    else:  # finished chains drop out of the batch: every column brings its chain's window
+        r = _lbfgs.minimize_batch(lambda X, idx: compute_loss_grad_batch(model, data, X, T_use=tu[np.asarray(idx)]),
+                                  X0, with_index=True, **opts)
     return dict(theta_c=np.asfortranarray(_p.transform_params(model.kind, r["x"])), p=r["x"],
                 init_c=np.asfortranarray(_p.transform_params(model.kind, X0)), ll=-r["f"], ll0=ll0,
                 status=r["status"], iterations=r["iterations"], n_evals=r["n_evals"] + X0.shape[1],

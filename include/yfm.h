@@ -323,7 +323,8 @@ int yfm_tvl_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_spa
  * gradient is exact and needs no tangent recursion: on a data column filter replaces β by an OLS fit and takes
  * the score from it (filter.jl:52-91), so δ and Φ enter only the prediction μ + Φβ (filter.jl:84-88).  A missing
  * first column makes step 1 prediction-only from β₀ = δ (filter.jl:53-59).  The derivatives with respect to the
- * leading parameters (A, B, ω; γ for NS) are not formed: the reference's defaults optimise those by Nelder–Mead.
+ * leading parameters (A, B, ω; γ for NS) are not formed here (the reference's defaults optimise those by
+ * Nelder–Mead): yfm_lambda_loss_fullgrad_batch below forms all P rows.
  * YFM_MODEL_NS, SD_NS, RWSD_NS, SSD_NS and SRWSD_NS only: the Kalman kinds return YFM_EUNSUPPORTED (their
  * gradient is yfm_loglik_grad_batch).  grad_out[:, b] is NaN in all 12 entries where loss_out[b] is −Inf
  * (n_neg_inf).  A candidate's 13 outputs do not depend on the batch.  yfm_last_batch_flags keeps its meaning.
@@ -336,6 +337,35 @@ int yfm_lambda_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, co
 int yfm_lambda_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
                                       int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                       void* hip_stream);
+
+/* The λ kinds' loss WITH its gradient with respect to EVERY row of θ — the value and the gradient that estimate!'s
+ * L-BFGS asks for (optimization.jl:329-410, :367) of compute_loss for these kinds, with the sign of get_loss, and what
+ * an L-BFGS group of estimate_steps! that holds leading parameters needs.  The argument, ordering and synchrony rules
+ * are those of yfm_lambda_loss_grad_batch(_device); grad_out is P×B column-major in the order of θ.
+ *   What it is: the derivative of the function get_loss computes (filter.jl:209-243, K = 1) with respect to every
+ * row of θ, in the space the caller passed — what a finite-difference L-BFGS on get_loss converges to.  It is NOT
+ * the reference's own dual-number path, which cannot serve as the definition: get_grad_gamma! strips the outer tangent
+ * of β (ForwardDiff.value.(beta), filter.jl:175) and set_params! writes into Float arrays.  The leading rows (A, B, ω
+ * for SD-NS and SSD-NS; A, ω for RWSD-NS and SRWSD-NS; γ for NS) come from a forward tangent through the score
+ * recursion: per direction the scalar γ̇ and, for the scaled kinds, the tangent of the score's second-moment average,
+ * with β' = ∂β/∂γ of both OLS fits and the exact score's ∂g/∂γ (second derivatives of the loadings included).  The
+ * value path is untouched — the scaled kinds still take their score at the refined β — and the tangent is the exact
+ * score's.  The unconstrained space multiplies row A by A and row B by B(1 − B); a missing first column is a
+ * prediction-only step, γ₁ = ν + Bγ₀ with its tangent.
+ *   Bits: loss_out[b] is bitwise what yfm_loglik_batch returns, and rows P−12 … P−1 of an available gradient are
+ * bitwise yfm_lambda_loss_grad_batch's.  A candidate's P + 1 outputs do not depend on the batch it sits in.  A window
+ * that compares no column (T_use = 1) gives the loss yfm_loglik_batch gives and an exactly zero gradient.
+ *   NaN rule: grad_out[:, b] is NaN in all P rows where (1) loss_out[b] is −Inf (n_neg_inf); (2) the loss is finite
+ * but a tangent or a leading accumulator is not finite — a score that is exactly 0 on a scaled kind's first step
+ * (the root of its average is 0), λ overflow.  Case (2) is counted by yfm_last_batch_grad_unavailable.
+ *   YFM_MODEL_NS, SD_NS, RWSD_NS, SSD_NS and SRWSD_NS with the N range of yfm_loglik_batch for them; every other kind
+ * returns YFM_EUNSUPPORTED.  yfm_loglik_grad_batch and yfm_lambda_loss_grad_batch keep their behaviour and refusals.
+ * Additive: YFM_ABI_VERSION stays 5; a library that has the symbols has the feature. */
+int yfm_lambda_loss_fullgrad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                                   const int* T_use, double* loss_out, double* grad_out);
+int yfm_lambda_loss_fullgrad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                          int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                                          void* hip_stream);
 
 /* The same for the neural kinds (YFM_MODEL_NNS, NNS_ANCHORED and the 24 score-driven NNS kinds): their parameter
  * group "2" is the same last 12 rows of θ, and δ and Φ enter their filter through the prediction only as well, so

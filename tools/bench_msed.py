@@ -1,6 +1,6 @@
 """Cost of the batched loss of the static and score-driven λ models (csrc/yfm_msed.hip).
 
-    python tools/bench_msed.py [--T 600] [--reps 7] [--warmup 2] [--kinds 3,4,5,6,8] [--cases abcde]
+    python tools/bench_msed.py [--T 600] [--reps 7] [--warmup 2] [--kinds 3,4,5,6,8] [--cases abcdef]
 
 Three cases on the N = 30 grid, one yfm_loglik_batch_device launch each, HIP events around the launch, `warmup`
 untimed launches, the median of `reps` with min–max:
@@ -13,6 +13,11 @@ Two cases for the estimation of these models, SD-NS only:
       passes;
   (e) the 240-window rolling re-estimation with the default parameter groups (models.estimate_steps_batch): wall
       clock, and evaluations and rounds split by group.
+One case for the full gradient, every kind:
+  (f) one loss-and-full-gradient launch (yfm_lambda_loss_fullgrad_batch_device, all P rows) beside one loss launch and
+      one loss-and-δ/Φ-gradient launch at the shapes of (a) — and, SD-NS, at B = 7,440 —, the three alternating within
+      every repetition, with the
+      ratios of the medians to the loss launch.
 For scale: the Float64 NumPy restatement (tests/msed_reference.py) on (a), wall clock, and the project's own
 yfm_loglik_batch_device for DNS at the same B.  Prints one JSON line.  Not part of bench.py.
 """
@@ -84,6 +89,41 @@ def grad_launch_stats(eng, kind, Th, space, tu, reps, warmup):
             "finite": int(np.isfinite(d_g.cpu().numpy()).all(axis=1).sum())}
 
 
+def fullgrad_case(eng, kind, Th, space, tu, reps, warmup):
+    """Case (f): the loss launch, the loss-and-δ/Φ-gradient launch and the loss-and-full-gradient launch on the same
+    candidates, alternating within every repetition so that a drift of the shared host falls on all three."""
+    stream = torch.cuda.current_stream()
+    P_, B = Th.shape
+    d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
+    d_tu = None if tu is None else torch.from_numpy(np.ascontiguousarray(tu, dtype=np.int32)).cuda()
+    tu_ptr = None if d_tu is None else d_tu.data_ptr()
+    d_out = torch.empty(B, dtype=torch.float64, device="cuda")
+    d_g = torch.empty((B, 12), dtype=torch.float64, device="cuda")
+    d_f = torch.empty((B, P_), dtype=torch.float64, device="cuda")
+    runs = {
+        "loss": lambda: eng.loglik_device(kind, d_th.data_ptr(), P_, B, d_out.data_ptr(), space=space, d_T_use=tu_ptr,
+                                          stream=stream.cuda_stream),
+        "loss_and_grad": lambda: eng.lambda_loss_grad_device(kind, d_th.data_ptr(), P_, B, d_out.data_ptr(),
+                                                             d_g.data_ptr(), space=space, d_T_use=tu_ptr,
+                                                             stream=stream.cuda_stream),
+        "loss_and_full_grad": lambda: eng.lambda_loss_full_grad_device(kind, d_th.data_ptr(), P_, B, d_out.data_ptr(),
+                                                                       d_f.data_ptr(), space=space, d_T_use=tu_ptr,
+                                                                       stream=stream.cuda_stream)}
+    for _ in range(warmup):
+        for run in runs.values():
+            run()
+    torch.cuda.synchronize()
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, run in runs.items():
+            t[k].append(timed(run, stream))
+    out = {k: {"B": B, "ms_median": statistics.median(v), "ms_min": min(v), "ms_max": max(v)} for k, v in t.items()}
+    out["finite_full_gradients"] = int(np.isfinite(d_f.cpu().numpy()).all(axis=1).sum())
+    out["grad_over_loss"] = out["loss_and_grad"]["ms_median"] / out["loss"]["ms_median"]
+    out["full_grad_over_loss"] = out["loss_and_full_grad"]["ms_median"] / out["loss"]["ms_median"]
+    return out
+
+
 def grid(kind):
     """The start and its (A, B) trials, constrained (P × 31, or P × 7 without B)."""
     start = S.theta0_constrained(kind)
@@ -102,7 +142,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--kinds", default="3,4,5,6,8")
     ap.add_argument("--big", type=int, default=65536)
-    ap.add_argument("--cases", default="abcde")
+    ap.add_argument("--cases", default="abcdef")
     ap.add_argument("--max-group-iters", type=int, default=10)
     args = ap.parse_args()
     torch.cuda.set_device(0)
@@ -129,6 +169,12 @@ def main():
                 grad = grad_launch_stats(eng, kind, Th, space, tu, args.reps, args.warmup)
                 r[f"d_grad_{tag}"] = {"loss": loss, "loss_and_grad": grad,
                                       "ratio_of_medians": grad["ms_median"] / loss["ms_median"]}
+        if "f" in args.cases:
+            shapes = [(str(n), G, None)]
+            if kind == KIND_SD_NS:
+                shapes.append(("7440", np.asfortranarray(np.tile(G, (1, 240))), np.repeat(windows, n)))
+            for tag, Th, tu in shapes:
+                r[f"f_fullgrad_{tag}"] = fullgrad_case(eng, kind, Th, space, tu, args.reps, args.warmup)
         if kind == KIND_SD_NS and "e" in args.cases:
             model, _ = M.create_model("SD-NS", mats, len(mats), 3)
             Theta0 = np.repeat(S.theta0_constrained(kind)[:, None], 240, axis=1)

@@ -288,6 +288,7 @@ struct Launch {
   int share = 1;           // launches of this size the caller keeps in flight at once (yfm::loglik_device_ws)
   const yfm::MsedRecord* msed_rec = nullptr;  // λ models: the trajectory outputs this launch writes (nullptr: the loss)
   double* msed_grad = nullptr;  // λ and neural models: 12×B device, ∂loss/∂(δ, Φ) written with the loss
+  double* msed_fullgrad = nullptr;  // λ models: P×B device, ∂loss/∂θ written with the loss
 };
 
 // The plain log-likelihood launch, in the argument order of yfm_loglik_batch_device.
@@ -350,7 +351,8 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
   hipError_t e;
   if (yfm::msed_kind(q.kind)) {
     const int lanes = yfm::msed_lanes_for(B);
-    e = q.msed_grad  ? yfm::launch_msed_grad(q.kind, a, lanes, q.msed_grad)
+    e = q.msed_fullgrad ? yfm::launch_msed_fullgrad(q.kind, a, lanes, q.msed_fullgrad)
+        : q.msed_grad  ? yfm::launch_msed_grad(q.kind, a, lanes, q.msed_grad)
         : q.msed_rec ? yfm::launch_msed_record(q.kind, a, lanes, *q.msed_rec)
                      : yfm::launch_msed(q.kind, a, lanes);
   } else if (q.kind == YFM_MODEL_TVL) {
@@ -465,6 +467,17 @@ int check_lambda_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
   if (state_dim(kind) >= 0 && !yfm::msed_kind(kind))
     return set_error(YFM_EUNSUPPORTED, "the δ/Φ loss gradient is built for the λ kinds only (model_kind %d: use "
                      "yfm_loglik_grad_batch)", kind);
+  return check_batch(ctx, kind, space, P, B);
+}
+
+// The λ full-gradient entry points' model check: the five kinds of yfm_msed.hip only.
+int check_lambda_fullgrad(yfm_ctx* ctx, int kind, int space, int P, int B) {
+  if (yfm::msedn_kind(kind))
+    return set_error(YFM_EUNSUPPORTED, "yfm_lambda_loss_fullgrad_batch serves the λ kinds: the neural kinds have the "
+                     "delta/Phi loss gradient of yfm_neural_loss_grad_batch only (model_kind %d)", kind);
+  if (state_dim(kind) >= 0 && !yfm::msed_kind(kind))
+    return set_error(YFM_EUNSUPPORTED, "the full loss gradient is built for the λ kinds only (model_kind %d: use "
+                     "yfm_loglik_grad_batch or yfm_tvl_loglik_grad_batch)", kind);
   return check_batch(ctx, kind, space, P, B);
 }
 
@@ -584,21 +597,23 @@ using GradCheck = int (*)(yfm_ctx*, int, int, int, int);
 
 // yfm_lambda_loss_grad_batch and yfm_neural_loss_grad_batch: one launch path, each with its own model check
 int loss_grad_batch(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
-                    const int* T_use, double* loss_out, double* grad_out) {
+                    const int* T_use, double* loss_out, double* grad_out, bool full = false) {
   if (int r = check_ctx(ctx)) return r;
   if (int r = check(ctx, model_kind, param_space, P, B)) return r;
   if (B > 0 && (!theta || !loss_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loss_out or grad_out");
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
   Launch q;
   if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  const size_t gb = sizeof(double) * yfm::kMsedGrad * (size_t)(B > 0 ? B : 1);
+  const size_t rows = full ? (size_t)P : (size_t)yfm::kMsedGrad;  // full: every row of θ (the λ kinds)
+  const size_t gb = sizeof(double) * rows * (size_t)(B > 0 ? B : 1);
   YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
-  q.msed_grad = static_cast<double*>(ctx->own.grad.p);
+  double* const d_grad = static_cast<double*>(ctx->own.grad.p);
+  (full ? q.msed_fullgrad : q.msed_grad) = d_grad;
   if (int r = launch(ctx, q)) return r;
   if (B > 0) {
     YFM_HIP_CHECK(hipMemcpyAsync(loss_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
-    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, q.msed_grad, sizeof(double) * yfm::kMsedGrad * (size_t)B,
-                                 hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, d_grad, sizeof(double) * rows * (size_t)B, hipMemcpyDeviceToHost,
+                                 ctx->stream));
   }
   YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return YFM_OK;
@@ -606,14 +621,14 @@ int loss_grad_batch(GradCheck check, yfm_ctx* ctx, int model_kind, int param_spa
 
 int loss_grad_batch_device(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta,
                            int P, int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
-                           void* hip_stream) {
+                           void* hip_stream, bool full = false) {
   if (int r = check_ctx(ctx)) return r;
   if (int r = check(ctx, model_kind, param_space, P, B)) return r;
   if (B > 0 && (!d_theta || !d_loss_out || !d_grad_out))
     return set_error(YFM_EINVAL, "null d_theta, d_loss_out or d_grad_out");
   Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
                            static_cast<hipStream_t>(hip_stream));
-  q.msed_grad = d_grad_out;
+  (full ? q.msed_fullgrad : q.msed_grad) = d_grad_out;
   return launch(ctx, q);
 }
 
@@ -870,6 +885,19 @@ int yfm_lambda_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_sp
                                       void* hip_stream) {
   return loss_grad_batch_device(check_lambda_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
                                 d_grad_out, hip_stream);
+}
+
+int yfm_lambda_loss_fullgrad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                                   const int* T_use, double* loss_out, double* grad_out) {
+  return loss_grad_batch(check_lambda_fullgrad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out,
+                         true);
+}
+
+int yfm_lambda_loss_fullgrad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                          int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                                          void* hip_stream) {
+  return loss_grad_batch_device(check_lambda_fullgrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use,
+                                d_loss_out, d_grad_out, hip_stream, true);
 }
 
 int yfm_neural_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,

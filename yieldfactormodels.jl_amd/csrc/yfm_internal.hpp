@@ -139,6 +139,11 @@ hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes);
 // With filter.jl:52-91 the γ path does not depend on δ or Φ, so no tangent recursion runs (yfm_msed.hpp).
 constexpr int kMsedGrad = 12;
 hipError_t launch_msed_grad(int kind, const LaunchArgs& a, int lanes, double* grad);
+// The loss with all P derivatives (λ kinds only; grad: P×B column-major device doubles): the loss is launch_msed's and
+// the last 12 rows are launch_msed_grad's bit for bit; the leading rows (A, B, ω; γ for NS) come from the tangent of
+// the score recursion (yfm_msed.hpp).  NaN in all P rows where the loss is −Inf (a.flags[1]) and where a tangent is
+// not finite (a.flags[5]).
+hipError_t launch_msed_fullgrad(int kind, const LaunchArgs& a, int lanes, double* grad);
 // The same recursion writing its trajectory straight into the caller's (NaN-prefilled) device outputs:
 // mode 1 predict (filter.jl:284-306), 2 forecast blocks (forecasting.jl:236-250), 3 get_loss_array (filter.jl:245-281).
 struct MsedRecord {

@@ -1,4 +1,4 @@
-// yfm_msed.hip — batched loss, its δ/Φ gradient, per-step loss array, predict and forecast of the static and
+// yfm_msed.hip — batched loss, its δ/Φ gradient, its full gradient, per-step loss array, predict and forecast of the static and
 // score-driven λ Nelson–Siegel models (NS, SD-NS, RWSD-NS, SSD-NS, SRWSD-NS) for gfx950.  FP64.
 //
 // Restates, per candidate θ_b (the algebra is in yfm_msed.hpp, which names the model files):
@@ -586,6 +586,311 @@ hipError_t launch_grad_lanes(int kind, const LaunchArgs& a, int TC, double* grad
   return hipErrorInvalidValue;
 }
 
+// The statistics of the full gradient's first pass: the δ/Φ gradient's (the same sums through the same tree, the
+// score's contractions formed for NS too), D'v of the comparison and the contractions of g' (yfm_msed.hpp accum_tan).
+template <bool STATIC>
+struct FullStats {
+  GradStats<true> g;
+  double dv[2];
+  double t[STATIC ? 1 : NTAN];
+  __device__ __forceinline__ void zero() {
+    g.zero();
+    dv[0] = dv[1] = 0.0;
+#pragma unroll
+    for (int k = 0; k < (STATIC ? 1 : NTAN); ++k) t[k] = 0.0;
+  }
+  __device__ __forceinline__ void add(const FullStats& a, const FullStats& b) {
+    g.add(a.g, b.g);
+    dv[0] = a.dv[0] + b.dv[0];
+    dv[1] = a.dv[1] + b.dv[1];
+#pragma unroll
+    for (int k = 0; k < (STATIC ? 1 : NTAN); ++k) t[k] = a.t[k] + b.t[k];
+  }
+};
+
+// the second pass's: the OLS sums and the score's contractions at γ⁺ (β'(γ⁺) needs them)
+struct PassB {
+  double o[NOLS];
+  double d[NSCORE];
+  __device__ __forceinline__ void zero() {
+#pragma unroll
+    for (int k = 0; k < NOLS; ++k) o[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < NSCORE; ++k) d[k] = 0.0;
+  }
+  __device__ __forceinline__ void add(const PassB& a, const PassB& b) {
+#pragma unroll
+    for (int k = 0; k < NOLS; ++k) o[k] = a.o[k] + b.o[k];
+#pragma unroll
+    for (int k = 0; k < NSCORE; ++k) d[k] = a.d[k] + b.d[k];
+  }
+};
+
+// what a candidate of the full-gradient kernel keeps in LDS
+template <int K>
+struct FullRec {
+  Grad g;
+  Tangent<K> tn;
+  double bpost[kM];
+};
+
+// get_loss and its gradient with respect to every row of θ in one pass: lambda_grad_kernel — the same mapping,
+// staging, passes, tree and sums, so the loss and the last 12 rows are the same bits — with the tangents of the score
+// recursion (yfm_msed.hpp) replicated on every lane of the group like the state.  Writes the loss to
+// out[b] and the gradient, in the caller's space, to grad[P·b ..]; NaN in all P rows where the loss is −Inf, and where
+// a tangent or a leading accumulator is not finite (counted in flags[5]).
+template <int L, bool STATIC, bool HASB, bool SCALED>
+__global__ __launch_bounds__(kMsedBlock) void lambda_fullgrad_kernel(const double* __restrict__ theta, int P, int B,
+                                                                      int space, const double* __restrict__ Y, int T,
+                                                                      int N, int TC, const double* __restrict__ mats,
+                                                                      const int* __restrict__ T_use,
+                                                                      double* __restrict__ out,
+                                                                      double* __restrict__ grad,
+                                                                      unsigned int* __restrict__ flags,
+                                                                      unsigned int* __restrict__ flags_next) {
+  constexpr int GPB = kMsedBlock / L;
+  constexpr int KQ = log_classes_per_lane<L>();
+  constexpr int K = lead_count<STATIC, HASB>();
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  double2* s_mr = reinterpret_cast<double2*>(smem);  // (m_i, 1/m_i)
+  double* s_y = smem + 2 * N;                         // TC columns of N yields
+  __shared__ int s_iters_max;
+  // the candidate's record: what is touched once per step — the 12 δ/Φ accumulators, the tangents with the leading
+  // accumulators and β_post — lives in LDS, not in registers.  Every lane of the group computes the
+  // same values and writes them to the same words; a group is part of one wave, so its lanes read and write in step.
+  __shared__ FullRec<K> s_rec[GPB];
+
+  const int tid = threadIdx.x;
+  if (flags_next && blockIdx.x == 0 && tid < kFlagsPerBank) flags_next[tid] = 0u;  // the next launch's counters
+  const int j = tid % L;
+  const int grp = tid / L;
+  const int b = blockIdx.x * GPB + grp;
+  const bool live = b < B;
+  const int bb = live ? b : (B - 1);
+  const int nobs = T_use ? T_use[bb] : T;
+
+  if (tid == 0) s_iters_max = 0;
+  for (int i = tid; i < N; i += kMsedBlock) {
+    const double m = mats[i];
+    s_mr[i] = make_double2(m, 1.0 / m);
+  }
+  __syncthreads();
+  const int my_steps = nobs - 1;
+  const int my_iters = my_steps + 1;  // iteration t: the comparison of step t − 1, then step t
+  atomicMax(&s_iters_max, live ? my_iters : 0);
+
+  const double* th = theta + (size_t)bb * P;
+  Model mdl;
+  State st;
+  decode<STATIC, HASB>(th, space, mdl);
+  init_state(mdl, st);
+  const double fN = (double)N;
+
+  double mse = 0.0;
+  bool fail = false;
+  bool pred_fail = false;
+  Grad& g = s_rec[grp].g;
+  Tangent<K>& tn = s_rec[grp].tn;
+  double(&bpost)[kM] = s_rec[grp].bpost;  // the β step t − 1 predicted from
+  grad_zero(g);
+  tangent_init(tn);
+#pragma unroll
+  for (int k = 0; k < kM; ++k) bpost[k] = 0.0;
+  bool pred_only = false;              // step t − 1 was prediction-only
+
+  __syncthreads();
+  const int niter = s_iters_max;
+  const int CHY = TC * N;
+
+  // ---- panel staging, as msed_kernel ----
+  double pre[kMsedPre];
+  auto load_chunk = [&](int c) {
+    const size_t base = (size_t)c * CHY;
+    const size_t lim = (size_t)T * N;
+#pragma unroll
+    for (int r = 0; r < kMsedPre; ++r) {
+      const int e = r * kMsedBlock + tid;
+      const size_t gi = base + e;
+      pre[r] = (e < CHY && gi < lim) ? Y[gi] : 0.0;
+    }
+  };
+  auto store_chunk = [&]() {
+#pragma unroll
+    for (int r = 0; r < kMsedPre; ++r) {
+      const int e = r * kMsedBlock + tid;
+      if (e < CHY) s_y[e] = pre[r];
+    }
+  };
+  if (niter > 0) {
+    load_chunk(0);
+    store_chunk();
+    __syncthreads();
+    load_chunk(1);
+  }
+
+  for (int t = 0; t < niter; ++t) {
+    const int tt = t % TC;
+    const bool act = live && t < my_iters;
+    if (act) {
+      const double* col = s_y + tt * N;  // t < nobs: always a data column here
+      // ---- first pass: the loadings at γ ----
+      const Lambda la = make_lambda(st.gamma);
+      FullStats<STATIC> sa;
+      auto leaf_a = [&](int c, FullStats<STATIC>& s) {
+        s.zero();
+        for (int i = c; i < N; i += kMsedClasses) {
+          const double2 mr = s_mr[i];
+          double z, z2, z3, d2, d3;
+          loadings(la, mr.x, mr.y, z, z2, z3);
+          const double y = col[i];
+          accum_ols(s.g.s.o, z2, z3, y);
+          dloadings(la, mr.x, z, z2, d2, d3);
+          accum_score(s.g.s.d, z2, z3, d2, d3, y);
+          const double v = y - fitted(st.beta, z2, z3);
+          s.g.s.vv = mfma(v, v, s.g.s.vv);
+          accum_zv(s.g.zv, z2, z3, v);
+          accum_dv(s.dv, d2, d3, v);
+          if constexpr (!STATIC) {
+            double e2, e3;
+            d2loadings(la, mr.x, z, z2, e2, e3);
+            accum_tan(s.t, z2, z3, d2, d3, e2, e3, y);
+          }
+        }
+      };
+      class_tree<KQ>(j, leaf_a, sa);
+      sa.g.s.each([](double x) { return group_sum_desc<L>(x); });
+#pragma unroll
+      for (int k = 0; k < kM; ++k) sa.g.zv[k] = group_sum_desc<L>(sa.g.zv[k]);
+      sa.dv[0] = group_sum_desc<L>(sa.dv[0]);
+      sa.dv[1] = group_sum_desc<L>(sa.dv[1]);
+      if constexpr (!STATIC) {
+#pragma unroll
+        for (int k = 0; k < NTAN; ++k) sa.t[k] = group_sum_desc<L>(sa.t[k]);
+      }
+
+      if (t >= 1) {
+        // v = y_t − ŷ_t; mse −= v'v; a non-finite running sum returns −Inf (filter.jl:226-234)
+        mse += pred_fail ? -__builtin_inf() : -sa.g.s.vv;
+        fail = fail || !(fabs(mse) <= __DBL_MAX__);
+        grad_accum(mdl, pred_only, sa.g.zv, bpost, g);
+        lead_accum(sa.g.zv, sa.dv, st.beta, tn);
+      }
+
+      if (t < my_steps) {
+        // ---- step t (filter.jl:52-110), as msed_kernel, with the tangents (yfm_msed.hpp filter_step_tangent) ----
+        pred_only = col[0] != col[0];
+        pred_fail = false;
+        if (pred_only) {
+          advance_tangent_pred_only<HASB>(mdl, st.gamma, tn);
+          advance<HASB>(mdl, st);
+        } else if (bool ridged = false; !ols(sa.g.s.o, fN, st.beta, ridged)) {
+          pred_fail = true;
+        } else {
+          bool ok = true;
+          double bp[kM] = {0.0, 0.0, 0.0}, dv[2];
+          ols_tangent(sa.g.s.o, fN, ridged, sa.g.s.d, st.beta, bp, dv);
+          if constexpr (!STATIC) {
+            double sc;
+            if constexpr (SCALED) {
+              Refine sr;
+              auto leaf_r = [&](int c, Refine& s) {
+                s.zero();
+                for (int i = c; i < N; i += kMsedClasses) {
+                  const double2 mr = s_mr[i];
+                  double z, z2, z3, d2, d3;
+                  loadings(la, mr.x, mr.y, z, z2, z3);
+                  dloadings(la, mr.x, z, z2, d2, d3);
+                  accum_refine(s.r, st.beta, z2, z3, d2, d3, col[i]);
+                }
+              };
+              class_tree<KQ>(j, leaf_r, sr);
+#pragma unroll
+              for (int k = 0; k < NREFINE; ++k) sr.r[k] = group_sum_desc<L>(sr.r[k]);
+              sc = score_refined(sa.g.s.o, fN, ridged, sa.g.s.d, sr.r, st.beta);
+            } else {
+              sc = score(sa.g.s.d, st.beta);
+            }
+            const double gprime = score_tangent(sa.g.s.d, sa.t, st.beta, bp, dv);
+            update_gamma<SCALED>(mdl, st, sc);
+            update_gamma_tangent<SCALED>(mdl, st, sc, gprime, tn);
+            // ---- second pass: the loadings at the updated γ ----
+            const Lambda lb = make_lambda(st.gamma);
+            PassB sb;
+            auto leaf_b = [&](int c, PassB& s) {
+              s.zero();
+              for (int i = c; i < N; i += kMsedClasses) {
+                const double2 mr = s_mr[i];
+                double z, z2, z3, d2, d3;
+                loadings(lb, mr.x, mr.y, z, z2, z3);
+                const double y = col[i];
+                accum_ols(s.o, z2, z3, y);
+                dloadings(lb, mr.x, z, z2, d2, d3);
+                accum_score(s.d, z2, z3, d2, d3, y);
+              }
+            };
+            class_tree<KQ>(j, leaf_b, sb);
+#pragma unroll
+            for (int k = 0; k < NOLS; ++k) sb.o[k] = group_sum_desc<L>(sb.o[k]);
+#pragma unroll
+            for (int k = 0; k < NSCORE; ++k) sb.d[k] = group_sum_desc<L>(sb.d[k]);
+            ok = ols(sb.o, fN, st.beta, ridged);
+            if (ok) ols_tangent(sb.o, fN, ridged, sb.d, st.beta, bp, dv);
+          }
+          if (ok) {
+#pragma unroll
+            for (int k = 0; k < kM; ++k) bpost[k] = st.beta[k];
+            advance_tangent<HASB>(mdl, st.gamma, bp, tn);
+            advance<HASB>(mdl, st);
+          } else {
+            pred_fail = true;
+          }
+        }
+      }
+    }
+    if (tt == TC - 1) {  // chunk done: its buffer takes the prefetched chunk, prefetch the one after
+      __syncthreads();
+      store_chunk();
+      __syncthreads();
+      load_chunk(t / TC + 2);
+    }
+  }
+
+  if (!live || j != 0) return;
+  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
+  if (fail) {
+    ll = -__builtin_inf();
+    atomicAdd(&flags[1], 1u);
+  }
+  out[b] = ll;
+  double go[K + kGrad];
+  if (fullgrad_finish<STATIC, HASB>(mdl, tn, g, th, P, space, fN, nobs, fail, go)) atomicAdd(&flags[5], 1u);
+#pragma unroll
+  for (int k = 0; k < K + kGrad; ++k) grad[(size_t)b * (K + kGrad) + k] = go[k];
+}
+
+template <int L, bool STATIC, bool HASB, bool SCALED>
+hipError_t launch_fullgrad_variant(const LaunchArgs& a, int TC, double* grad) {
+  constexpr int GPB = kMsedBlock / L;
+  const int grid = (a.B + GPB - 1) / GPB;
+  const size_t shmem = sizeof(double) * (size_t)(2 * a.N + TC * a.N);
+  hipLaunchKernelGGL((lambda_fullgrad_kernel<L, STATIC, HASB, SCALED>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
+                     a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, grad, a.flags,
+                     a.flags_next);
+  return hipGetLastError();
+}
+
+template <int L>
+hipError_t launch_fullgrad_lanes(int kind, const LaunchArgs& a, int TC, double* grad) {
+  switch (kind) {
+    case YFM_MODEL_NS: return launch_fullgrad_variant<L, true, false, false>(a, TC, grad);
+    case YFM_MODEL_SD_NS: return launch_fullgrad_variant<L, false, true, false>(a, TC, grad);
+    case YFM_MODEL_RWSD_NS: return launch_fullgrad_variant<L, false, false, false>(a, TC, grad);
+    case YFM_MODEL_SSD_NS: return launch_fullgrad_variant<L, false, true, true>(a, TC, grad);
+    case YFM_MODEL_SRWSD_NS: return launch_fullgrad_variant<L, false, false, true>(a, TC, grad);
+  }
+  return hipErrorInvalidValue;
+}
+
 template <int L, bool STATIC, bool HASB, bool SCALED>
 hipError_t launch_variant(const LaunchArgs& a, int TC, const MsedOut* ro) {
   constexpr int GPB = kMsedBlock / L;
@@ -661,6 +966,17 @@ hipError_t launch_msed_grad(int kind, const LaunchArgs& a, int lanes, double* gr
   switch (lanes) {
     case 4: return launch_grad_lanes<4>(kind, a, TC, grad);
     case 16: return launch_grad_lanes<16>(kind, a, TC, grad);
+  }
+  return hipErrorInvalidValue;
+}
+
+hipError_t launch_msed_fullgrad(int kind, const LaunchArgs& a, int lanes, double* grad) {
+  if (!msed::kind_known(kind) || a.P != msed::kind_params(kind)) return hipErrorInvalidValue;
+  const int TC = chunk_columns(a.N);
+  if (TC < 1) return hipErrorInvalidValue;
+  switch (lanes) {
+    case 4: return launch_fullgrad_lanes<4>(kind, a, TC, grad);
+    case 16: return launch_fullgrad_lanes<16>(kind, a, TC, grad);
   }
   return hipErrorInvalidValue;
 }

@@ -482,5 +482,301 @@ YFM_MHD double get_loss_grad(const double* th, int space, const double* mats, co
   return fail ? -HUGE_VAL : mse / (double)N / (double)nobs;
 }
 
+// ---- ∂loss/∂(A, B, ω; γ for NS): the full gradient ---------------------------------------------------------------
+// The derivative of the function get_loss computes with respect to the leading parameters, by a forward tangent
+// through the score recursion.  γ is a scalar, so per direction k the state tangent is the scalar
+// γ̇ₖ and, for the scaled kinds, ėₖ of the score's second-moment average.  The directions are the constrained
+// parameters — (A, B, ω), (A, ω) or (γ) — and space 0 multiplies the finished rows by dA/dx = A and dB/dx = B(1 − B).
+//
+// With Z = Z(γ), D = ∂Z/∂γ, E = ∂²Z/∂γ², G = Z'Z (ridged where ols ridged), v = y − Zβ and w = Dβ:
+//   β' = ∂β/∂γ = G⁻¹(D'v − Z'w)                                   (ols_tangent)
+//   g' = ∂g/∂γ = 2[−(w + Zβ')'w + v'Eβ + v'Dβ']                   (score_tangent)
+// both from contractions over the maturities: the score's eight, and D'D (3), E'[1 z₂ z₃] (6), E'y (2) (accum_tan).
+// The value path is untouched: the scaled kinds keep score_refined, and the tangent is the exact score's.
+enum : int { DD22 = 0, DD23, DD33, E21, E22, E23, E31, E32, E33, EY2, EY3, NTAN };
+
+// ∂²Z₂/∂γ² = (∂u/∂λ)q² + uq and ∂²Z₃/∂γ² = (∂u/∂λ − m²z)q² + (u + mz)q with q = e^γ, u = ∂Z₂/∂λ = (z − Z₂)/λ,
+// ∂u/∂λ = (−mz − 2u)/λ
+YFM_MHD void d2loadings(const Lambda& l, double m, double z, double z2, double& e2, double& e3) {
+  const double u = (z - z2) * l.rl;
+  const double mz = m * z;
+  const double du = (-mz - 2.0 * u) * l.rl;
+  e2 = mfma(du, l.dl, u) * l.dl;
+  e3 = mfma(mfma(-m, mz, du), l.dl, u + mz) * l.dl;
+}
+
+YFM_MHD void accum_tan(double (&t)[NTAN], double z2, double z3, double d2, double d3, double e2, double e3, double y) {
+  t[DD22] = mfma(d2, d2, t[DD22]);
+  t[DD23] = mfma(d2, d3, t[DD23]);
+  t[DD33] = mfma(d3, d3, t[DD33]);
+  t[E21] += e2;
+  t[E22] = mfma(e2, z2, t[E22]);
+  t[E23] = mfma(e2, z3, t[E23]);
+  t[E31] += e3;
+  t[E32] = mfma(e3, z2, t[E32]);
+  t[E33] = mfma(e3, z3, t[E33]);
+  t[EY2] = mfma(e2, y, t[EY2]);
+  t[EY3] = mfma(e3, y, t[EY3]);
+}
+
+// D'v of one maturity of the comparison: v = y_{t+1} − Zβ_pred at the loadings the prediction used
+YFM_MHD void accum_dv(double (&s)[2], double d2, double d3, double v) {
+  s[0] = mfma(d2, v, s[0]);
+  s[1] = mfma(d3, v, s[1]);
+}
+
+// β' = G⁻¹(D'v − Z'Dβ) at the OLS β of the statistics o, d, in the system ols solved (ridged or not); dv receives
+// d₂'v and d₃'v.  bp is left alone where the factorisation fails (ols failed on the same matrix: the step is −Inf).
+YFM_MHD void ols_tangent(const double (&o)[NOLS], double n, bool ridged, const double (&d)[NSCORE],
+                         const double (&beta)[kM], double (&bp)[kM], double (&dv)[2]) {
+  const double zb2 = mfma(d[D23], beta[2], mfma(d[D22], beta[1], d[D21] * beta[0]));  // d₂'Zβ
+  const double zb3 = mfma(d[D33], beta[2], mfma(d[D32], beta[1], d[D31] * beta[0]));  // d₃'Zβ
+  dv[0] = d[DY2] - zb2;
+  dv[1] = d[DY3] - zb3;
+  const double zw0 = mfma(d[D31], beta[2], d[D21] * beta[1]);  // Z'w
+  const double zw1 = mfma(d[D32], beta[2], d[D22] * beta[1]);
+  const double zw2 = mfma(d[D33], beta[2], d[D23] * beta[1]);
+  const double rhs[kM] = {-zw0, dv[0] - zw1, dv[1] - zw2};
+  const double rd = ridged ? kRidge : 0.0;
+  (void)chol3_solve(n + rd, o[S2], o[S3], o[G22] + rd, o[G23], o[G33] + rd, rhs, bp);
+}
+
+// g' = ∂g/∂γ of the score g = 2v'Dβ at the OLS β (β' and D'v from ols_tangent)
+YFM_MHD double score_tangent(const double (&d)[NSCORE], const double (&t)[NTAN], const double (&beta)[kM],
+                             const double (&bp)[kM], const double (&dv)[2]) {
+  const double ww = mfma(beta[2] * beta[2], t[DD33], mfma(2.0 * beta[1] * beta[2], t[DD23], beta[1] * beta[1] * t[DD22]));
+  const double zw0 = mfma(d[D31], beta[2], d[D21] * beta[1]);
+  const double zw1 = mfma(d[D32], beta[2], d[D22] * beta[1]);
+  const double zw2 = mfma(d[D33], beta[2], d[D23] * beta[1]);
+  const double bzw = mfma(bp[2], zw2, mfma(bp[1], zw1, bp[0] * zw0));                            // β''Z'w
+  const double ev2 = t[EY2] - mfma(t[E23], beta[2], mfma(t[E22], beta[1], t[E21] * beta[0]));  // e₂'v
+  const double ev3 = t[EY3] - mfma(t[E33], beta[2], mfma(t[E32], beta[1], t[E31] * beta[0]));  // e₃'v
+  const double veb = mfma(beta[2], ev3, beta[1] * ev2);                                          // v'Eβ
+  const double vdb = mfma(bp[2], dv[1], bp[1] * dv[0]);                                          // v'Dβ'
+  return 2.0 * ((veb + vdb) - (ww + bzw));
+}
+
+// The tangents of one candidate.  K directions: (A, B, ω) K = 3, (A, ω) K = 2, (γ) K = 1 — A is direction 0, B
+// direction 1 where there is one, ω (γ) the last.
+template <int K>
+struct Tangent {
+  double gd[K];     // γ̇ₖ of the state's γ
+  double ed[K];     // ėₖ of the score's second-moment average (scaled kinds)
+  double gp[K];     // γ̇⁺ₖ of the γ the last data step's second OLS ran at
+  double pb[kM];    // Φβ'(γ⁺) of that OLS: ∂β_pred/∂pₖ = pb·γ̇⁺ₖ (zero after a prediction-only step)
+  double lead[K];   // Σ over the compared columns of ½ ∂(−‖v‖²)/∂pₖ
+};
+
+template <bool STATIC, bool HASB>
+constexpr int lead_count() {
+  return STATIC ? 1 : (HASB ? 3 : 2);
+}
+
+// γ₀ = ω (set_params!): γ̇ is 1 in the ω direction (γ for NS) and 0 in the others
+template <int K>
+YFM_MHD void tangent_init(Tangent<K>& tn) {
+  for (int k = 0; k < K; ++k) {
+    tn.gd[k] = k == K - 1 ? 1.0 : 0.0;
+    tn.ed[k] = 0.0;
+    tn.gp[k] = 0.0;
+    tn.lead[k] = 0.0;
+  }
+  for (int r = 0; r < kM; ++r) tn.pb[r] = 0.0;
+}
+
+// The tangent of update_gamma, called after it (s holds e⁺ and fⁿ) with the score g it was given and g' = ∂g/∂γ:
+//   ġₖ = g'γ̇ₖ;  scaled: ė⁺ₖ = fėₖ + 2(1 − f)gġₖ, c = 1 − fⁿ, r = √(e⁺/c), s = r + ε, ṡₖ = ė⁺ₖ/(2cr),
+//   g̃ = g/s, g̃˙ₖ = ġₖ/s − gṡₖ/s²;  γ̇⁺ₖ = γ̇ₖ + Ȧₖg̃ + Ag̃˙ₖ.   r = 0 (a score that is exactly zero) gives NaN.
+template <bool SCALED, int K>
+YFM_MHD void update_gamma_tangent(const Model& m, const State& s, double g, double gprime, Tangent<K>& tn) {
+  double rs = 1.0, c2r = 1.0;
+  if (SCALED) {
+    const double c = 1.0 - s.fpow;
+    const double r = sqrt(s.ewma / c);
+    rs = 1.0 / (r + kEps);
+    c2r = 2.0 * c * r;
+  }
+  const double gs = SCALED ? g * rs : g;
+  for (int k = 0; k < K; ++k) {
+    double gk = gprime * tn.gd[k];
+    if (SCALED) {
+      tn.ed[k] = kForget * tn.ed[k] + 2.0 * (1.0 - kForget) * (g * gk);
+      const double sd = tn.ed[k] / c2r;
+      gk = gk * rs - g * sd * (rs * rs);
+    }
+    tn.gd[k] = tn.gd[k] + (k == 0 ? gs : 0.0) + m.A * gk;
+  }
+}
+
+// The end of a data step: β_pred = μ + Φβ₂ with β̇₂ₖ = β'(γ⁺)γ̇⁺ₖ, then the tangent of advance's γ ← ν + Bγ⁺ (gamma: γ⁺,
+// the state's γ before advance): γ̇ₖ ← ν̇ₖ + Ḃₖγ⁺ + Bγ̇⁺ₖ with ν = (1 − B)ω, so ν̇ = −ω for B and 1 − B for ω.
+template <bool HASB, int K>
+YFM_MHD void advance_tangent(const Model& m, double gamma, const double (&bp)[kM], Tangent<K>& tn) {
+  for (int r = 0; r < kM; ++r) {
+    double a = 0.0;
+    for (int c = 0; c < kM; ++c) a = mfma(m.Phi[r][c], bp[c], a);
+    tn.pb[r] = a;
+  }
+  for (int k = 0; k < K; ++k) {
+    tn.gp[k] = tn.gd[k];
+    if (HASB) {
+      const double off = k == 1 ? gamma - m.gamma0 : (k == K - 1 ? 1.0 - m.B : 0.0);
+      tn.gd[k] = mfma(m.B, tn.gd[k], off);
+    }
+  }
+}
+
+// A prediction-only step (a missing first column): γ₁ = ν + Bγ₀ with its tangent, and no β̇
+template <bool HASB, int K>
+YFM_MHD void advance_tangent_pred_only(const Model& m, double gamma, Tangent<K>& tn) {
+  const double zero[kM] = {0.0, 0.0, 0.0};
+  advance_tangent<HASB>(m, gamma, zero, tn);
+}
+
+// One compared column: v = y_{t+1} − Z(γ)β_pred, zv = Z'v, dv = [d₂'v, d₃'v] at the state's γ, bpred the state's β:
+//   ½ ∂(−‖v‖²)/∂pₖ = (v'Dβ_pred)γ̇ₖ + (v'ZΦβ')γ̇⁺ₖ
+template <int K>
+YFM_MHD void lead_accum(const double (&zv)[kM], const double (&dv)[2], const double (&bpred)[kM], Tangent<K>& tn) {
+  const double c1 = mfma(bpred[2], dv[1], bpred[1] * dv[0]);
+  const double c2 = mfma(zv[2], tn.pb[2], mfma(zv[1], tn.pb[1], zv[0] * tn.pb[0]));
+  for (int k = 0; k < K; ++k) tn.lead[k] = mfma(c2, tn.gp[k], mfma(c1, tn.gd[k], tn.lead[k]));
+}
+
+// All P rows in the caller's space: the K leading rows scaled by 2/(N·nobs) and by dA/dx = A, dB/dx = B(1 − B) in
+// space 0, then grad_finish's 12.  NaN in every row where the loss is −Inf (fail) and where a tangent or a leading
+// accumulator is not finite; returns true in the second case alone (the gradient of a finite loss is unavailable).
+template <bool STATIC, bool HASB, int K>
+YFM_MHD bool fullgrad_finish(const Model& m, const Tangent<K>& tn, const Grad& g, const double* th, int P, int space,
+                             double n, int nobs, bool fail, double* out /* P */) {
+  const double sc = 2.0 / n / (double)nobs;
+  const double big = 1.79769313486231570815e308;
+  bool bad = false;
+  for (int k = 0; k < K; ++k) {
+    bad = bad || !(fabs(tn.gd[k]) <= big) || !(fabs(tn.ed[k]) <= big) || !(fabs(tn.gp[k]) <= big) ||
+          !(fabs(tn.lead[k]) <= big);
+    double v = tn.lead[k] * sc;
+    if (space == 0 && !STATIC && k == 0) v = v * m.A;
+    if (space == 0 && HASB && k == 1) v = v * (m.B * (1.0 - m.B));
+    out[k] = v;
+  }
+  for (int r = 0; r < kM; ++r) bad = bad || !(fabs(tn.pb[r]) <= big);
+  double tail[kGrad];
+  grad_finish(g, th, P, space, n, nobs, fail, tail);
+  for (int k = 0; k < kGrad; ++k) out[K + k] = tail[k];
+  if (fail || bad)
+    for (int k = 0; k < P; ++k) out[k] = __builtin_nan("");
+  return bad && !fail;
+}
+
+// filter_step with the tangents carried: the same value path, sum for sum, with the score statistics formed for NS too
+// (β' needs them) and the second pass's as well.
+template <bool STATIC, bool HASB, bool SCALED, int K>
+YFM_MHD bool filter_step_tangent(const Model& m, State& s, Tangent<K>& tn, const double* mats, const double* y, int N,
+                                 double* bpost) {
+  if (y[0] != y[0]) {
+    advance_tangent_pred_only<HASB>(m, s.gamma, tn);
+    advance<HASB>(m, s);
+    return true;
+  }
+  Lambda l = make_lambda(s.gamma);
+  double o[NOLS] = {0, 0, 0, 0, 0, 0, 0, 0}, d[NSCORE] = {0, 0, 0, 0, 0, 0, 0, 0};
+  double tt[NTAN] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = 0; i < N; ++i) {
+    double z, z2, z3, d2, d3;
+    loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+    accum_ols(o, z2, z3, y[i]);
+    dloadings(l, mats[i], z, z2, d2, d3);
+    accum_score(d, z2, z3, d2, d3, y[i]);
+    if (!STATIC) {
+      double e2, e3;
+      d2loadings(l, mats[i], z, z2, e2, e3);
+      accum_tan(tt, z2, z3, d2, d3, e2, e3, y[i]);
+    }
+  }
+  bool ridged;
+  if (!ols(o, (double)N, s.beta, ridged)) return false;
+  double bp[kM] = {0.0, 0.0, 0.0}, dv[2];
+  ols_tangent(o, (double)N, ridged, d, s.beta, bp, dv);
+  if (!STATIC) {
+    double g;
+    if (SCALED) {
+      double r[NREFINE] = {0, 0, 0, 0};
+      for (int i = 0; i < N; ++i) {
+        double z, z2, z3, d2, d3;
+        loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+        dloadings(l, mats[i], z, z2, d2, d3);
+        accum_refine(r, s.beta, z2, z3, d2, d3, y[i]);
+      }
+      g = score_refined(o, (double)N, ridged, d, r, s.beta);
+    } else {
+      g = score(d, s.beta);
+    }
+    const double gprime = score_tangent(d, tt, s.beta, bp, dv);
+    update_gamma<SCALED>(m, s, g);
+    update_gamma_tangent<SCALED>(m, s, g, gprime, tn);
+    l = make_lambda(s.gamma);
+    double o2[NOLS] = {0, 0, 0, 0, 0, 0, 0, 0}, dd[NSCORE] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < N; ++i) {
+      double z, z2, z3, d2, d3;
+      loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+      accum_ols(o2, z2, z3, y[i]);
+      dloadings(l, mats[i], z, z2, d2, d3);
+      accum_score(dd, z2, z3, d2, d3, y[i]);
+    }
+    if (!ols(o2, (double)N, s.beta, ridged)) return false;
+    ols_tangent(o2, (double)N, ridged, dd, s.beta, bp, dv);
+  }
+  for (int r = 0; r < kM; ++r) bpost[r] = s.beta[r];
+  advance_tangent<HASB>(m, s.gamma, bp, tn);
+  advance<HASB>(m, s);
+  return true;
+}
+
+// get_loss with all P derivatives in the caller's space (grad: P entries): the loss is get_loss's and the last 12
+// rows are get_loss_grad's, sum for sum.  unavailable, where given, receives fullgrad_finish's return.
+template <bool STATIC, bool HASB, bool SCALED>
+YFM_MHD double get_loss_fullgrad(const double* th, int space, const double* mats, const double* Y, int N, int nobs,
+                                 double* grad, bool* unavailable = nullptr) {
+  constexpr int K = lead_count<STATIC, HASB>();
+  Model m;
+  State s;
+  decode<STATIC, HASB>(th, space, m);
+  init_state(m, s);
+  Grad g;
+  grad_zero(g);
+  Tangent<K> tn;
+  tangent_init(tn);
+  const int P = K + kGrad;
+  double mse = 0.0;
+  bool fail = false;
+  for (int t = 0; t + 1 < nobs && !fail; ++t) {
+    const double* y = Y + (size_t)t * N;
+    const bool pred_only = y[0] != y[0];
+    double bpost[kM] = {0.0, 0.0, 0.0};
+    if (!filter_step_tangent<STATIC, HASB, SCALED>(m, s, tn, mats, y, N, bpost)) {
+      fail = true;
+      break;
+    }
+    const Lambda l = make_lambda(s.gamma);
+    double vv = 0.0, zv[kM] = {0.0, 0.0, 0.0}, dv[2] = {0.0, 0.0};
+    for (int i = 0; i < N; ++i) {
+      double z, z2, z3, d2, d3;
+      loadings(l, mats[i], 1.0 / mats[i], z, z2, z3);
+      const double v = y[N + i] - fitted(s.beta, z2, z3);
+      vv = mfma(v, v, vv);
+      accum_zv(zv, z2, z3, v);
+      dloadings(l, mats[i], z, z2, d2, d3);
+      accum_dv(dv, d2, d3, v);
+    }
+    mse -= vv;
+    fail = !(fabs(mse) <= 1.79769313486231570815e308);
+    grad_accum(m, pred_only, zv, bpost, g);
+    lead_accum(zv, dv, s.beta, tn);
+  }
+  const bool un = fullgrad_finish<STATIC, HASB>(m, tn, g, th, P, space, (double)N, nobs, fail, grad);
+  if (unavailable) *unavailable = un;
+  return fail ? -HUGE_VAL : mse / (double)N / (double)nobs;
+}
+
 }  // namespace msed
 }  // namespace yfm

@@ -133,6 +133,24 @@ function lambda_loss_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64
     loss, grad
 end
 
+"The λ models' loss and its gradient over every row of Θ — estimate!'s value and gradient (optimization.jl:329-410,
+:367) for these kinds: (loss[B], grad[P, B]), loss bitwise loglik_batch's (get_loss, filter.jl:209-243), grad[:, b] =
+∂(+get_loss)/∂Θ[:, b] in `space`.  The leading rows (A, B, ω; γ for NS) come from a forward tangent through the score
+recursion — the derivative of the function get_loss computes, not the reference's dual-number path (filter.jl:175
+strips β's tangent); the last 12 rows are lambda_loss_grad_batch's bit for bit.  NaN gradient columns where the loss is
+-Inf or a tangent is not finite (yfm.h; the second counted by yfm_last_batch_grad_unavailable).  NS, SD-NS, RWSD-NS,
+SSD-NS, SRWSD-NS only; binds yfm_lambda_loss_fullgrad_batch."
+function lambda_loss_fullgrad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,
+                                    T_use::Union{Nothing,Vector{Cint}} = nothing)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    loss, grad = Vector{Float64}(undef, B), Matrix{Float64}(undef, P, B)
+    GC.@preserve Θ loss grad T_use check(@ccall LIB.yfm_lambda_loss_fullgrad_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, loss::Ptr{Cdouble},
+        grad::Ptr{Cdouble})::Cint)
+    loss, grad
+end
+
 "The same for the neural models (NNS, NNS-Anchored and the score-driven NNS kinds): (loss[B], grad[12, B]) with
 lambda_loss_grad_batch's layout, spaces and NaN columns; binds yfm_neural_loss_grad_batch."
 function neural_loss_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,

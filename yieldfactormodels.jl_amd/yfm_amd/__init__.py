@@ -10,7 +10,7 @@ from .params import (KIND_DNS, KIND_GNS, KIND_TVL, SPACE_CONSTRAINED, SPACE_UNCO
 from .models import (DNSModel, EstimationError, GNS5Model, SingularException, TVLambdaDNSModel, compute_loss, compute_loss_batch, compute_loss_grad_batch,
                      create_model, estimate_, estimate_batch, estimate_lbfgs_batch, estimate_steps_, filter_states, forecast_batch, get_loss, get_loss_array, get_loss_batch,
                      get_params, predict, set_params_, transform_params, untransform_params)
-from .models import (MSEDLambdaModel, StaticLambdaModel, compute_loss_grad_block, estimate_steps_batch,
+from .models import (MSEDLambdaModel, StaticLambdaModel, compute_lambda_loss_grad_batch, compute_loss_grad_block, estimate_steps_batch,
                      get_param_groups, try_initializations, try_initializations_batch)
 from .models import MSEDNeuralModel, StaticNeuralModel, create_neural_model
 from .models import compute_neural_loss_grad_block, estimate_neural_steps_, estimate_neural_steps_batch
@@ -27,7 +27,7 @@ __all__ = [
     "get_engine", "run", "load_initial_parameters_", "compute_loss_grad_batch", "estimate_", "estimate_lbfgs_batch",
     "EstimationError", "lbfgs", "KIND_NS", "KIND_SD_NS", "KIND_RWSD_NS", "KIND_SSD_NS", "KIND_SRWSD_NS", "LAMBDA_KINDS",
     "StaticLambdaModel", "MSEDLambdaModel", "get_param_groups", "try_initializations", "try_initializations_batch",
-    "compute_loss_grad_block", "estimate_steps_batch", "StaticNeuralModel", "MSEDNeuralModel", "create_neural_model", "KIND_NNS",
+    "compute_loss_grad_block", "compute_lambda_loss_grad_batch", "estimate_steps_batch", "StaticNeuralModel", "MSEDNeuralModel", "create_neural_model", "KIND_NNS",
     "KIND_NNS_ANCHORED", "NEURAL_KINDS", "is_neural_kind", "neural_kind",
     "compute_neural_loss_grad_block", "estimate_neural_steps_", "estimate_neural_steps_batch", "run_neural_estimation_",
 ]

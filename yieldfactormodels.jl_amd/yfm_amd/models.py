@@ -511,13 +511,13 @@ def forecast_batch(model: AbstractKalmanModel, data, Theta, T_use, horizon: int,
 
 
 def estimate_steps_(model: AbstractKalmanModel, data, all_params, param_groups=None, max_group_iters: int = 10,
-                    tol: float = 1e-8, printing: bool = False, iterations: int = 500):
+                    tol: float = 1e-8, printing: bool = False, iterations: int = 500, full_gradient: bool = False):
     """estimate_steps! (optimization.jl:137-312): all_params (P×n, constrained; column 1 only is used, :153)
     → (init_p, ll, best_p, ir), init_p and best_p constrained like the
     reference: init_p = transform_params of the untransformed, sanitised and ×0.95-rescaled start
     (:157-184, :298-302).
     Kalman models: parameter groups other than all-"1" are not supported (their default, kalmanbasemodel.jl:150-159).
-    λ models: :func:`estimate_steps_batch` with one chain.
+    λ models: :func:`estimate_steps_batch` with one chain (`full_gradient` is its keyword, for them alone).
     `iterations`: the NelderMead budget per group (opt1, optimization.jl:442-451: 500)."""
     if _p.is_neural_kind(model.kind):
         raise NotImplementedError("estimate_steps_ is " + _NEURAL_GAP)
@@ -526,7 +526,8 @@ def estimate_steps_(model: AbstractKalmanModel, data, all_params, param_groups=N
     if _p.is_lambda_kind(model.kind):
         # the λ models: block-coordinate descent over param_groups (default get_param_groups), column 1 only (:153)
         r = estimate_steps_batch(model, data, start[:, None], param_groups=param_groups,
-                                 max_group_iters=max_group_iters, tol=tol, iterations=iterations)
+                                 max_group_iters=max_group_iters, tol=tol, iterations=iterations,
+                                 full_gradient=full_gradient)
         if printing:
             print(f"✓ Best overall LL = {r['ll'][0]} from start 1")
         return r["init_c"][:, 0].copy(), float(r["ll"][0]), r["theta_c"][:, 0].copy(), 0
@@ -552,7 +553,8 @@ def estimate_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, space: 
 
 
 def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, param_groups=None,
-                         max_group_iters: int = 10, tol: float = 1e-8, iterations=None) -> dict:
+                         max_group_iters: int = 10, tol: float = 1e-8, iterations=None,
+                         full_gradient: bool = False) -> dict:
     """R independent estimate_steps! chains of a λ model (optimization.jl:137-312), one per column of Θ₀ (P×R,
     constrained, as all_params) on the window ``data[:, :T_use[r]]``, advancing in lockstep: every step of the
     block-coordinate descent (:mod:`yfm_amd.groups`) is one batched call for all unfinished chains.
@@ -563,7 +565,9 @@ def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, p
       coordinates — ``yfm_nm_block``, one launch per round for all chains;
     * group "2": L-BFGS (:mod:`yfm_amd.lbfgs`, opt2's options) on δ and Φ with value and gradient rows from
       :func:`compute_loss_grad_block`, one launch per round;
-    * groups "3" / "5" (Adam) and a "2" group holding a leading parameter raise NotImplementedError.
+    * groups "3" / "5" (Adam) and a "2" group holding a leading parameter raise NotImplementedError;
+    * ``full_gradient=True``: a "2" group may hold leading parameters (A, B, ω; γ for NS) — its rows then come from
+      the full gradient, :func:`compute_lambda_loss_grad_batch`, one launch per round as before.
 
     `iterations` caps both optimisers' budgets (None: the reference's 500 and 250).  Returns what
     :func:`estimate_batch` returns — theta_c, p, init_c (the reference's init_p), ll, status, n_evals — plus
@@ -573,19 +577,21 @@ def estimate_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, p
     if not _p.is_lambda_kind(model.kind):
         raise NotImplementedError("estimate_steps_batch is the λ models' driver; Kalman models use estimate_batch")
     return _estimate_groups(model, data, Theta0, T_use, param_groups, max_group_iters, tol, iterations,
-                            searched=isinstance(model, MSEDLambdaModel), grad="lambda_loss_grad")
+                            searched=isinstance(model, MSEDLambdaModel),
+                            grad="lambda_loss_full_grad" if full_gradient else "lambda_loss_grad", full=full_gradient)
 
 
 def _estimate_groups(model, data, Theta0, T_use, param_groups, max_group_iters, tol, iterations, searched: bool,
-                     grad: str) -> dict:
+                     grad: str, full: bool = False) -> dict:
     """The body of :func:`estimate_steps_batch` and :func:`estimate_neural_steps_batch`: they differ in whether the
-    start is searched (try_initializations_batch) and in the engine method that returns the δ/Φ gradient."""
+    start is searched (try_initializations_batch) and in the engine method that returns the gradient — the δ/Φ rows,
+    or with `full` all P rows, so that no row counts as a leading one an L-BFGS group must not hold."""
     kind = model.kind
     Th = np.asarray(Theta0, dtype=np.float64)
     Th = Th.reshape(Th.shape[0], -1)
     P, R = Th.shape
     groups = get_param_groups(model, () if param_groups is None else param_groups)
-    n_lead = P - model.base.M * (model.base.M + 1)
+    n_lead = 0 if full else P - model.base.M * (model.base.M + 1)  # rows without a gradient
     _groups.check_groups(groups, n_lead)  # before any launch
     tu = None if T_use is None else np.ascontiguousarray(np.broadcast_to(T_use, (R,)), dtype=np.int32)
     if searched:
@@ -649,12 +655,27 @@ def estimate_neural_steps_(model: AbstractKalmanModel, data, all_params, param_g
 def compute_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
     """Batched compute_loss with its gradient — what estimate!'s TwiceDifferentiable(...; autodiff=:forward)
     evaluates (optimization.jl:367): (−loglik[B], −∂loglik/∂θ[P, B]) for every unconstrained θ_b, the
-    reference's loss sign.  DNS with N ≤ 64 (:meth:`Engine.loglik_grad`) and TVλ (:meth:`Engine.tvl_loglik_grad`);
-    NaN gradient columns as there."""
+    reference's loss sign.  DNS with N ≤ 64 (:meth:`Engine.loglik_grad`), TVλ (:meth:`Engine.tvl_loglik_grad`) and
+    the λ models (:meth:`Engine.lambda_loss_full_grad`: −get_loss and its full gradient); NaN gradient columns as
+    there."""
     eng = _engine(model, data)
-    fn = eng.tvl_loglik_grad if model.kind == _p.KIND_TVL else eng.loglik_grad
+    if _p.is_lambda_kind(model.kind):
+        fn = eng.lambda_loss_full_grad
+    else:
+        fn = eng.tvl_loglik_grad if model.kind == _p.KIND_TVL else eng.loglik_grad
     ll, g = fn(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
     return -ll, -g
+
+
+def compute_lambda_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
+    """Batched compute_loss of a λ model with its gradient over every row of θ — what an L-BFGS group of
+    estimate_steps! that holds leading parameters evaluates: (−loss[B], −∂loss/∂θ[P, B]) for every unconstrained θ_b
+    (:meth:`Engine.lambda_loss_full_grad`).  NaN gradient columns where the loss is −Inf or a tangent is not finite."""
+    if not _p.is_lambda_kind(model.kind):
+        raise NotImplementedError("the full loss gradient is the λ models'; Kalman models use compute_loss_grad_batch, "
+                                  "neural models compute_neural_loss_grad_block")
+    loss, g = _engine(model, data).lambda_loss_full_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
+    return -loss, -g
 
 
 def compute_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_use=None):

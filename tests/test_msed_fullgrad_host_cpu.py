@@ -3,7 +3,8 @@ kernel runs, driven by get_loss_fullgrad) compiled for the host (tests/msed_full
 -ffp-contract=off, -fsanitize=address,undefined, a stand-alone program) against tests/golden/msed_fullgrad/: central
 differences of the 40-digit restatement over all P rows.  Every fixture candidate, in both parameter spaces, passes
 max_i |g − g_fd| ≤ 1e-9·‖g_fd‖∞ + e_fd; the loss is get_loss's and the last 12 rows are get_loss_grad's, bit for bit;
-a −Inf loss comes with P NaNs, exactly where the fixture has them."""
+a −Inf loss comes with P NaNs, exactly where the fixture has them.  The N = 30, T = 600 cases of msed_fullgrad_long.npz
+(make_msed_fullgrad_long.py) run through the same program."""
 from __future__ import annotations
 
 import subprocess
@@ -16,6 +17,7 @@ from conftest import GOLDEN, ROOT
 
 sys.path.insert(0, str(GOLDEN / "msed_fullgrad"))
 import make_msed_fullgrad as MF  # noqa: E402
+import make_msed_fullgrad_long as MFL  # noqa: E402
 
 REL = 1e-9
 
@@ -90,6 +92,27 @@ def test_host_full_gradient_matches_truth(harness, cases, tmp_path, name, space)
     assert np.array_equal(np.isneginf(loss), np.isneginf(want))
     f = np.isfinite(want)
     assert np.all(np.abs(loss[f] - want[f]) <= 1e-9 * np.abs(want[f]))  # the project's parity bar
+    check_gradient(g, c[f"{name}_g_fd_s{space}"], c[f"{name}_e_fd_s{space}"], loss, f"{name} space {space}")
+
+
+@pytest.mark.parametrize("space", [0, 1])
+@pytest.mark.parametrize("name", MFL.case_names())
+def test_host_full_gradient_matches_truth_at_estimation_length(harness, tmp_path, name, space):
+    """The same assertions on msed_fullgrad_long.npz (make_msed_fullgrad_long.py): N = 30, T = 600, and for two kinds
+    the windows 300 and 600 over a missing column 450 (the long one is −Inf with no gradient)."""
+    c = MFL.load_cases()
+    kind = int(name[1])
+    Th = c[f"{name}_theta"] if space == 0 else c[f"{name}_theta_c"]
+    loss, loss_plain, un, g, g12 = run_host(harness, tmp_path, kind, c[f"{name}_Y"], c[f"{name}_maturities"], Th,
+                                            c[f"{name}_T_use"], space)
+    assert same_bits(loss, loss_plain), (loss, loss_plain)
+    assert not un.any()
+    fin = np.isfinite(loss)
+    assert same_bits(g[-12:, fin], g12[:, fin])
+    want = c[f"{name}_loss_s{space}"]
+    assert np.array_equal(np.isneginf(loss), np.isneginf(want))
+    f = np.isfinite(want)
+    assert np.all(np.abs(loss[f] - want[f]) <= 1e-9 * np.abs(want[f]))
     check_gradient(g, c[f"{name}_g_fd_s{space}"], c[f"{name}_e_fd_s{space}"], loss, f"{name} space {space}")
 
 

@@ -3,6 +3,9 @@ compiled for the host (tests/tvl_grad_host_check.cpp, -ffp-contract=off) and run
 case of the fixture (tests/golden/tvl_grad), held to the GPU test's rule:
 
     max_i |g − g_fd| ≤ 1e-9·‖g_fd‖∞ + e_fd[b]   for every compared candidate, at least 75% compared.
+
+The estimation-length cases of tvl_grad_long_cases.npz (T = 200 and 600, make_tvl_grad_long.py) run through the same
+program.
 """
 from __future__ import annotations
 
@@ -16,6 +19,7 @@ from conftest import GOLDEN, ROOT
 
 sys.path.insert(0, str(GOLDEN / "tvl_grad"))
 import make_tvl_grad as MG  # noqa: E402
+import make_tvl_grad_long as ML  # noqa: E402
 
 REL = 1e-9
 POS = (0, 1, 3, 6, 10)     # σ² and the diagonal of U: exp
@@ -79,6 +83,16 @@ def check_case(c, ll, g):
 @pytest.mark.parametrize("name", MG.CASE_NAMES)
 def test_host_gradient_matches_truth_differences(harness, cases, tmp_path, name):
     c = cases[name]
+    ll, g = run_host(harness, tmp_path, c["Y"], c["maturities"], c["Theta"], c["T_use"])
+    check_case(c, ll, g)
+
+
+@pytest.mark.parametrize("name", ML.CASE_NAMES)
+def test_host_gradient_matches_truth_differences_at_estimation_length(harness, tmp_path, name):
+    """The same rule on tvl_grad_long_cases.npz (make_tvl_grad_long.py): T = 200 and 600, windows over a NaN column
+    late in the panel."""
+    c = ML.load_cases()[name]
+    print(f"case {name}: compared {int(c['compared'].sum())}/{c['compared'].size}")
     ll, g = run_host(harness, tmp_path, c["Y"], c["maturities"], c["Theta"], c["T_use"])
     check_case(c, ll, g)
 

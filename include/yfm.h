@@ -380,6 +380,40 @@ int yfm_neural_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_sp
                                       int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                       void* hip_stream);
 
+/* The neural kinds' loss WITH its gradient with respect to EVERY row of θ: yfm_lambda_loss_fullgrad_batch(_device) for
+ * YFM_MODEL_NNS, NNS_ANCHORED and the 24 score-driven NNS kinds, with its arguments, ordering and synchrony rules;
+ * grad_out is P×B column-major in the order of θ (P = 30 for the static kinds, 34 / 42 / 66 for the score-driven kinds
+ * with a B, 32 / 36 / 48 for the random-walk kinds).
+ *   What it is: the derivative of the function get_loss computes (filter.jl:209-243, K = 1) with respect to every row
+ * of θ, in the space the caller passed — what a finite-difference L-BFGS on get_loss converges to.  It is NOT the
+ * reference's own dual-number path, which cannot serve as the definition: get_grad_gamma! strips the outer tangent of
+ * β (ForwardDiff.value.(beta), filter.jl:175) and set_params! writes into Float arrays.  The leading rows (A, B, ω;
+ * A, ω for the random-walk kinds; γ for the static kinds) come from a reverse (adjoint) sweep over the score recursion,
+ * whose cost does not depend on the number of rows: a forward sweep records the γ — and, for the scaled kinds, the
+ * score's second-moment average — every step enters with, and a backward sweep rebuilds each step from its record
+ * and applies the transposes of both OLS fits, of the update and of the score's Jacobian (a Hessian–vector product of
+ * the loadings' second derivatives plus the OLS transpose of the β the score is taken at).  The value path is
+ * untouched.  The unconstrained space multiplies row A by A and row B by B(1 − B); a missing first column is a
+ * prediction-only step, γ₁ = ν + B∘γ₀, with no β adjoint.
+ *   Bits: loss_out[b] is bitwise what yfm_loglik_batch returns, and rows P−12 … P−1 of an available gradient are
+ * bitwise yfm_neural_loss_grad_batch's.  A candidate's P + 1 outputs do not depend on the batch it sits in, on the
+ * lanes per candidate, or on how the launch is split into chunks: the trajectory workspace is capped at 1 GiB (the
+ * environment variable YFM_NNS_TRAJ_BYTES overrides the cap in bytes, with a floor of one block's candidates) and a
+ * larger batch runs as several chunks of whole blocks on the same stream.  A window that compares no column
+ * (T_use = 1) gives the loss yfm_loglik_batch gives and an exactly zero gradient.
+ *   NaN rule: grad_out[:, b] is NaN in all P rows where (1) loss_out[b] is −Inf (n_neg_inf); (2) the loss is finite
+ * but an adjoint or an accumulator is not finite — a scaled kind's average that is exactly 0 in a component (its
+ * root is 0), overflow of a hidden unit.  Case (2) is counted by yfm_last_batch_grad_unavailable.
+ *   Every other kind returns YFM_EUNSUPPORTED, and so does a panel with fewer than 4 maturities or more than the two
+ * sweeps' maximum, 512 (below the loss kernel's 1024: the backward sweep's LDS record takes the room).
+ * yfm_lambda_loss_fullgrad_batch keeps refusing the neural kinds.  Additive: YFM_ABI_VERSION stays 5; a library that
+ * has the symbols has the feature. */
+int yfm_neural_loss_fullgrad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                                   const int* T_use, double* loss_out, double* grad_out);
+int yfm_neural_loss_fullgrad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                          int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                                          void* hip_stream);
+
 /* One Optim.NelderMead run per chain on a block of coordinates — what estimate_steps! does for a parameter group
  * that uses opt1 (optimization.jl:218-247 with :442-451, :479: NelderMead, `iterations`, g_tol), without the outer
  * group loop, the sanitising or the rescaling around it (:157-184, :249-281), which stay with the caller.  p is

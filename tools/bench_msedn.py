@@ -15,6 +15,9 @@ restatement (tests/msedn_reference.py) timed on a few candidates and quoted per 
       candidates (its grid) and at 4,080 (17 of them on each of the 240 windows);
   (f) (asked for by name: --cases f) the wall clock of the 240-window rolling re-estimation of 1SD-NNS with its default
       groups (estimate_neural_steps_batch), with evaluations and rounds by group.
+  (g) (--cases g) the loss launch, the δ/Φ launch and the full-gradient launch (yfm_neural_loss_fullgrad_batch_device:
+      the forward sweep with its trajectory and the adjoint sweep) alternating, for NNS, 1SD-NNS, 3SD-NNS and 3SSD-NNS
+      at 257 candidates and at 4,080 (17 on each of the 240 windows): full ÷ loss per kind.
 Prints one JSON line.  Not part of bench.py.
 """
 from __future__ import annotations
@@ -57,6 +60,39 @@ def numpy_ms_per_candidate(kind, mats, Y, Th, space, n=3):
     for b in range(n):
         R.get_loss(kind, mats, Y, Th[:, b], space, R.FLOAT)
     return 1e3 * (time.perf_counter() - t0) / n
+
+
+def alternating_stats(eng, kind, Th, space, tu, reps, warmup):
+    """The loss, δ/Φ and full-gradient launches of one batch, timed in turn within every repetition."""
+    stream = torch.cuda.current_stream()
+    Pn, B = Th.shape
+    d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
+    d_tu = None if tu is None else torch.from_numpy(np.ascontiguousarray(tu, dtype=np.int32)).cuda()
+    tup = None if d_tu is None else d_tu.data_ptr()
+    d_out = torch.empty(B, dtype=torch.float64, device="cuda")
+    d_g = torch.empty((B, Pn), dtype=torch.float64, device="cuda")
+    runs = {"loss": lambda: eng.loglik_device(kind, d_th.data_ptr(), Pn, B, d_out.data_ptr(), space=space,
+                                              d_T_use=tup, stream=stream.cuda_stream),
+            "delta_phi": lambda: eng.neural_loss_grad_device(kind, d_th.data_ptr(), Pn, B, d_out.data_ptr(),
+                                                             d_g.data_ptr(), space=space, d_T_use=tup,
+                                                             stream=stream.cuda_stream),
+            "full": lambda: eng.neural_loss_full_grad_device(kind, d_th.data_ptr(), Pn, B, d_out.data_ptr(),
+                                                             d_g.data_ptr(), space=space, d_T_use=tup,
+                                                             stream=stream.cuda_stream)}
+    for _ in range(warmup):
+        for run in runs.values():
+            run()
+    torch.cuda.synchronize()
+    t = {k: [] for k in runs}
+    for _ in range(reps):
+        for k, run in runs.items():
+            t[k].append(timed(run, stream))
+    out = {k: {"ms_median": statistics.median(v), "ms_min": min(v), "ms_max": max(v)} for k, v in t.items()}
+    out["B"] = B
+    out["finite"] = int(np.isfinite(d_g.cpu().numpy()).all(axis=1).sum())
+    out["full_over_loss"] = out["full"]["ms_median"] / out["loss"]["ms_median"]
+    out["delta_phi_over_loss"] = out["delta_phi"]["ms_median"] / out["loss"]["ms_median"]
+    return out
 
 
 def grad_launch_stats(eng, kind, Th, space, tu, reps, warmup):
@@ -148,6 +184,14 @@ def main():
             "rounds_by_group": {k: int(v) for k, v in est["rounds_by_group"].items()},
             "group_iters_max": int(est["group_iters"].max()), "group_iters_mean": float(est["group_iters"].mean()),
             "status_ok": int((est["status"] == 0).sum()), "ll_mean": float(np.mean(est["ll"]))}
+    if "g" in args.cases:
+        for name in ("NNS", "1SD-NNS", "3SD-NNS", "3SSD-NNS"):
+            kind = next(k for k in P.NEURAL_KINDS if P.KIND_NAMES[k] == name)
+            G = grid(kind) if name != "NNS" else np.asfortranarray(
+                P.transform_params(kind, S.theta_batch(kind, 257, seed=5, bad_frac=0.0)))
+            for tag, Th, tu in (("257", G, None),
+                                ("4080", np.asfortranarray(np.tile(G[:, :17], (1, 240))), np.repeat(windows, 17))):
+                res["cases"][f"g_fullgrad_{name}_{tag}"] = alternating_stats(eng, kind, Th, 1, tu, args.reps, args.warmup)
     print(json.dumps(res), flush=True)
 
 

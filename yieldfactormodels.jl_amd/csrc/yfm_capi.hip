@@ -73,6 +73,7 @@ struct yfm::Workspace {
   DevBuf defer;       // candidates handed from the FP64 fixed-loading kernels to the dd kernel
   DevBuf scratch_fd;  // their double-double records (yfm_fixedz_dd.hip)
   DevBuf grad;        // gradient staging of the host-pointer gradient calls (yfm_loglik_grad_batch, yfm_lambda_loss_grad_batch)
+  DevBuf nns_traj;    // the neural full gradient's trajectory: the forward sweep's records of one chunk of candidates
   // allocate and zero the two counter banks
   hipError_t init() {
     const size_t nb = 2 * yfm::kFlagsPerBank * sizeof(unsigned int);
@@ -288,7 +289,7 @@ struct Launch {
   int share = 1;           // launches of this size the caller keeps in flight at once (yfm::loglik_device_ws)
   const yfm::MsedRecord* msed_rec = nullptr;  // λ models: the trajectory outputs this launch writes (nullptr: the loss)
   double* msed_grad = nullptr;  // λ and neural models: 12×B device, ∂loss/∂(δ, Φ) written with the loss
-  double* msed_fullgrad = nullptr;  // λ models: P×B device, ∂loss/∂θ written with the loss
+  double* msed_fullgrad = nullptr;  // λ and neural models: P×B device, ∂loss/∂θ written with the loss
 };
 
 // The plain log-likelihood launch, in the argument order of yfm_loglik_batch_device.
@@ -351,7 +352,16 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
   hipError_t e;
   if (yfm::msed_kind(q.kind)) {
     const int lanes = yfm::msed_lanes_for(B);
-    e = q.msed_fullgrad ? yfm::launch_msed_fullgrad(q.kind, a, lanes, q.msed_fullgrad)
+    double* nns_traj = nullptr;
+    if (q.msed_fullgrad && yfm::msedn_kind(q.kind)) {
+      if (const size_t tb = yfm::msedn_fullgrad_traj_bytes(q.kind, B, a.T, lanes)) {
+        YFM_HIP_CHECK(w.nns_traj.ensure(tb));
+        nns_traj = static_cast<double*>(w.nns_traj.p);
+      }
+    }
+    e = q.msed_fullgrad && yfm::msedn_kind(q.kind)
+            ? yfm::launch_msedn_fullgrad(q.kind, a, lanes, q.msed_fullgrad, nns_traj)
+        : q.msed_fullgrad ? yfm::launch_msed_fullgrad(q.kind, a, lanes, q.msed_fullgrad)
         : q.msed_grad  ? yfm::launch_msed_grad(q.kind, a, lanes, q.msed_grad)
         : q.msed_rec ? yfm::launch_msed_record(q.kind, a, lanes, *q.msed_rec)
                      : yfm::launch_msed(q.kind, a, lanes);
@@ -493,6 +503,18 @@ int check_neural_grad(yfm_ctx* ctx, int kind, int space, int P, int B) {
   return YFM_OK;
 }
 
+// The neural full-gradient entry points' model check: the 26 kinds of yfm_msedn.hip, at the N its two sweeps take.
+int check_neural_fullgrad(yfm_ctx* ctx, int kind, int space, int P, int B) {
+  if (state_dim(kind) >= 0 && !yfm::msedn_kind(kind))
+    return set_error(YFM_EUNSUPPORTED, "yfm_neural_loss_fullgrad_batch is built for the neural kinds only (model_kind "
+                     "%d: use yfm_lambda_loss_fullgrad_batch, yfm_loglik_grad_batch or yfm_tvl_loglik_grad_batch)", kind);
+  if (int r = check_batch(ctx, kind, space, P, B)) return r;
+  if (ctx->N > yfm::msedn_fullgrad_max_n())
+    return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the neural full-gradient kernels' %d", ctx->N,
+                     yfm::msedn_fullgrad_max_n());
+  return YFM_OK;
+}
+
 // The loglik launch q on the context's own workspace, then the tangent kernel on the same stream: it reads the
 // logliks q.out and (DNS) that launch's deferral list and adds n_grad_unavailable to its counter bank.
 int launch_grad(yfm_ctx* ctx, const Launch& q, double* d_grad) {
@@ -604,7 +626,7 @@ int loss_grad_batch(GradCheck check, yfm_ctx* ctx, int model_kind, int param_spa
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
   Launch q;
   if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  const size_t rows = full ? (size_t)P : (size_t)yfm::kMsedGrad;  // full: every row of θ (the λ kinds)
+  const size_t rows = full ? (size_t)P : (size_t)yfm::kMsedGrad;  // full: every row of θ
   const size_t gb = sizeof(double) * rows * (size_t)(B > 0 ? B : 1);
   YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
   double* const d_grad = static_cast<double*>(ctx->own.grad.p);
@@ -910,6 +932,19 @@ int yfm_neural_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_sp
                                       void* hip_stream) {
   return loss_grad_batch_device(check_neural_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
                                 d_grad_out, hip_stream);
+}
+
+int yfm_neural_loss_fullgrad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                                   const int* T_use, double* loss_out, double* grad_out) {
+  return loss_grad_batch(check_neural_fullgrad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out,
+                         true);
+}
+
+int yfm_neural_loss_fullgrad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                          int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
+                                          void* hip_stream) {
+  return loss_grad_batch_device(check_neural_fullgrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use,
+                                d_loss_out, d_grad_out, hip_stream, true);
 }
 
 int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n) {

@@ -170,6 +170,16 @@ hipError_t launch_msedn(int kind, const LaunchArgs& a, int lanes, const MsedReco
 // msedn_min_n ≤ N ≤ msedn_grad_max_n.
 int msedn_grad_max_n();
 hipError_t launch_msedn_grad(int kind, const LaunchArgs& a, int lanes, double* grad);
+// The loss with all P derivatives for these kinds (yfm_msedn_adj.hip; grad: P×B column-major device doubles): a forward
+// sweep that is launch_msedn_grad's loop — the loss and the last 12 rows are its bits — and records the γ (and e) every
+// step enters with into traj, then an adjoint sweep backwards over those records for the leading rows (A, B, ω; γ for
+// the static kinds).  NaN in all P rows where the loss is −Inf (a.flags[1]) and where an adjoint is not finite
+// (a.flags[5]).  traj: msedn_fullgrad_traj_bytes(kind, B, T, lanes) bytes (0 for the static kinds: nullptr) — the
+// records of one chunk of whole blocks, at most 1 GiB (YFM_NNS_TRAJ_BYTES overrides the cap, floor one block); a
+// larger batch runs as several chunks on a.stream.  msedn_min_n ≤ N ≤ msedn_fullgrad_max_n.
+int msedn_fullgrad_max_n();
+size_t msedn_fullgrad_traj_bytes(int kind, int B, int T, int lanes);
+hipError_t launch_msedn_fullgrad(int kind, const LaunchArgs& a, int lanes, double* grad, double* traj);
 // Trajectory outputs (yfm_predict.hip) from a recorded state trajectory.
 struct PredictArgs {
   int kind, M, L, N, P, B, T;

@@ -164,6 +164,21 @@ function neural_loss_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64
     loss, grad
 end
 
+"The neural models' loss and its gradient over every row of Θ: (loss[B], grad[P, B]) with lambda_loss_fullgrad_batch's
+layout, spaces and NaN columns.  The leading rows (A, B, ω; γ for the static kinds) come from an adjoint sweep over the
+score recursion — the derivative of the function get_loss computes; the last 12 rows are neural_loss_grad_batch's bit
+for bit (yfm.h).  Binds yfm_neural_loss_fullgrad_batch."
+function neural_loss_fullgrad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,
+                                    T_use::Union{Nothing,Vector{Cint}} = nothing)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    loss, grad = Vector{Float64}(undef, B), Matrix{Float64}(undef, P, B)
+    GC.@preserve Θ loss grad T_use check(@ccall LIB.yfm_neural_loss_fullgrad_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, loss::Ptr{Cdouble},
+        grad::Ptr{Cdouble})::Cint)
+    loss, grad
+end
+
 "One Optim.NelderMead run (opt1, optimization.jl:442-451) per column of p (P×R, unconstrained) on the coordinates
 `inds` (1-based, as findall(param_groups .== g) gives them, optimization.jl:229), the others held: what estimate_steps!
 does for one NelderMead group of one group iteration (:218-247), all chains sharing one launch per round.  Returns

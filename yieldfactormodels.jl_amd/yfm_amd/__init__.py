@@ -14,6 +14,7 @@ from .models import (MSEDLambdaModel, StaticLambdaModel, compute_lambda_loss_gra
                      get_param_groups, try_initializations, try_initializations_batch)
 from .models import MSEDNeuralModel, StaticNeuralModel, create_neural_model
 from .models import compute_neural_loss_grad_block, estimate_neural_steps_, estimate_neural_steps_batch
+from .models import compute_neural_loss_fullgrad_batch, estimate_neural_, estimate_neural_lbfgs_batch
 from .params import KIND_NNS, KIND_NNS_ANCHORED, NEURAL_KINDS, is_neural_kind, neural_kind
 from .engine import Engine, get_engine
 from .driver import load_initial_parameters_, run, run_neural_estimation_
@@ -30,4 +31,5 @@ __all__ = [
     "compute_loss_grad_block", "compute_lambda_loss_grad_batch", "estimate_steps_batch", "StaticNeuralModel", "MSEDNeuralModel", "create_neural_model", "KIND_NNS",
     "KIND_NNS_ANCHORED", "NEURAL_KINDS", "is_neural_kind", "neural_kind",
     "compute_neural_loss_grad_block", "estimate_neural_steps_", "estimate_neural_steps_batch", "run_neural_estimation_",
+    "compute_neural_loss_fullgrad_batch", "estimate_neural_lbfgs_batch", "estimate_neural_",
 ]

@@ -67,6 +67,10 @@ SIGNATURES = {
                                                   _D, _D]),
     "yfm_neural_loss_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
                                                          ctypes.c_int, _V, _V, _V, _V]),
+    "yfm_neural_loss_fullgrad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int,
+                                                      _I, _D, _D]),
+    "yfm_neural_loss_fullgrad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
+                                                             ctypes.c_int, _V, _V, _V, _V]),
     "yfm_tvl_loglik_grad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I,
                                                  _D, _D]),
     "yfm_tvl_loglik_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,

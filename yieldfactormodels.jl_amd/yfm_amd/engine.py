@@ -220,6 +220,30 @@ class Engine:
                                                               ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
                                                               ctypes.c_void_p(stream) if stream else None))
 
+    def neural_loss_full_grad(self, kind: int, theta, space: int = 0, T_use=None):
+        """:meth:`lambda_loss_full_grad` for a neural kind (include/yfm.h yfm_neural_loss_fullgrad_batch): (loss[B],
+        grad[P, B]) — the loss :meth:`loglik`'s bit for bit, the leading rows (A, B, ω; γ for the static kinds) from an
+        adjoint sweep over the score recursion, the last 12 the rows of :meth:`neural_loss_grad`, bit for bit.  A
+        candidate's gradient is NaN where its loss is −Inf, and where an adjoint is not finite
+        (:meth:`last_grad_unavailable`)."""
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        loss = np.empty(B, dtype=np.float64)
+        grad = np.empty((P, B), dtype=np.float64, order="F")
+        _lib.check(self.lib.yfm_neural_loss_fullgrad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                                           _lib.iptr(self._tuse(T_use, B)), _lib.dptr(loss),
+                                                           _lib.dptr(grad)))
+        return loss, grad
+
+    def neural_loss_full_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int,
+                                     space: int = 0, d_T_use: int | None = None, stream: int | None = None) -> None:
+        """Device-pointer variant of :meth:`neural_loss_full_grad` (raw addresses; d_grad: P×B column-major);
+        asynchronous on ``stream``."""
+        _lib.check(self.lib.yfm_neural_loss_fullgrad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P,
+                                                                  B, ctypes.c_void_p(d_T_use) if d_T_use else None,
+                                                                  ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
+                                                                  ctypes.c_void_p(stream) if stream else None))
+
     def filter_states(self, kind: int, theta, space: int = 0, T_use=None):
         """Returns (loglik[B], beta[M, T-1, B], P[M, M, T-1, B]) — a_{t+1|t}, P_{t+1|t} after each filter! call."""
         Th = np.asfortranarray(np.atleast_2d(np.asarray(theta, dtype=np.float64).T).T)

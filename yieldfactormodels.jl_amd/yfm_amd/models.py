@@ -170,8 +170,10 @@ class MSEDLambdaModel(AbstractKalmanModel):
 
 _NEURAL_GAP = ("the λ and Kalman models' entry point; the neural kinds (NNS, …SD-NNS) are estimated through names of "
                "their own: estimate_neural_steps_ / estimate_neural_steps_batch (groups \"1\" and \"2\"), "
-               "compute_neural_loss_grad_block (the δ/Φ gradient) and driver.run_neural_estimation_; the L-BFGS "
-               "multistart over every parameter and the Kalman Nelder–Mead driver are not built for them")
+               "compute_neural_loss_grad_block (the δ/Φ gradient), compute_neural_loss_fullgrad_batch, "
+               "estimate_neural_lbfgs_batch / estimate_neural_ (the L-BFGS multistart over every parameter) and "
+               "driver.run_neural_estimation_; under this name the L-BFGS multistart and the Kalman Nelder–Mead driver "
+               "are not built for them")
 
 
 _NEURAL_RESTARTS = ("try_initializations of the static neural models draws its restarts from Julia's seeded generator "
@@ -626,17 +628,21 @@ def _estimate_groups(model, data, Theta0, T_use, param_groups, max_group_iters, 
 
 
 def estimate_neural_steps_batch(model: AbstractKalmanModel, data, Theta0, T_use=None, param_groups=None,
-                                max_group_iters: int = 10, tol: float = 1e-8, iterations=None) -> dict:
+                                max_group_iters: int = 10, tol: float = 1e-8, iterations=None,
+                                full_gradient: bool = False) -> dict:
     """:func:`estimate_steps_batch` for the neural kinds (a model from :func:`create_neural_model`): the same
     arguments, descent and returned dict.  The start is :func:`try_initializations_batch` for the score-driven kinds
     (the 256-trial grid, 16 for the random-walk kinds); NNS and NNS-Anchored keep their start, as the reference's
     ``max_tries = 0`` does (optimization.jl:37-43).  Group "1" (A, B, ω; γ for the static kinds: 18–54 coordinates)
-    is ``yfm_nm_block``, group "2" is L-BFGS on value and gradient rows from ``yfm_neural_loss_grad_batch``."""
+    is ``yfm_nm_block``, group "2" is L-BFGS on value and gradient rows from ``yfm_neural_loss_grad_batch``.
+    ``full_gradient=True``: a "2" group may hold leading parameters — its rows then come from the full gradient,
+    :func:`compute_neural_loss_fullgrad_batch`, one launch per round as before."""
     if not _p.is_neural_kind(model.kind):
         raise NotImplementedError("estimate_neural_steps_batch is the neural models' driver; λ models use "
                                   "estimate_steps_batch, Kalman models estimate_batch")
     return _estimate_groups(model, data, Theta0, T_use, param_groups, max_group_iters, tol, iterations,
-                            searched=isinstance(model, MSEDNeuralModel), grad="neural_loss_grad")
+                            searched=isinstance(model, MSEDNeuralModel),
+                            grad="neural_loss_full_grad" if full_gradient else "neural_loss_grad", full=full_gradient)
 
 
 def estimate_neural_steps_(model: AbstractKalmanModel, data, all_params, param_groups=None, max_group_iters: int = 10,
@@ -700,6 +706,17 @@ def compute_neural_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_us
     return -loss, -g
 
 
+def compute_neural_loss_fullgrad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
+    """Batched compute_loss of a neural model with its gradient over every row of θ — what an L-BFGS over all
+    parameters evaluates: (−loss[B], −∂loss/∂θ[P, B]) for every unconstrained θ_b
+    (:meth:`Engine.neural_loss_full_grad`).  NaN gradient columns where the loss is −Inf or an adjoint is not finite."""
+    if not _p.is_neural_kind(model.kind):
+        raise NotImplementedError("compute_neural_loss_fullgrad_batch is the neural models'; λ models use "
+                                  "compute_lambda_loss_grad_batch, Kalman models compute_loss_grad_batch")
+    loss, g = _engine(model, data).neural_loss_full_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
+    return -loss, -g
+
+
 def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 1, T_use=None, **opts) -> dict:
     """One L-BFGS chain of estimate! (optimization.jl:329-410) per column of Θ₀ (P×R; constrained by default, as
     all_params), all chains advancing in lockstep with one gradient launch per round (:mod:`yfm_amd.lbfgs`;
@@ -707,19 +724,25 @@ def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 
     p (P×R unconstrained optimum), init_c (P×R: the start, constrained), ll (R), ll0 (R: the loglik at the
     start), status (R: lbfgs status; 0 = converged), iterations (R), n_evals, rounds.  ``T_use`` (an int, or one per
     column) runs chain r on the window ``data[:, :T_use[r]]``; None is the whole panel."""
-    from . import lbfgs as _lbfgs
     if _p.is_neural_kind(model.kind):
         raise NotImplementedError("estimate_ (the L-BFGS multistart) is " + _NEURAL_GAP)
+    return _lbfgs_chains(model, data, Theta0, space, T_use, compute_loss_grad_batch, opts)
+
+
+def _lbfgs_chains(model, data, Theta0, space, T_use, loss_grad, opts) -> dict:
+    """The body of :func:`estimate_lbfgs_batch` and :func:`estimate_neural_lbfgs_batch`: they differ in the function
+    that returns (−loss, −gradient) over every row of θ."""
+    from . import lbfgs as _lbfgs
     Th = np.asarray(Theta0, dtype=np.float64)
     if Th.ndim == 1:
         Th = Th[:, None]
     X0 = Th if space == _p.SPACE_UNCONSTRAINED else _p.untransform_params(model.kind, Th)
     tu = None if T_use is None else np.ascontiguousarray(np.broadcast_to(T_use, (X0.shape[1],)), dtype=np.int32)
-    ll0 = -compute_loss_grad_batch(model, data, X0, T_use=tu)[0]
+    ll0 = -loss_grad(model, data, X0, T_use=tu)[0]
     if tu is None:
-        r = _lbfgs.minimize_batch(lambda X: compute_loss_grad_batch(model, data, X), X0, **opts)
+        r = _lbfgs.minimize_batch(lambda X: loss_grad(model, data, X), X0, **opts)
     else:  # finished chains drop out of the batch: every column brings its chain's window
-        r = _lbfgs.minimize_batch(lambda X, idx: compute_loss_grad_batch(model, data, X, T_use=tu[np.asarray(idx)]),
+        r = _lbfgs.minimize_batch(lambda X, idx: loss_grad(model, data, X, T_use=tu[np.asarray(idx)]),
                                   X0, with_index=True, **opts)
     return dict(theta_c=np.asfortranarray(_p.transform_params(model.kind, r["x"])), p=r["x"],
                 init_c=np.asfortranarray(_p.transform_params(model.kind, X0)), ll=-r["f"], ll0=ll0,
@@ -733,10 +756,15 @@ def estimate_(model: AbstractKalmanModel, data, all_params, printing: bool = Fal
     ir = 0 if that chain converged else 1.  Raises :class:`EstimationError` where the reference throws:
     compute_loss throws at a start (singular initialize_filter), or no start ends with ll > −Inf (the
     reference then indexes its results with best_j = 0)."""
+    return _best_start(estimate_lbfgs_batch, model, data, all_params, printing, opts)
+
+
+def _best_start(chains, model, data, all_params, printing, opts):
+    """The body of :func:`estimate_` and :func:`estimate_neural_`: the multistart over `chains` and its best start."""
     A = np.asarray(all_params, dtype=np.float64)
     if A.ndim == 1:
         A = A[:, None]
-    r = estimate_lbfgs_batch(model, data, A, space=_p.SPACE_CONSTRAINED, **opts)
+    r = chains(model, data, A, space=_p.SPACE_CONSTRAINED, **opts)
     if np.isnan(r["ll0"]).any():
         raise EstimationError("compute_loss threw at a starting point (singular initialize_filter)")
     ll = np.where(np.isnan(r["ll"]), -np.inf, r["ll"])
@@ -746,3 +774,22 @@ def estimate_(model: AbstractKalmanModel, data, all_params, printing: bool = Fal
     if printing:
         print(f"✓ Best LL = {r['ll'][j]} from starting point {j + 1}")
     return r["init_c"][:, j].copy(), float(r["ll"][j]), r["theta_c"][:, j].copy(), 0 if r["status"][j] == 0 else 1
+
+
+def estimate_neural_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 1, T_use=None, **opts) -> dict:
+    """:func:`estimate_lbfgs_batch` for a model from :func:`create_neural_model`: one L-BFGS chain over all P rows per
+    column of Θ₀, on value and gradient from :func:`compute_neural_loss_fullgrad_batch` (one launch per round); the
+    same arguments, `opts` and returned dict."""
+    if not _p.is_neural_kind(model.kind):
+        raise NotImplementedError("estimate_neural_lbfgs_batch is the neural models'; λ and Kalman models use "
+                                  "estimate_lbfgs_batch")
+    return _lbfgs_chains(model, data, Theta0, space, T_use, compute_neural_loss_fullgrad_batch, opts)
+
+
+def estimate_neural_(model: AbstractKalmanModel, data, all_params, printing: bool = False, **opts):
+    """:func:`estimate_` for a model from :func:`create_neural_model`: the multistart L-BFGS over the columns of
+    all_params through :func:`estimate_neural_lbfgs_batch` → (init_params, ll, best_params, ir), with
+    :class:`EstimationError` as there."""
+    if not _p.is_neural_kind(model.kind):
+        raise NotImplementedError("estimate_neural_ is the neural models'; λ and Kalman models use estimate_")
+    return _best_start(estimate_neural_lbfgs_batch, model, data, all_params, printing, opts)

@@ -414,6 +414,45 @@ int yfm_neural_loss_fullgrad_batch_device(yfm_ctx* ctx, int model_kind, int para
                                           int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                           void* hip_stream);
 
+/* Score series, information matrices and the Hessian of the DNS log-likelihood — what standard errors of a
+ * maximum-likelihood estimate are made of.  AN EXTENSION: the reference has no counterpart (estimate! in
+ * optimization.jl returns the optimum and its loss, no covariance), so the definitions below are this library's own.
+ *   get_loss over nobs = T_use[b] columns is ll = Σ_{k=1}^{nobs−2} ℓ_k, ℓ_k the term added after column k (0-based)
+ * is processed; at a NaN column it is the stale term, added again as the reference does (filter.jl:195).
+ *   Score series: S[d, k, b] = ∂ℓ_k/∂θ_d for 1 ≤ k ≤ nobs_b − 2 and exactly 0.0 elsewhere; scores_out is
+ * P × (T − 1) × B column-major (Julia's S[:, k, b], k 0-based here), θ in the space passed (the unconstrained space
+ * through the chain factors of the transform).  Σ_k S[:, k, b] is yfm_loglik_grad_batch's gradient up to the order of
+ * the sum.  loglik_out is bitwise yfm_loglik_batch's.
+ *   OPG / HAC matrix: Γ_ℓ = Σ_k s_k s_{k−ℓ}' over the pairs that both lie in the accumulated range, and
+ * J = Γ_0 + Σ_{ℓ=1}^{lags} (1 − ℓ/(lags+1))(Γ_ℓ + Γ_ℓ') (Bartlett weights; lags = 0: the plain outer product of
+ * gradients; lags ≥ nobs − 2 is allowed, the sums are empty).  opg_out is P × P × B column-major, symmetric to the bit.
+ *   Hessian: H = ∂²ll/∂θ∂θ' by fourth-order central differences of the EXACT gradient over the realised steps,
+ * D_i = (8(g(θ+h e_i) − g(θ−h e_i)) − (g(θ+2h e_i) − g(θ−2h e_i)))/(12h), H = ½(D + D'): 4P perturbed candidates per
+ * θ through the loglik and gradient kernels.  step ≤ 0 asks for the default h = YFM_INFO_DEFAULT_STEP.  hess_out is
+ * P × P × B column-major, symmetric to the bit.
+ *   Unavailable: a candidate has NaN in all of S, J and H where its loglik is −Inf or NaN or where it was evaluated
+ * on the double-double path (the deferral list: κ₁(Z'Z) ≥ 1e6), and in all of H also where any of its 4P perturbed
+ * points is in that state.  yfm_last_batch_grad_unavailable counts, after yfm_loglik_scores_batch(_device), the
+ * deferred candidates (as after yfm_loglik_grad_batch) and, after yfm_loglik_info_batch, the candidates with NaN in H
+ * (hess_out NULL: in J); the other yfm_last_batch_* counters then answer for the batch's own loglik launch.
+ *   yfm_loglik_info_batch: host pointers; hess_out or opg_out may be NULL to skip that half (not both); loglik_out is
+ * bitwise yfm_loglik_batch's and grad_out bitwise yfm_loglik_grad_batch's.  A candidate's outputs do not depend on
+ * the batch it sits in.  Beyond the staging that yfm_loglik_grad_batch allocates for the same batch (θ, T_use, loglik,
+ * gradient, the work records of the batch's loglik launch), no temporary exceeds 128 MiB: the scores, the perturbed
+ * points with the work records of their launches, H and J go chunk by chunk.
+ *   YFM_MODEL_DNS with N ≤ 64 only: every other kind, and a larger N, returns YFM_EUNSUPPORTED; lags < 0 and two
+ * NULL outputs return YFM_EINVAL.  The _device twin takes device pointers and is asynchronous on hip_stream, with the
+ * ordering rules of yfm_loglik_grad_batch_device.  Additive: YFM_ABI_VERSION stays 5; a library that has the symbols
+ * has the feature. */
+#define YFM_INFO_DEFAULT_STEP 1e-4
+int yfm_loglik_scores_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                            const int* T_use, double* loglik_out, double* scores_out);
+int yfm_loglik_scores_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
+                                   const int* d_T_use, double* d_loglik_out, double* d_scores_out, void* hip_stream);
+int yfm_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                          const int* T_use, int lags, double step, double* loglik_out, double* grad_out,
+                          double* hess_out, double* opg_out);
+
 /* One Optim.NelderMead run per chain on a block of coordinates — what estimate_steps! does for a parameter group
  * that uses opt1 (optimization.jl:218-247 with :442-451, :479: NelderMead, `iterations`, g_tol), without the outer
  * group loop, the sanitising or the rescaling around it (:157-184, :249-281), which stay with the caller.  p is

@@ -74,6 +74,11 @@ struct yfm::Workspace {
   DevBuf scratch_fd;  // their double-double records (yfm_fixedz_dd.hip)
   DevBuf grad;        // gradient staging of the host-pointer gradient calls (yfm_loglik_grad_batch, yfm_lambda_loss_grad_batch)
   DevBuf nns_traj;    // the neural full gradient's trajectory: the forward sweep's records of one chunk of candidates
+  // yfm_loglik_scores_batch / yfm_loglik_info_batch: one chunk of candidates at a time, each buffer ≤ kInfoChunkBytes
+  DevBuf info_scores;  // the score series of a chunk
+  DevBuf info_pts, info_pgrad, info_pmisc;  // a chunk's 4P perturbed θ, their gradients, their logliks / steps / T_use
+  DevBuf info_out;     // H or J of a chunk (P × P per candidate), copied out before the next chunk
+  DevBuf info_flags;   // the batch's own counter bank kept over the perturbed launches, and the unavailable count
   // allocate and zero the two counter banks
   hipError_t init() {
     const size_t nb = 2 * yfm::kFlagsPerBank * sizeof(unsigned int);
@@ -515,11 +520,9 @@ int check_neural_fullgrad(yfm_ctx* ctx, int kind, int space, int P, int B) {
   return YFM_OK;
 }
 
-// The loglik launch q on the context's own workspace, then the tangent kernel on the same stream: it reads the
-// logliks q.out and (DNS) that launch's deferral list and adds n_grad_unavailable to its counter bank.
-int launch_grad(yfm_ctx* ctx, const Launch& q, double* d_grad) {
-  if (int r = launch(ctx, q)) return r;
-  if (q.B == 0) return YFM_OK;
+// What a tangent kernel enqueued after the loglik launch q (on the context's own workspace) reads: that launch's
+// inputs, its counter bank and its deferral list.
+yfm::LaunchArgs tangent_args(yfm_ctx* ctx, const Launch& q) {
   yfm::Workspace& w = ctx->own;
   yfm::LaunchArgs a{};
   a.theta = q.theta;
@@ -537,6 +540,16 @@ int launch_grad(yfm_ctx* ctx, const Launch& q, double* d_grad) {
   a.flags = w.bank_ptr(w.bank);  // the bank of the loglik launch just enqueued
   a.defer_list = static_cast<int*>(w.defer.p);
   a.stream = q.stream;
+  return a;
+}
+
+// The loglik launch q on the context's own workspace, then the tangent kernel on the same stream: it reads the
+// logliks q.out and (DNS) that launch's deferral list and adds n_grad_unavailable to its counter bank.
+int launch_grad(yfm_ctx* ctx, const Launch& q, double* d_grad) {
+  if (int r = launch(ctx, q)) return r;
+  if (q.B == 0) return YFM_OK;
+  yfm::Workspace& w = ctx->own;
+  const yfm::LaunchArgs a = tangent_args(ctx, q);
   const hipError_t e = q.kind == YFM_MODEL_TVL ? yfm::launch_tvl_grad(a, q.out, d_grad)
                                                : yfm::launch_dns_grad(a, q.out, d_grad);
   if (e != hipSuccess) {
@@ -684,6 +697,104 @@ int loglik_grad_batch_device(GradCheck check, yfm_ctx* ctx, int model_kind, int 
     return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_grad_out");
   return launch_grad(ctx, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
                                         static_cast<hipStream_t>(hip_stream)), d_grad_out);
+}
+
+
+// The score / information entry points' model check: they run the DNS tangent recursion, so its limits hold.
+int check_info(yfm_ctx* ctx, const char* what, int kind, int space, int P, int B) {
+  if (state_dim(kind) >= 0 && kind != YFM_MODEL_DNS)
+    return set_error(YFM_EUNSUPPORTED, "%s is built for YFM_MODEL_DNS only (model_kind %d): no score series, "
+                     "information matrix or Hessian exists for the other kinds", what, kind);
+  if (int r = check_batch(ctx, kind, space, P, B)) return r;
+  if (ctx->N > yfm::grad_max_n())
+    return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the %d of the tangent kernel that %s runs", ctx->N,
+                     yfm::grad_max_n(), what);
+  return YFM_OK;
+}
+
+// No temporary that the score / information entry points add is larger than this: bigger batches go chunk by chunk.
+// (The batch's own staging — θ, T_use, loglik, gradient and the work records of its loglik launch — is what
+// yfm_loglik_grad_batch allocates for the same batch.)
+constexpr size_t kInfoChunkBytes = (size_t)128 << 20;
+
+int info_chunk(size_t bytes_per_candidate, int B) {
+  const size_t n = kInfoChunkBytes / std::max<size_t>(bytes_per_candidate, 1);
+  return (int)std::min<size_t>(std::max<size_t>(n, 1), (size_t)std::max(B, 1));
+}
+
+// The largest work buffer enqueue() grows for a fixed-loading loglik launch of n candidates (the double-double records
+// of the deferral path, the per-lane kernel's init records, the deferral list).
+size_t fixedz_launch_bytes(int kind, int n) {
+  return std::max({yfm::fixedz_dd_scratch_bytes(kind, n), yfm::fixedz_scratch_bytes(kind, n), sizeof(int) * (size_t)n});
+}
+
+// The scores of the candidates of the loglik launch q (the last one enqueued on the own workspace), chunk by chunk
+// through info_scores; `each(b0, nb, d_scores)` consumes a chunk before the next one overwrites it (same stream).
+// `out_per`: bytes per candidate of what `each` itself keeps per chunk.
+template <class F>
+int for_score_chunks(yfm_ctx* ctx, const Launch& q, bool count, size_t out_per, F&& each) {
+  const size_t per = sizeof(double) * (size_t)q.P * (size_t)std::max(ctx->T - 1, 0);
+  const int chunk = info_chunk(std::max(per, out_per), q.B);
+  YFM_HIP_CHECK(ctx->own.info_scores.ensure(per * chunk));
+  double* const d_scores = static_cast<double*>(ctx->own.info_scores.p);
+  const yfm::LaunchArgs a = tangent_args(ctx, q);
+  for (int b0 = 0; b0 < q.B; b0 += chunk) {
+    const int nb = std::min(chunk, q.B - b0);
+    const hipError_t e = yfm::launch_dns_scores(a, q.out, d_scores, b0, nb, count);
+    if (e != hipSuccess) {
+      ctx->own.bank_dirty = true;
+      return set_error(YFM_EHIP, "score kernel launch: %s", hipGetErrorString(e));
+    }
+    if (int r = each(b0, nb, d_scores)) return r;
+  }
+  return YFM_OK;
+}
+
+// Candidates per Hessian chunk: the 4P perturbed θ and their gradients (P doubles per point each), and everything the
+// loglik launch of the chunk's 4P·nb points allocates, each within kInfoChunkBytes.
+int hessian_chunk(int kind, int P, int B) {
+  const size_t np = 4 * (size_t)P;
+  int chunk = info_chunk(sizeof(double) * (size_t)P * np, B);
+  while (chunk > 1) {
+    const size_t need = fixedz_launch_bytes(kind, (int)(np * chunk));
+    if (need <= kInfoChunkBytes) break;
+    const int fit = (int)((double)chunk * ((double)kInfoChunkBytes / (double)need));
+    chunk = std::max(1, std::min(chunk - 1, fit));
+  }
+  return chunk;
+}
+
+// H of every candidate of the staged launch q, chunk by chunk: the perturbed points, their logliks and gradients (the
+// existing launches, on the own workspace), the assembly with the unavailable rule (d_grad: the batch's own gradients;
+// d_count: raised per unavailable candidate), and the chunk's H to the host.
+int hessian_chunks(yfm_ctx* ctx, const Launch& q, double h, const double* d_grad, unsigned int* d_count,
+                   double* hess_out) {
+  yfm::Workspace& w = ctx->own;
+  const size_t P = (size_t)q.P, np = 4 * P;  // points per candidate
+  const int chunk = hessian_chunk(q.kind, q.P, q.B);
+  YFM_HIP_CHECK(w.info_pts.ensure(sizeof(double) * P * np * chunk));
+  YFM_HIP_CHECK(w.info_pgrad.ensure(sizeof(double) * P * np * chunk));
+  // logliks (np), realised steps (2P), windows (np ints) per candidate
+  YFM_HIP_CHECK(w.info_pmisc.ensure((sizeof(double) * (np + 2 * P) + sizeof(int) * np) * chunk));
+  YFM_HIP_CHECK(w.info_out.ensure(sizeof(double) * P * P * chunk));
+  double* const d_pts = static_cast<double*>(w.info_pts.p);
+  double* const d_pgrad = static_cast<double*>(w.info_pgrad.p);
+  double* const d_pll = static_cast<double*>(w.info_pmisc.p);
+  double* const d_steps = d_pll + np * chunk;
+  int* const d_ptu = reinterpret_cast<int*>(d_steps + 2 * P * chunk);
+  double* const d_H = static_cast<double*>(w.info_out.p);
+  for (int b0 = 0; b0 < q.B; b0 += chunk) {
+    const int nb = std::min(chunk, q.B - b0);
+    YFM_HIP_CHECK(yfm::launch_hessian_points(q.theta + P * b0, q.P, nb, q.T_use ? q.T_use + b0 : nullptr, h, d_pts,
+                                             d_ptu, d_steps, q.stream));
+    const Launch qp = loglik_launch(q.kind, q.space, d_pts, q.P, (int)np * nb, q.T_use ? d_ptu : nullptr, d_pll,
+                                    q.stream);
+    if (int r = launch_grad(ctx, qp, d_pgrad)) return r;
+    YFM_HIP_CHECK(yfm::launch_hessian_assemble(d_pgrad, d_steps, d_grad + P * b0, q.P, nb, d_H, d_count, q.stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(hess_out + P * P * b0, d_H, sizeof(double) * P * P * nb, hipMemcpyDeviceToHost,
+                                 q.stream));
+  }
+  return YFM_OK;
 }
 
 }  // namespace
@@ -951,6 +1062,106 @@ int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n) {
   unsigned int h[yfm::kFlagsPerBank];
   if (int r = read_flags(ctx, h)) return r;
   if (n) *n = h[5];
+  return YFM_OK;
+}
+
+int yfm_loglik_scores_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                            const int* T_use, double* loglik_out, double* scores_out) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_info(ctx, "yfm_loglik_scores_batch", model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !loglik_out || !scores_out))
+    return set_error(YFM_EINVAL, "null theta, loglik_out or scores_out");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  if (int r = launch(ctx, q)) return r;
+  if (B > 0) {
+    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t per = (size_t)P * (size_t)(ctx->T - 1);
+    const int rc = for_score_chunks(ctx, q, true, 0, [&](int b0, int nb, const double* d_scores) {
+      if (per > 0)
+        YFM_HIP_CHECK(hipMemcpyAsync(scores_out + per * b0, d_scores, sizeof(double) * per * nb, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+      return (int)YFM_OK;
+    });
+    if (rc != YFM_OK) return rc;
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+int yfm_loglik_scores_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
+                                   const int* d_T_use, double* d_loglik_out, double* d_scores_out, void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_info(ctx, "yfm_loglik_scores_batch_device", model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_loglik_out || !d_scores_out))
+    return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_scores_out");
+  const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
+                                 static_cast<hipStream_t>(hip_stream));
+  if (int r = launch(ctx, q)) return r;
+  if (B == 0) return YFM_OK;
+  const hipError_t e = yfm::launch_dns_scores(tangent_args(ctx, q), q.out, d_scores_out, 0, B, true);
+  if (e != hipSuccess) {
+    ctx->own.bank_dirty = true;
+    return set_error(YFM_EHIP, "score kernel launch: %s", hipGetErrorString(e));
+  }
+  return YFM_OK;
+}
+
+int yfm_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                          const int* T_use, int lags, double step, double* loglik_out, double* grad_out,
+                          double* hess_out, double* opg_out) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_info(ctx, "yfm_loglik_info_batch", model_kind, param_space, P, B)) return r;
+  if (lags < 0) return set_error(YFM_EINVAL, "lags = %d < 0 (0: the plain outer product of the scores)", lags);
+  if (!hess_out && !opg_out)
+    return set_error(YFM_EINVAL, "hess_out and opg_out are both null: yfm_loglik_grad_batch is the call for the "
+                     "loglik and its gradient alone");
+  if (!(step == step) || step > 1.79769313486231570815e308)
+    return set_error(YFM_EINVAL, "step is not a finite number (<= 0: the default)");
+  if (B > 0 && (!theta || !loglik_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loglik_out or grad_out");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  yfm::Workspace& w = ctx->own;
+  const size_t PP = (size_t)P * P;
+  YFM_HIP_CHECK(w.grad.ensure(sizeof(double) * (size_t)P * (size_t)(B > 0 ? B : 1)));
+  YFM_HIP_CHECK(w.info_flags.ensure(sizeof(unsigned int) * (yfm::kFlagsPerBank + 1)));
+  double* const d_grad = static_cast<double*>(w.grad.p);
+  unsigned int* const d_saved = static_cast<unsigned int*>(w.info_flags.p);
+  unsigned int* const d_count = d_saved + yfm::kFlagsPerBank;  // the candidates with a NaN H (no Hessian: a NaN J)
+  YFM_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned int), ctx->stream));
+  // the batch's own loglik and gradient, bitwise yfm_loglik_grad_batch's
+  if (int r = launch_grad(ctx, q, d_grad)) return r;
+  if (B > 0) {
+    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, d_grad, sizeof(double) * (size_t)P * B, hipMemcpyDeviceToHost, ctx->stream));
+    if (opg_out) {  // before any other launch: the scores read this launch's deferral list
+      const int rc = for_score_chunks(ctx, q, false, sizeof(double) * PP, [&](int b0, int nb, const double* d_scores) {
+        YFM_HIP_CHECK(w.info_out.ensure(sizeof(double) * PP * nb));
+        double* const d_J = static_cast<double*>(w.info_out.p);
+        YFM_HIP_CHECK(yfm::launch_opg(d_scores, ctx->T, nb, q.T_use ? q.T_use + b0 : nullptr, lags,
+                                      d_grad + (size_t)P * b0, d_J, hess_out ? nullptr : d_count, ctx->stream));
+        YFM_HIP_CHECK(hipMemcpyAsync(opg_out + PP * b0, d_J, sizeof(double) * PP * nb, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+        return (int)YFM_OK;
+      });
+      if (rc != YFM_OK) return rc;
+    }
+    if (hess_out) {
+      // the perturbed launches take over the counter banks: the batch's own counters are kept and put back into the
+      // bank of the last launch, so yfm_last_batch_flags, _deferred and _steady answer for the batch itself
+      YFM_HIP_CHECK(hipMemcpyAsync(d_saved, w.bank_ptr(w.bank), sizeof(unsigned int) * yfm::kFlagsPerBank,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+      if (int r = hessian_chunks(ctx, q, step > 0.0 ? step : YFM_INFO_DEFAULT_STEP, d_grad, d_count, hess_out))
+        return r;
+      YFM_HIP_CHECK(hipMemcpyAsync(w.bank_ptr(w.bank), d_saved, sizeof(unsigned int) * yfm::kFlagsPerBank,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    YFM_HIP_CHECK(hipMemcpyAsync(w.bank_ptr(w.bank) + 5, d_count, sizeof(unsigned int), hipMemcpyDeviceToDevice,
+                                 ctx->stream));
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return YFM_OK;
 }
 

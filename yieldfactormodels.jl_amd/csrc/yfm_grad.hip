@@ -18,34 +18,13 @@
 // candidates of that launch's deferral list (ill-conditioned Z'Z: their value comes from the double-double
 // kernel, which has no tangents).
 #include <algorithm>
-#include <type_traits>
 
 #include "yfm_device.hpp"
 #include "yfm_grad.hpp"
+#include "yfm_grad_map.hpp"
 #include "yfm_internal.hpp"
 
 namespace yfm {
-
-namespace {
-
-constexpr int kGradBlock = 256;
-constexpr int kGradMaxN = 64;
-
-// the seed kinds of slot S when a candidate has L lanes: its directions are S·L … S·L + L − 1
-template <int L, int S>
-constexpr int slot_mask() {
-  constexpr int lo = S * L, hi = S * L + L - 1;
-  return (lo <= 1 ? grad::kSeedG : 0) | ((lo <= 7 && hi >= 2) ? grad::kSeedQ : 0) |
-         ((lo <= 10 && hi >= 8) ? grad::kSeedD : 0) | ((lo <= 19 && hi >= 11) ? grad::kSeedF : 0);
-}
-// f(integral_constant<int, S>) for S = 0 … ND − 1
-template <int ND, int S = 0, class F>
-__device__ __forceinline__ void for_slots(F&& f) {
-  f(std::integral_constant<int, S>{});
-  if constexpr (S + 1 < ND) for_slots<ND, S + 1>(f);
-}
-
-}  // namespace
 
 // L lanes per candidate, ND directions per lane
 template <int L, int ND>
@@ -154,11 +133,7 @@ __global__ void grad_unavailable_kernel(const int* __restrict__ defer_list, cons
 
 int grad_max_n() { return kGradMaxN; }
 
-// the mapping in use (tools/ab_build.py -DYFM_GRAD_LANES=16 -DYFM_GRAD_DIRS=2 builds the other one that fits)
-#ifndef YFM_GRAD_LANES
-#define YFM_GRAD_LANES 8
-#define YFM_GRAD_DIRS 3
-#endif
+// the mapping in use (yfm_grad_map.hpp)
 namespace {
 constexpr int kGradLanes = YFM_GRAD_LANES, kGradDirs = YFM_GRAD_DIRS;
 }

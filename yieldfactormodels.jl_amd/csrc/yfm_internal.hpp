@@ -82,6 +82,22 @@ hipError_t launch_fixedz_dd(int kind, const LaunchArgs& a, double* rec);
 // (counted in a.flags[5]).  grad_max_n: the largest N of its lane mapping.
 int grad_max_n();
 hipError_t launch_dns_grad(const LaunchArgs& a, const double* ll, double* grad_out);
+// DNS score series, OPG matrix and Hessian pieces (yfm_score.hip).  launch_dns_scores, enqueued like launch_dns_grad
+// after the loglik launch of all a.B candidates: S[d, k, b] = ∂ℓ_k/∂θ_d of candidates b0 … b0 + nb − 1 into scores
+// (P × (T − 1) × nb column-major, starting at candidate b0), exact zeros outside a window's accumulated columns, NaN
+// where ll[b] is not finite or b was deferred (`count`: the deferred counted into a.flags[5]).
+hipError_t launch_dns_scores(const LaunchArgs& a, const double* ll, double* scores, int b0, int nb, bool count);
+// J_b = Γ₀ + Σ_{ℓ ≤ lags} (1 − ℓ/(lags + 1))(Γ_ℓ + Γ_ℓ') from the scores of nb candidates (T_use, grad: theirs), 20 × 20 × nb;
+// NaN where the candidate's own gradient grad[:, b] is NaN; count (may be null): raised by the candidates with a NaN J
+hipError_t launch_opg(const double* scores, int T, int nb, const int* T_use, int lags, const double* grad, double* J,
+                      unsigned int* count, hipStream_t s);
+// the 4P points θ ± h e_i, θ ± 2h e_i of nb candidates (pts: P × 4P nb; pts_T_use: 4P nb, untouched when T_use is
+// null) and the realised steps (2P nb); then H = ½(D + D') from their gradients, NaN where one of them or the candidate's
+// own gradient grad[:, b] is not finite (such candidates raise *count)
+hipError_t launch_hessian_points(const double* theta, int P, int nb, const int* T_use, double h, double* pts,
+                                 int* pts_T_use, double* steps, hipStream_t s);
+hipError_t launch_hessian_assemble(const double* pts_grad, const double* steps, const double* grad, int P, int nb,
+                                   double* H, unsigned int* count, hipStream_t s);
 // TVλ loglik gradient (yfm_tvl_grad.hip), enqueued after the loglik launch whose counter bank a.flags it adds to:
 // ∂loglik/∂θ into grad_out (31×B) from the FP64 tangent recursion over a.raw (NaN flags from a.panel), NaN where
 // ll[b] is not finite or the recursion's own value or tangents are not usable (those counted in a.flags[5]).

@@ -19,6 +19,8 @@ from .params import KIND_NNS, KIND_NNS_ANCHORED, NEURAL_KINDS, is_neural_kind, n
 from .engine import Engine, get_engine
 from .driver import load_initial_parameters_, run, run_neural_estimation_
 from . import lbfgs
+from . import inference
+from .inference import covariance, standard_errors_, standard_errors_batch
 
 __all__ = [
     "KIND_DNS", "KIND_TVL", "KIND_GNS", "SPACE_CONSTRAINED", "SPACE_UNCONSTRAINED", "n_params", "param_layout",
@@ -32,4 +34,5 @@ __all__ = [
     "KIND_NNS_ANCHORED", "NEURAL_KINDS", "is_neural_kind", "neural_kind",
     "compute_neural_loss_grad_block", "estimate_neural_steps_", "estimate_neural_steps_batch", "run_neural_estimation_",
     "compute_neural_loss_fullgrad_batch", "estimate_neural_lbfgs_batch", "estimate_neural_",
+    "inference", "covariance", "standard_errors_batch", "standard_errors_",
 ]

@@ -75,9 +75,18 @@ SIGNATURES = {
                                                  _D, _D]),
     "yfm_tvl_loglik_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
                                                         ctypes.c_int, _V, _V, _V, _V]),
+    "yfm_loglik_scores_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D,
+                                               _D]),
+    "yfm_loglik_scores_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int,
+                                                      _V, _V, _V, _V]),
+    "yfm_loglik_info_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I,
+                                             ctypes.c_int, ctypes.c_double, _D, _D, _D, _D]),
 }
 
 ABI_VERSION = 5
+
+# the default Hessian step (include/yfm.h: YFM_INFO_DEFAULT_STEP)
+INFO_DEFAULT_STEP = 1e-4
 
 # precision modes (include/yfm.h: enum yfm_precision)
 PREC_CERTIFIED, PREC_FP64 = 0, 1

@@ -12,7 +12,7 @@ import threading
 import numpy as np
 
 from . import _lib
-from .params import gamma_dim, n_params, state_dim
+from .params import KIND_DNS, gamma_dim, n_params, state_dim
 
 
 class Engine:
@@ -130,6 +130,59 @@ class Engine:
                                                          ctypes.c_void_p(d_T_use) if d_T_use else None,
                                                          ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
                                                          ctypes.c_void_p(stream) if stream else None))
+
+    def loglik_scores(self, kind: int, theta, space: int = 0, T_use=None):
+        """(ll[B], S[P, T−1, B]): the logliks of :meth:`loglik` and the score series S[d, k, b] = ∂ℓ_k/∂θ_d, ℓ_k the
+        term get_loss adds after column k — exact zeros outside a window's accumulated columns 1 … T_use − 2, NaN for
+        a candidate without a gradient (include/yfm.h yfm_loglik_scores_batch; DNS with N ≤ 64)."""
+        self._dns_only(kind, "loglik_scores")
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        ll = np.empty(B, dtype=np.float64)
+        S = np.empty((P, max(self.T - 1, 0), B), dtype=np.float64, order="F")
+        _lib.check(self.lib.yfm_loglik_scores_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                                    _lib.iptr(self._tuse(T_use, B)), _lib.dptr(ll), _lib.dptr(S)))
+        return ll, S
+
+    def loglik_scores_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_scores: int, space: int = 0,
+                             d_T_use: int | None = None, stream: int | None = None) -> None:
+        """Device-pointer variant of :meth:`loglik_scores` (raw addresses; d_scores: P×(T−1)×B column-major);
+        asynchronous on ``stream``."""
+        self._dns_only(kind, "loglik_scores_device")
+        _lib.check(self.lib.yfm_loglik_scores_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
+                                                           ctypes.c_void_p(d_T_use) if d_T_use else None,
+                                                           ctypes.c_void_p(d_out), ctypes.c_void_p(d_scores),
+                                                           ctypes.c_void_p(stream) if stream else None))
+
+    def loglik_info(self, kind: int, theta, space: int = 0, T_use=None, lags: int = 0, step: float | None = None,
+                    hessian: bool = True, opg: bool = True) -> dict:
+        """ll[B], grad[P, B] (those of :meth:`loglik_grad`, bit for bit), hess[P, P, B] = ∂²ll/∂θ∂θ' (fourth-order
+        central differences of the exact gradient, step ``step``; None: the library's default) and opg[P, P, B] =
+        Γ₀ + Σ_ℓ (1 − ℓ/(lags+1))(Γ_ℓ + Γ_ℓ') of the score series, as a dict; ``hessian`` / ``opg`` False skips that
+        half (its entry is None).  NaN matrices for a candidate without a gradient, and a NaN Hessian where one of
+        its perturbed points has none (include/yfm.h yfm_loglik_info_batch; DNS with N ≤ 64)."""
+        self._dns_only(kind, "loglik_info")
+        if not (hessian or opg):
+            raise ValueError("loglik_info: hessian and opg are both off (loglik_grad gives the loglik and gradient)")
+        if lags < 0:
+            raise ValueError(f"lags = {lags} < 0")
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        ll = np.empty(B, dtype=np.float64)
+        grad = np.empty((P, B), dtype=np.float64, order="F")
+        H = np.empty((P, P, B), dtype=np.float64, order="F") if hessian else None
+        J = np.empty((P, P, B), dtype=np.float64, order="F") if opg else None
+        _lib.check(self.lib.yfm_loglik_info_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                                  _lib.iptr(self._tuse(T_use, B)), int(lags),
+                                                  0.0 if step is None else float(step), _lib.dptr(ll), _lib.dptr(grad),
+                                                  _lib.dptr(H) if hessian else None, _lib.dptr(J) if opg else None))
+        return dict(ll=ll, grad=grad, hess=H, opg=J)
+
+    @staticmethod
+    def _dns_only(kind, what):
+        if kind != KIND_DNS:
+            raise NotImplementedError(f"{what} is built for the DNS model (kind {KIND_DNS}) only, not kind {kind}: the "
+                                      "other kinds have no score series, information matrix or Hessian")
 
     def tvl_loglik_grad(self, kind: int, theta, space: int = 0, T_use=None):
         """(ll[B], grad[31, B]) of the TVλ model: the logliks of :meth:`loglik`, bit for bit under the context's

@@ -453,6 +453,43 @@ int yfm_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const d
                           const int* T_use, int lags, double step, double* loglik_out, double* grad_out,
                           double* hess_out, double* opg_out);
 
+/* The fixed-interval Kalman smoother of the fixed-loading models — β̂_{t|n} = E[β_t | y_1 … y_n], its covariance and the
+ * lag-one covariance: level, slope and curvature paths, fitted curves, residuals that are not one-step forecasts, and
+ * the moments Σ V_t, Σ C_t of an EM step.  AN EXTENSION: the reference has no counterpart (its predict, filter.jl:250-282,
+ * returns the forecasts a_{t+1|t} only), so the definitions below are this library's own.
+ *   Model: the one the reference's fixed-loading filter! runs (filter.jl:125-179, initialize_filter filter.jl:1-10):
+ * y_t = Zβ_t + ε_t with Var ε = σ²I; β_{t+1} = δ + Φβ_t + η_t with Var η = Q; a_1 = (I − Φ)⁻¹δ and P_1 the unconditional
+ * covariance.  A column with any NaN entry is a missing column (the reference's rule any(isnan.(y))).
+ *   Window: candidate b has n = T_use[b] columns, or T when T_use is NULL.  All n columns condition the result, column 1
+ * and column n included: the exclusion of t = 1 from the log-likelihood and the unused last column of get_loss are
+ * properties of the loss, not of the state estimate.  n = 1 is valid: one update, no C.
+ *   Definitions: with G = Z'Z and a_t, P_t the predicted moments a_{t|t−1}, P_{t|t−1}, at a data column
+ *     B_t = σ²I + G P_t,  s_t = B_t⁻¹(Z'y_t − G a_t) (= Z'F_t⁻¹v_t),  W_t = B_t⁻¹G (= Z'F_t⁻¹Z),  L_t = Φ(I − P_t W_t);
+ * at a missing column s_t = 0, W_t = 0, L_t = Φ.  Backward, from r_n = 0 and N_n = 0:
+ *     r_{t−1} = s_t + L_t' r_t,   N_{t−1} = W_t + L_t' N_t L_t,
+ *     β̂_t = a_t + P_t r_{t−1},   V_t = P_t − P_t N_{t−1} P_t,
+ *     C_t = Cov(β_{t+1}, β_t | y_1..n) = (I − P_{t+1} N_t) L_t P_t,  t = 1 … n − 1.
+ *   Outputs, column-major, NaN beyond a candidate's window: beta_s M × T × B, slot t − 1 = β̂_t; V_s M × M × T × B,
+ * symmetric to the bit; C_s M × M × (T − 1) × B, slot t − 1 = C_t — C_s may be NULL.
+ *   Unavailable: all of a candidate's outputs are NaN where initialize_filter would throw; where its log-likelihood
+ * over the window is −Inf or NaN; where it sits on the deferral list (κ₁(Z'Z) ≥ 1e6 and the like: an FP64 backward
+ * sweep of those is not certified — their forward states remain available through yfm_filter_states); and where any
+ * of its outputs is not finite.  yfm_last_batch_grad_unavailable counts these candidates; yfm_last_batch_flags and
+ * yfm_last_batch_deferred answer for the batch's forward launch.  A candidate's outputs are bitwise independent of the
+ * batch it is in and of its position in it.
+ *   yfm_smooth_batch takes host pointers and is synchronous; yfm_smooth_batch_device takes device pointers and only
+ * enqueues on hip_stream, with the ordering rules of yfm_loglik_batch_device.  The forward pass is the trajectory
+ * launch of yfm_filter_states.  Beyond the batch's own staging (θ, T_use, the logliks, the work records of the forward
+ * launch) no device temporary exceeds 128 MiB: the recorded moments go chunk by chunk over candidates, and in the
+ * host-pointer call the outputs leave per chunk.  B = 0 succeeds.
+ *   YFM_MODEL_DNS and YFM_MODEL_GNS5 with N ≤ 64: a larger N returns YFM_EUNSUPPORTED, and so do YFM_MODEL_TVL (its
+ * extended smoother is not built), the λ kinds and the neural kinds (no Kalman filter: nothing to smooth).  Additive:
+ * YFM_ABI_VERSION stays 5; a library that has the symbols has the feature. */
+int yfm_smooth_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                     const int* T_use, double* beta_s, double* V_s, double* C_s);
+int yfm_smooth_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
+                            const int* d_T_use, double* d_beta_s, double* d_V_s, double* d_C_s, void* hip_stream);
+
 /* One Optim.NelderMead run per chain on a block of coordinates — what estimate_steps! does for a parameter group
  * that uses opt1 (optimization.jl:218-247 with :442-451, :479: NelderMead, `iterations`, g_tol), without the outer
  * group loop, the sanitising or the rescaling around it (:157-184, :249-281), which stay with the caller.  p is

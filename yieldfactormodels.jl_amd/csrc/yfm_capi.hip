@@ -79,6 +79,11 @@ struct yfm::Workspace {
   DevBuf info_pts, info_pgrad, info_pmisc;  // a chunk's 4P perturbed θ, their gradients, their logliks / steps / T_use
   DevBuf info_out;     // H or J of a chunk (P × P per candidate), copied out before the next chunk
   DevBuf info_flags;   // the batch's own counter bank kept over the perturbed launches, and the unavailable count
+  // yfm_smooth_batch(_device): one chunk of candidates at a time, the record and each output buffer ≤ kInfoChunkBytes
+  DevBuf smooth_rec_beta, smooth_rec_P;    // the forward launch's record of a chunk (a_{t+1|t}, P_{t+1|t})
+  DevBuf smooth_skip;                      // a chunk's deferred marks
+  DevBuf smooth_ll;                        // the device-pointer call's logliks (the host-pointer call uses ctx->out)
+  DevBuf smooth_beta, smooth_V, smooth_C;  // the host-pointer call's outputs of a chunk, copied out before the next
   // allocate and zero the two counter banks
   hipError_t init() {
     const size_t nb = 2 * yfm::kFlagsPerBank * sizeof(unsigned int);
@@ -797,6 +802,95 @@ int hessian_chunks(yfm_ctx* ctx, const Launch& q, double h, const double* d_grad
   return YFM_OK;
 }
 
+// The smoother entry points' model check: the backward sweep is built for the fixed-loading Kalman models.
+int check_smooth(yfm_ctx* ctx, const char* what, int kind, int space, int P, int B) {
+  if (kind == YFM_MODEL_TVL)
+    return set_error(YFM_EUNSUPPORTED, "%s is built for YFM_MODEL_DNS and YFM_MODEL_GNS5: the TVlambda model's loadings "
+                     "move with the state, and its extended smoother is not built (model_kind %d)", what, kind);
+  if (yfm::msed_kind(kind))
+    return set_error(YFM_EUNSUPPORTED, "%s is built for YFM_MODEL_DNS and YFM_MODEL_GNS5: the %s kinds are not Kalman "
+                     "filters and have no state covariance to smooth (model_kind %d)", what,
+                     yfm::msedn_kind(kind) ? "neural" : "lambda", kind);
+  if (int r = check_batch(ctx, kind, space, P, B)) return r;
+  if (ctx->N > yfm::smooth_max_n())
+    return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the %d of the smoother's backward sweep", ctx->N,
+                     yfm::smooth_max_n());
+  return YFM_OK;
+}
+
+// Candidates per smoother chunk: the forward record (a and P of T − 1 steps), each output array and everything the
+// trajectory launch of the chunk allocates, each within kInfoChunkBytes.
+int smooth_chunk(int kind, int M, int T, int B) {
+  const size_t rec = sizeof(double) * (size_t)(M + M * M) * (size_t)std::max(T - 1, 1);
+  const size_t out = sizeof(double) * (size_t)M * M * (size_t)T;
+  int chunk = info_chunk(std::max(rec, out), B);
+  while (chunk > 1) {
+    const size_t need = fixedz_launch_bytes(kind, chunk);
+    if (need <= kInfoChunkBytes) break;
+    const int fit = (int)((double)chunk * ((double)kInfoChunkBytes / (double)need));
+    chunk = std::max(1, std::min(chunk - 1, fit));
+  }
+  return chunk;
+}
+
+// The smoother over the candidates of q (θ, T_use and the logliks q.out on the device), chunk by chunk on q.stream:
+// the trajectory launch of the chunk into the record scratch, then the backward sweep.  h_beta null: the sweep writes
+// into the caller's device arrays d_beta, d_V, d_C (whole batch).  Otherwise it writes a chunk's outputs into the
+// context's staging buffers, which leave for h_beta, h_V, h_C before the next chunk (want_C: with the lag-one array).
+int smooth_chunks(yfm_ctx* ctx, const Launch& q, double* d_beta, double* d_V, double* d_C, double* h_beta, double* h_V,
+                  double* h_C, bool want_C) {
+  yfm::Workspace& w = ctx->own;
+  const int M = state_dim(q.kind), T = ctx->T;
+  const size_t nM = (size_t)M * T, nV = (size_t)M * M * T, nC = (size_t)M * M * (size_t)(T - 1);
+  const int chunk = smooth_chunk(q.kind, M, T, q.B);
+  const size_t steps = (size_t)std::max(T - 1, 1) * chunk;
+  YFM_HIP_CHECK(w.smooth_rec_beta.ensure(sizeof(double) * steps * M));
+  YFM_HIP_CHECK(w.smooth_rec_P.ensure(sizeof(double) * steps * M * M));
+  YFM_HIP_CHECK(w.smooth_skip.ensure((size_t)chunk));
+  if (h_beta) {
+    YFM_HIP_CHECK(w.smooth_beta.ensure(sizeof(double) * nM * chunk));
+    YFM_HIP_CHECK(w.smooth_V.ensure(sizeof(double) * nV * chunk));
+    if (want_C) YFM_HIP_CHECK(w.smooth_C.ensure(sizeof(double) * std::max<size_t>(nC, 1) * chunk));
+  }
+  for (int b0 = 0; b0 < q.B; b0 += chunk) {
+    const int nb = std::min(chunk, q.B - b0);
+    Launch qc = q;
+    qc.theta = q.theta + (size_t)q.P * b0;
+    qc.B = nb;
+    qc.T_use = q.T_use ? q.T_use + b0 : nullptr;
+    qc.out = q.out + b0;
+    qc.continues = b0 > 0;  // one batch: the chunks' counters add up
+    if (T >= 2) {           // a one-column panel has no recorded step: the sweep takes a_1, P_1 alone
+      qc.rec_beta = static_cast<double*>(w.smooth_rec_beta.p);
+      qc.rec_P = static_cast<double*>(w.smooth_rec_P.p);
+      qc.rec_len = T - 1;
+    }
+    if (int r = launch(ctx, qc)) return r;
+    yfm::LaunchArgs a = tangent_args(ctx, qc);
+    a.rec_beta = qc.rec_beta;
+    a.rec_P = qc.rec_P;
+    a.rec_len = qc.rec_len;
+    double* const ob = h_beta ? static_cast<double*>(w.smooth_beta.p) : d_beta + nM * b0;
+    double* const oV = h_beta ? static_cast<double*>(w.smooth_V.p) : d_V + nV * b0;
+    double* const oC = h_beta ? (want_C ? static_cast<double*>(w.smooth_C.p) : nullptr) : (d_C ? d_C + nC * b0 : nullptr);
+    // measurement only (tools/bench_smooth.py): YFM_SMOOTH_SWEEP=0 leaves the sweep out, so the forward trajectory
+    // launch can be timed alone; the outputs are then not written
+    if (std::atoi(yfm::env_or("YFM_SMOOTH_SWEEP", "1")) == 0) continue;
+    const hipError_t e = yfm::launch_smooth(q.kind, a, qc.out, static_cast<unsigned char*>(w.smooth_skip.p), ob, oV, oC);
+    if (e != hipSuccess) {
+      w.bank_dirty = true;
+      return set_error(YFM_EHIP, "smoother kernel launch: %s", hipGetErrorString(e));
+    }
+    if (h_beta) {
+      YFM_HIP_CHECK(hipMemcpyAsync(h_beta + nM * b0, ob, sizeof(double) * nM * nb, hipMemcpyDeviceToHost, q.stream));
+      YFM_HIP_CHECK(hipMemcpyAsync(h_V + nV * b0, oV, sizeof(double) * nV * nb, hipMemcpyDeviceToHost, q.stream));
+      if (want_C && nC > 0)
+        YFM_HIP_CHECK(hipMemcpyAsync(h_C + nC * b0, oC, sizeof(double) * nC * nb, hipMemcpyDeviceToHost, q.stream));
+    }
+  }
+  return YFM_OK;
+}
+
 }  // namespace
 
 namespace yfm {
@@ -1163,6 +1257,35 @@ int yfm_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const d
   }
   YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return YFM_OK;
+}
+
+int yfm_smooth_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                     const int* T_use, double* beta_s, double* V_s, double* C_s) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_smooth(ctx, "yfm_smooth_batch", model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !beta_s || !V_s)) return set_error(YFM_EINVAL, "null theta, beta_s or V_s");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  if (B == 0) {
+    if (int r = launch(ctx, q)) return r;
+  } else if (int r = smooth_chunks(ctx, q, nullptr, nullptr, nullptr, beta_s, V_s, C_s, C_s != nullptr)) {
+    return r;
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+int yfm_smooth_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
+                            const int* d_T_use, double* d_beta_s, double* d_V_s, double* d_C_s, void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_smooth(ctx, "yfm_smooth_batch_device", model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_beta_s || !d_V_s)) return set_error(YFM_EINVAL, "null d_theta, d_beta_s or d_V_s");
+  YFM_HIP_CHECK(ctx->own.smooth_ll.ensure(sizeof(double) * (size_t)(B > 0 ? B : 1)));
+  const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use,
+                                 static_cast<double*>(ctx->own.smooth_ll.p), static_cast<hipStream_t>(hip_stream));
+  if (B == 0) return launch(ctx, q);
+  return smooth_chunks(ctx, q, d_beta_s, d_V_s, d_C_s, nullptr, nullptr, nullptr, false);
 }
 
 int yfm_filter_states(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,

@@ -98,6 +98,14 @@ hipError_t launch_hessian_points(const double* theta, int P, int nb, const int* 
                                  int* pts_T_use, double* steps, hipStream_t s);
 hipError_t launch_hessian_assemble(const double* pts_grad, const double* steps, const double* grad, int P, int nb,
                                    double* H, unsigned int* count, hipStream_t s);
+// The backward sweep of the fixed-interval smoother (yfm_smooth.hip; DNS and GNS5, N ≤ smooth_max_n), enqueued after
+// the trajectory launch of the a.B candidates at a.theta whose record a.rec_beta / a.rec_P (stride a.rec_len = T − 1),
+// counters a.flags and deferral list a.defer_list it reads: β̂ (M × T × B), V (M × M × T × B) and, C_s not null, the
+// lag-one covariances (M × M × (T − 1) × B), NaN past a window and in all of a candidate whose ll[b] is not finite,
+// that was deferred or that has an output that is not finite (those counted in a.flags[5]).  skip: a.B bytes of work.
+int smooth_max_n();
+hipError_t launch_smooth(int kind, const LaunchArgs& a, const double* ll, unsigned char* skip, double* beta_s,
+                         double* V_s, double* C_s);
 // TVλ loglik gradient (yfm_tvl_grad.hip), enqueued after the loglik launch whose counter bank a.flags it adds to:
 // ∂loglik/∂θ into grad_out (31×B) from the FP64 tangent recursion over a.raw (NaN flags from a.panel), NaN where
 // ll[b] is not finite or the recursion's own value or tangents are not usable (those counted in a.flags[5]).

@@ -104,6 +104,24 @@ function loglik_grad_batch(model, data::Matrix{Float64}, Θ::Matrix{Float64}; sp
     ll, grad
 end
 
+"Fixed-interval Kalman smoother of the fixed-loading models (DNS, GNS5; N ≤ 64) — an extension, predict returns the
+forecasts a_{t+1|t} only: (β̂[M, T, B], V[M, M, T, B], C[M, M, T-1, B]) with β̂[:, t, b] = E[β_t | y_1..n],
+V its covariance and C[:, :, t, b] = Cov(β_{t+1}, β_t | y_1..n), n = T_use[b] (nothing: every column).  NaN beyond a
+window and for a candidate without states (ll -Inf / NaN, the double-double path, a non-finite output: yfm.h; counted
+by yfm_last_batch_grad_unavailable).  lag_one = false skips C (returned as nothing)."
+function smooth(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = CONSTRAINED,
+                T_use::Union{Nothing,Vector{Cint}} = nothing, lag_one::Bool = true)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    M, T = Int(@ccall LIB.yfm_state_dim(kind(model)::Cint)::Cint), size(data, 2)
+    βs, V = Array{Float64}(undef, M, T, B), Array{Float64}(undef, M, M, T, B)
+    C = lag_one ? Array{Float64}(undef, M, M, max(T - 1, 0), B) : nothing
+    GC.@preserve Θ βs V C T_use check(@ccall LIB.yfm_smooth_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint, space::Cint,
+        Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, βs::Ptr{Cdouble}, V::Ptr{Cdouble},
+        (lag_one ? pointer(C) : Ptr{Cdouble}(C_NULL))::Ptr{Cdouble})::Cint)
+    βs, V, C
+end
+
 "TVλ loglik and its gradient: (ll[B], grad[31, B]), grad[:, b] = ∂(+loglik)/∂Θ[:, b] in `space` — estimate!'s
 ForwardDiff gradient (optimization.jl:367, :10-23) of the EKF of filter.jl:12-80.  ll is bitwise loglik_batch's under the
 context's precision; the gradient is the FP64 tangent recursion.  NaN gradient columns where ll is -Inf / NaN or the

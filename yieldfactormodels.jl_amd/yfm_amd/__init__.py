@@ -21,6 +21,8 @@ from .driver import load_initial_parameters_, run, run_neural_estimation_
 from . import lbfgs
 from . import inference
 from .inference import covariance, standard_errors_, standard_errors_batch
+from . import smoothing
+from .smoothing import em_moments, smooth_, smooth_batch, smoothed_yields
 
 __all__ = [
     "KIND_DNS", "KIND_TVL", "KIND_GNS", "SPACE_CONSTRAINED", "SPACE_UNCONSTRAINED", "n_params", "param_layout",
@@ -35,4 +37,5 @@ __all__ = [
     "compute_neural_loss_grad_block", "estimate_neural_steps_", "estimate_neural_steps_batch", "run_neural_estimation_",
     "compute_neural_loss_fullgrad_batch", "estimate_neural_lbfgs_batch", "estimate_neural_",
     "inference", "covariance", "standard_errors_batch", "standard_errors_",
+    "smoothing", "smooth_batch", "smooth_", "smoothed_yields", "em_moments",
 ]

@@ -483,12 +483,51 @@ int yfm_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const d
  * launch) no device temporary exceeds 128 MiB: the recorded moments go chunk by chunk over candidates, and in the
  * host-pointer call the outputs leave per chunk.  B = 0 succeeds.
  *   YFM_MODEL_DNS and YFM_MODEL_GNS5 with N ≤ 64: a larger N returns YFM_EUNSUPPORTED, and so do YFM_MODEL_TVL (its
- * extended smoother is not built), the λ kinds and the neural kinds (no Kalman filter: nothing to smooth).  Additive:
- * YFM_ABI_VERSION stays 5; a library that has the symbols has the feature. */
+ * extended smoother is yfm_tvl_smooth_batch), the λ kinds and the neural kinds (no Kalman filter: nothing to smooth).
+ * Additive: YFM_ABI_VERSION stays 5; a library that has the symbols has the feature. */
 int yfm_smooth_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                      const int* T_use, double* beta_s, double* V_s, double* C_s);
 int yfm_smooth_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
                             const int* d_T_use, double* d_beta_s, double* d_V_s, double* d_C_s, void* hip_stream);
+
+/* The extended Kalman smoother of the TVλ model — β̂_{t|n}, V_t, C_t as above with M = 4, and with them the path of the
+ * decay parameter given all the data, λ̂_t = 0.01 + exp(β̂_{4,t|n}).  AN EXTENSION, as the fixed-loading smoother is: the
+ * reference has no counterpart (its predict, filter.jl:250-282, returns forecasts only).
+ *   Model: the one the reference's TVλ filter! runs (filter.jl:12-80, update_factor_loadings! in tvλdns.jl:53-64,
+ * initialize_filter filter.jl:1-10), linearised once, at the forward pass's predicted states: nothing is re-linearised
+ * or iterated.  At a data column t, with a_t, P_t the predicted moments,
+ *     λ_t = 0.01 + exp(a_{4,t}),   Z_t = [1, S(λ_t), C(λ_t), ż_t]  (N × 4; ż_t the Jacobian column as written at
+ *     filter.jl:38-46, quirk kept),   v_t = y_t − Z_t[:,1:3]·a_t[1:3],   G_t = Z_t'Z_t,   u_t = Z_t'v_t,
+ *     B_t = σ²I + G_t P_t,   s_t = B_t⁻¹u_t,   W_t = B_t⁻¹G_t,   L_t = Φ(I − P_t W_t);
+ * a column with any NaN is a missing column: s_t = 0, W_t = 0, L_t = Φ.  Backwards from r_n = 0, N_n = 0 the recursion is
+ * exactly that of yfm_smooth_batch:
+ *     r_{t−1} = s_t + L_t' r_t,   N_{t−1} = W_t + L_t' N_t L_t,
+ *     β̂_t = a_t + P_t r_{t−1},   V_t = P_t − P_t N_{t−1} P_t,   C_t = (I − P_{t+1} N_t) L_t P_t,  t = 1 … n − 1.
+ * All n columns of the window condition the result; n = 1 is valid.
+ *   Outputs: the layout of yfm_smooth_batch with M = 4 — beta_s 4 × T × B, V_s 4 × 4 × T × B, symmetric to the bit, C_s
+ * 4 × 4 × (T − 1) × B, which may be NULL; slots past a window are NaN.
+ *   Unavailable: all of a candidate's outputs are NaN, and yfm_last_batch_grad_unavailable counts it, where
+ * initialize_filter would throw; where the window's log-likelihood is −Inf or NaN; where a data column's
+ * det(σ²I + P_t G_t) is ≤ 0 or not finite, by the rule of yfm_tvl_loglik_grad_batch's kernel — which, like the loss,
+ * lets a negative determinant pass at column 1 alone: a non-stationary Φ gives an indefinite P_1, the reference goes on
+ * filtering, and the smoothed moments remain the Gaussian conditional's; and where any output inside the window is not
+ * finite.  TVλ has no deferral list.
+ *   The forward pass is the TVλ trajectory launch of yfm_filter_states at the context's precision (YFM_PREC_CERTIFIED:
+ * double-double); the backward sweep is FP64.  Candidates go in chunks: the record (20 doubles × (T − 1) per candidate),
+ * each staging buffer and the launch's own scratch stay within 128 MiB each.  The TVλ forward picks its lane count from
+ * the batch size, and every chunk's launch takes the whole batch's: a candidate's outputs do not depend on its position
+ * in the batch, or on the other candidates of a batch of the same size.  Across batch sizes the recorded bits may differ,
+ * and only the parity rule is promised (per array and step, within 1e-9 of a dense FP64 statement of the same smoother,
+ * or at least as close to the 40-digit truth as that statement is).
+ *   yfm_tvl_smooth_batch takes host pointers and is synchronous; yfm_tvl_smooth_batch_device takes device pointers and
+ * only enqueues on hip_stream, with the ordering rules of yfm_loglik_batch_device.  Every N the TVλ log-likelihood takes,
+ * both parameter spaces, a per-candidate T_use.  B = 0 succeeds.  Any model_kind but YFM_MODEL_TVL returns
+ * YFM_EUNSUPPORTED: DNS and GNS5 have yfm_smooth_batch, the λ and neural kinds are not Kalman filters and have nothing
+ * to smooth.  Additive: YFM_ABI_VERSION stays 5; a library that has the symbols has the feature. */
+int yfm_tvl_smooth_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                         const int* T_use, double* beta_s, double* V_s, double* C_s);
+int yfm_tvl_smooth_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
+                                const int* d_T_use, double* d_beta_s, double* d_V_s, double* d_C_s, void* hip_stream);
 
 /* One Optim.NelderMead run per chain on a block of coordinates — what estimate_steps! does for a parameter group
  * that uses opt1 (optimization.jl:218-247 with :442-451, :479: NelderMead, `iterations`, g_tol), without the outer

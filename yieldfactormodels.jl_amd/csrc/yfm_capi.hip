@@ -297,6 +297,8 @@ struct Launch {
   const PanelView* panel = nullptr;  // nullptr: the context's panel
   bool continues = false;  // a later chunk of a pipelined batch: accumulates into the previous chunk's counters
   int share = 1;           // launches of this size the caller keeps in flight at once (yfm::loglik_device_ws)
+  int lanes_B = 0;         // TVλ: the batch size its lane count is chosen from (0: this launch's B; a chunk of a
+                           // larger batch sets the whole batch's, so a candidate's bits do not depend on its chunk)
   const yfm::MsedRecord* msed_rec = nullptr;  // λ models: the trajectory outputs this launch writes (nullptr: the loss)
   double* msed_grad = nullptr;  // λ and neural models: 12×B device, ∂loss/∂(δ, Φ) written with the loss
   double* msed_fullgrad = nullptr;  // λ and neural models: P×B device, ∂loss/∂θ written with the loss
@@ -376,7 +378,8 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
         : q.msed_rec ? yfm::launch_msed_record(q.kind, a, lanes, *q.msed_rec)
                      : yfm::launch_msed(q.kind, a, lanes);
   } else if (q.kind == YFM_MODEL_TVL) {
-    int lanes = yfm::tvl_lanes_for(B, ctx->N, q.share);
+    const int Bl = q.lanes_B > 0 ? q.lanes_B : B;
+    int lanes = yfm::tvl_lanes_for(Bl, ctx->N, q.share);
     const char* const ov = yfm::env_or("YFM_TVL_LANES", nullptr);  // tuning override: 1, 2, 4, …, 64
     if (ov) {
       const int l = std::atoi(ov);
@@ -384,7 +387,7 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
     }
     yfm::TvlGaps g;
     if (ctx->precision == YFM_PREC_CERTIFIED) {
-      lanes = yfm::tvl_dd_lanes_for(B, ctx->N, ov ? lanes : 0, q.share);
+      lanes = yfm::tvl_dd_lanes_for(Bl, ctx->N, ov ? lanes : 0, q.share);
       // the context's panel has its column statistics already; a panel of the launch's own gets them here
       const bool own_panel = q.panel && q.panel->raw != static_cast<const double*>(ctx->raw.p);
       const size_t rec_bytes = yfm::tvl_dd_scratch_bytes(B);
@@ -806,7 +809,7 @@ int hessian_chunks(yfm_ctx* ctx, const Launch& q, double h, const double* d_grad
 int check_smooth(yfm_ctx* ctx, const char* what, int kind, int space, int P, int B) {
   if (kind == YFM_MODEL_TVL)
     return set_error(YFM_EUNSUPPORTED, "%s is built for YFM_MODEL_DNS and YFM_MODEL_GNS5: the TVlambda model's loadings "
-                     "move with the state, and its extended smoother is not built (model_kind %d)", what, kind);
+                     "move with the state, and its extended smoother is yfm_tvl_smooth_batch (model_kind %d)", what, kind);
   if (yfm::msed_kind(kind))
     return set_error(YFM_EUNSUPPORTED, "%s is built for YFM_MODEL_DNS and YFM_MODEL_GNS5: the %s kinds are not Kalman "
                      "filters and have no state covariance to smooth (model_kind %d)", what,
@@ -815,6 +818,22 @@ int check_smooth(yfm_ctx* ctx, const char* what, int kind, int space, int P, int
   if (ctx->N > yfm::smooth_max_n())
     return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the %d of the smoother's backward sweep", ctx->N,
                      yfm::smooth_max_n());
+  return YFM_OK;
+}
+
+// The TVλ extended smoother's model check: yfm_tvl_smooth.hip, every N the TVλ filter takes.
+int check_tvl_smooth(yfm_ctx* ctx, const char* what, int kind, int space, int P, int B) {
+  if (kind == YFM_MODEL_DNS || kind == YFM_MODEL_GNS5)
+    return set_error(YFM_EUNSUPPORTED, "%s is built for YFM_MODEL_TVL only: the fixed-loading models' smoother is "
+                     "yfm_smooth_batch (model_kind %d)", what, kind);
+  if (yfm::msed_kind(kind))
+    return set_error(YFM_EUNSUPPORTED, "%s is built for YFM_MODEL_TVL only: the %s kinds are not Kalman filters, "
+                     "there is nothing to smooth (model_kind %d)", what, yfm::msedn_kind(kind) ? "neural" : "lambda",
+                     kind);
+  if (int r = check_batch(ctx, kind, space, P, B)) return r;
+  if (ctx->N > yfm::tvl_smooth_max_n())
+    return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the %d of the TVλ smoother's backward sweep", ctx->N,
+                     yfm::tvl_smooth_max_n());
   return YFM_OK;
 }
 
@@ -833,6 +852,22 @@ int smooth_chunk(int kind, int M, int T, int B) {
   return chunk;
 }
 
+// The same for the TVλ extended smoother (M = 4): the record (20 doubles × (T − 1)), each output array and the work
+// records of the chunk's TVλ launch under the context's precision, each within kInfoChunkBytes.
+int tvl_smooth_chunk(const yfm_ctx* ctx, int T, int B) {
+  const size_t rec = sizeof(double) * 20 * (size_t)std::max(T - 1, 1);
+  const size_t out = sizeof(double) * 16 * (size_t)T;
+  int chunk = info_chunk(std::max(rec, out), B);
+  while (chunk > 1) {
+    const size_t need = ctx->precision == YFM_PREC_CERTIFIED ? yfm::tvl_dd_scratch_bytes(chunk)
+                                                             : yfm::tvl_scratch_bytes(chunk);
+    if (need <= kInfoChunkBytes) break;
+    const int fit = (int)((double)chunk * ((double)kInfoChunkBytes / (double)need));
+    chunk = std::max(1, std::min(chunk - 1, fit));
+  }
+  return chunk;
+}
+
 // The smoother over the candidates of q (θ, T_use and the logliks q.out on the device), chunk by chunk on q.stream:
 // the trajectory launch of the chunk into the record scratch, then the backward sweep.  h_beta null: the sweep writes
 // into the caller's device arrays d_beta, d_V, d_C (whole batch).  Otherwise it writes a chunk's outputs into the
@@ -842,7 +877,8 @@ int smooth_chunks(yfm_ctx* ctx, const Launch& q, double* d_beta, double* d_V, do
   yfm::Workspace& w = ctx->own;
   const int M = state_dim(q.kind), T = ctx->T;
   const size_t nM = (size_t)M * T, nV = (size_t)M * M * T, nC = (size_t)M * M * (size_t)(T - 1);
-  const int chunk = smooth_chunk(q.kind, M, T, q.B);
+  const bool tvl = q.kind == YFM_MODEL_TVL;
+  const int chunk = tvl ? tvl_smooth_chunk(ctx, T, q.B) : smooth_chunk(q.kind, M, T, q.B);
   const size_t steps = (size_t)std::max(T - 1, 1) * chunk;
   YFM_HIP_CHECK(w.smooth_rec_beta.ensure(sizeof(double) * steps * M));
   YFM_HIP_CHECK(w.smooth_rec_P.ensure(sizeof(double) * steps * M * M));
@@ -860,6 +896,7 @@ int smooth_chunks(yfm_ctx* ctx, const Launch& q, double* d_beta, double* d_V, do
     qc.T_use = q.T_use ? q.T_use + b0 : nullptr;
     qc.out = q.out + b0;
     qc.continues = b0 > 0;  // one batch: the chunks' counters add up
+    qc.lanes_B = q.B;       // TVλ: every chunk's forward launch at the whole batch's lane count
     if (T >= 2) {           // a one-column panel has no recorded step: the sweep takes a_1, P_1 alone
       qc.rec_beta = static_cast<double*>(w.smooth_rec_beta.p);
       qc.rec_P = static_cast<double*>(w.smooth_rec_P.p);
@@ -873,10 +910,12 @@ int smooth_chunks(yfm_ctx* ctx, const Launch& q, double* d_beta, double* d_V, do
     double* const ob = h_beta ? static_cast<double*>(w.smooth_beta.p) : d_beta + nM * b0;
     double* const oV = h_beta ? static_cast<double*>(w.smooth_V.p) : d_V + nV * b0;
     double* const oC = h_beta ? (want_C ? static_cast<double*>(w.smooth_C.p) : nullptr) : (d_C ? d_C + nC * b0 : nullptr);
-    // measurement only (tools/bench_smooth.py): YFM_SMOOTH_SWEEP=0 leaves the sweep out, so the forward trajectory
+    // measurement only (tools/bench_smooth.py, tools/bench_tvl_smooth.py): YFM_SMOOTH_SWEEP=0 leaves the sweep out, so the forward trajectory
     // launch can be timed alone; the outputs are then not written
     if (std::atoi(yfm::env_or("YFM_SMOOTH_SWEEP", "1")) == 0) continue;
-    const hipError_t e = yfm::launch_smooth(q.kind, a, qc.out, static_cast<unsigned char*>(w.smooth_skip.p), ob, oV, oC);
+    const hipError_t e =
+        tvl ? yfm::launch_tvl_smooth(a, qc.out, ob, oV, oC)
+            : yfm::launch_smooth(q.kind, a, qc.out, static_cast<unsigned char*>(w.smooth_skip.p), ob, oV, oC);
     if (e != hipSuccess) {
       w.bank_dirty = true;
       return set_error(YFM_EHIP, "smoother kernel launch: %s", hipGetErrorString(e));
@@ -1280,6 +1319,35 @@ int yfm_smooth_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const
                             const int* d_T_use, double* d_beta_s, double* d_V_s, double* d_C_s, void* hip_stream) {
   if (int r = check_ctx(ctx)) return r;
   if (int r = check_smooth(ctx, "yfm_smooth_batch_device", model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_beta_s || !d_V_s)) return set_error(YFM_EINVAL, "null d_theta, d_beta_s or d_V_s");
+  YFM_HIP_CHECK(ctx->own.smooth_ll.ensure(sizeof(double) * (size_t)(B > 0 ? B : 1)));
+  const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use,
+                                 static_cast<double*>(ctx->own.smooth_ll.p), static_cast<hipStream_t>(hip_stream));
+  if (B == 0) return launch(ctx, q);
+  return smooth_chunks(ctx, q, d_beta_s, d_V_s, d_C_s, nullptr, nullptr, nullptr, false);
+}
+
+int yfm_tvl_smooth_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                         const int* T_use, double* beta_s, double* V_s, double* C_s) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_tvl_smooth(ctx, "yfm_tvl_smooth_batch", model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !beta_s || !V_s)) return set_error(YFM_EINVAL, "null theta, beta_s or V_s");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  if (B == 0) {
+    if (int r = launch(ctx, q)) return r;
+  } else if (int r = smooth_chunks(ctx, q, nullptr, nullptr, nullptr, beta_s, V_s, C_s, C_s != nullptr)) {
+    return r;
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+int yfm_tvl_smooth_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
+                                const int* d_T_use, double* d_beta_s, double* d_V_s, double* d_C_s, void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check_tvl_smooth(ctx, "yfm_tvl_smooth_batch_device", model_kind, param_space, P, B)) return r;
   if (B > 0 && (!d_theta || !d_beta_s || !d_V_s)) return set_error(YFM_EINVAL, "null d_theta, d_beta_s or d_V_s");
   YFM_HIP_CHECK(ctx->own.smooth_ll.ensure(sizeof(double) * (size_t)(B > 0 ? B : 1)));
   const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use,

@@ -106,6 +106,13 @@ hipError_t launch_hessian_assemble(const double* pts_grad, const double* steps, 
 int smooth_max_n();
 hipError_t launch_smooth(int kind, const LaunchArgs& a, const double* ll, unsigned char* skip, double* beta_s,
                          double* V_s, double* C_s);
+// The backward sweep of the TVλ extended smoother (yfm_tvl_smooth.hip; every N the TVλ filter takes), enqueued after
+// the TVλ trajectory launch of the a.B candidates at a.theta whose record a.rec_beta / a.rec_P (stride a.rec_len ≥
+// T − 1) and counters a.flags it reads: β̂ (4 × T × B), V (4 × 4 × T × B) and, C_s not null, the lag-one covariances
+// (4 × 4 × (T − 1) × B), NaN past a window and in all of a candidate whose ll[b] is not finite, whose initial state is
+// singular, that has a data column with det(σ²I + P_tG_t) ≤ 0 or an output that is not finite (counted in a.flags[5]).
+int tvl_smooth_max_n();
+hipError_t launch_tvl_smooth(const LaunchArgs& a, const double* ll, double* beta_s, double* V_s, double* C_s);
 // TVλ loglik gradient (yfm_tvl_grad.hip), enqueued after the loglik launch whose counter bank a.flags it adds to:
 // ∂loglik/∂θ into grad_out (31×B) from the FP64 tangent recursion over a.raw (NaN flags from a.panel), NaN where
 // ll[b] is not finite or the recursion's own value or tangents are not usable (those counted in a.flags[5]).

@@ -122,6 +122,23 @@ function smooth(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = CONST
     βs, V, C
 end
 
+"Extended Kalman smoother of the TVλ model — an extension, linearised once at the forward pass's predicted states:
+(β̂[4, T, B], V[4, 4, T, B], C[4, 4, T-1, B]) as `smooth` returns them, so λ̂[t, b] = 0.01 + exp(β̂[4, t, b]) is the decay
+path given all the data.  NaN beyond a window and for an unavailable candidate (ll -Inf / NaN, a data column with
+det(σ²I + P_tG_t) ≤ 0, a non-finite output: yfm.h; counted by yfm_last_batch_grad_unavailable).  lag_one = false skips C."
+function tvl_smooth(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = CONSTRAINED,
+                    T_use::Union{Nothing,Vector{Cint}} = nothing, lag_one::Bool = true)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    M, T = 4, size(data, 2)
+    βs, V = Array{Float64}(undef, M, T, B), Array{Float64}(undef, M, M, T, B)
+    C = lag_one ? Array{Float64}(undef, M, M, max(T - 1, 0), B) : nothing
+    GC.@preserve Θ βs V C T_use check(@ccall LIB.yfm_tvl_smooth_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, βs::Ptr{Cdouble},
+        V::Ptr{Cdouble}, (lag_one ? pointer(C) : Ptr{Cdouble}(C_NULL))::Ptr{Cdouble})::Cint)
+    βs, V, C
+end
+
 "TVλ loglik and its gradient: (ll[B], grad[31, B]), grad[:, b] = ∂(+loglik)/∂Θ[:, b] in `space` — estimate!'s
 ForwardDiff gradient (optimization.jl:367, :10-23) of the EKF of filter.jl:12-80.  ll is bitwise loglik_batch's under the
 context's precision; the gradient is the FP64 tangent recursion.  NaN gradient columns where ll is -Inf / NaN or the

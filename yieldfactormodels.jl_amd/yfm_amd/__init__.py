@@ -23,6 +23,7 @@ from . import inference
 from .inference import covariance, standard_errors_, standard_errors_batch
 from . import smoothing
 from .smoothing import em_moments, smooth_, smooth_batch, smoothed_yields
+from .smoothing import tvl_smooth_, tvl_smooth_batch, tvl_smoothed_yields
 
 __all__ = [
     "KIND_DNS", "KIND_TVL", "KIND_GNS", "SPACE_CONSTRAINED", "SPACE_UNCONSTRAINED", "n_params", "param_layout",
@@ -38,4 +39,5 @@ __all__ = [
     "compute_neural_loss_fullgrad_batch", "estimate_neural_lbfgs_batch", "estimate_neural_",
     "inference", "covariance", "standard_errors_batch", "standard_errors_",
     "smoothing", "smooth_batch", "smooth_", "smoothed_yields", "em_moments",
+    "tvl_smooth_batch", "tvl_smooth_", "tvl_smoothed_yields",
 ]

@@ -85,6 +85,10 @@ SIGNATURES = {
                                         _D]),
     "yfm_smooth_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int, _V, _V,
                                                _V, _V, _V]),
+    "yfm_tvl_smooth_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D, _D,
+                                            _D]),
+    "yfm_tvl_smooth_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int, _V,
+                                                   _V, _V, _V, _V]),
 }
 
 ABI_VERSION = 5

@@ -314,7 +314,7 @@ class Engine:
     @staticmethod
     def _smooth_kinds(kind, what):
         if kind not in (KIND_DNS, KIND_GNS):
-            gap = ("the TVλ model's extended smoother is not built" if kind == KIND_TVL
+            gap = ("the TVλ model's extended smoother is tvl_smooth" if kind == KIND_TVL
                    else "the λ and neural kinds are not Kalman filters and have no state covariance to smooth")
             raise NotImplementedError(f"{what} is built for the DNS and GNS5 models (kinds {KIND_DNS}, {KIND_GNS}), not "
                                       f"kind {kind}: {gap}")
@@ -347,6 +347,44 @@ class Engine:
                                                     ctypes.c_void_p(d_beta_s), ctypes.c_void_p(d_V_s),
                                                     ctypes.c_void_p(d_C_s) if d_C_s else None,
                                                     ctypes.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def _tvl_smooth_kinds(kind, what):
+        if kind != KIND_TVL:
+            gap = ("the fixed-loading models' smoother is smooth" if kind in (KIND_DNS, KIND_GNS)
+                   else "the λ and neural kinds are not Kalman filters: there is nothing to smooth")
+            raise NotImplementedError(f"{what} is built for the TVλ model (kind {KIND_TVL}), not kind {kind}: {gap}")
+
+    def tvl_smooth(self, kind: int, theta, space: int = 0, T_use=None, lag_one: bool = True):
+        """(beta_s[4, T, B], V_s[4, 4, T, B], C_s[4, 4, T−1, B] or None): the extended Kalman smoother of the TVλ model
+        (include/yfm.h yfm_tvl_smooth_batch), linearised once at the forward pass's predicted states — β̂_t =
+        E[β_t | y_1..n] in slot t − 1, its covariance V_t and, ``lag_one``, C_t = Cov(β_{t+1}, β_t | y_1..n), with
+        n = T_use[b] (None: every column).  NaN beyond a window, and in all of a candidate whose loglik is −Inf or NaN,
+        that has a data column with det(σ²I + P_tG_t) ≤ 0 or an output that is not finite
+        (:meth:`last_grad_unavailable` counts them)."""
+        self._tvl_smooth_kinds(kind, "tvl_smooth")
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        M, T = state_dim(kind), self.T
+        bs = np.empty((M, T, B), dtype=np.float64, order="F")
+        Vs = np.empty((M, M, T, B), dtype=np.float64, order="F")
+        Cs = np.empty((M, M, max(T - 1, 0), B), dtype=np.float64, order="F") if lag_one else None
+        _lib.check(self.lib.yfm_tvl_smooth_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                                 _lib.iptr(self._tuse(T_use, B)), _lib.dptr(bs), _lib.dptr(Vs),
+                                                 _lib.dptr(Cs) if lag_one else None))
+        return bs, Vs, Cs
+
+    def tvl_smooth_device(self, kind: int, d_theta: int, P: int, B: int, d_beta_s: int, d_V_s: int,
+                          d_C_s: int | None = None, space: int = 0, d_T_use: int | None = None,
+                          stream: int | None = None) -> None:
+        """Device-pointer variant of :meth:`tvl_smooth` (raw addresses; d_beta_s 4×T×B, d_V_s 4×4×T×B, d_C_s
+        4×4×(T−1)×B column-major or None); asynchronous on ``stream``."""
+        self._tvl_smooth_kinds(kind, "tvl_smooth_device")
+        _lib.check(self.lib.yfm_tvl_smooth_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
+                                                        ctypes.c_void_p(d_T_use) if d_T_use else None,
+                                                        ctypes.c_void_p(d_beta_s), ctypes.c_void_p(d_V_s),
+                                                        ctypes.c_void_p(d_C_s) if d_C_s else None,
+                                                        ctypes.c_void_p(stream) if stream else None))
 
     @staticmethod
     def _batch(theta, kind):

@@ -17,7 +17,7 @@ SMOOTH_KINDS = (_p.KIND_DNS, _p.KIND_GNS)
 def _check_kind(kind, what):
     if kind in SMOOTH_KINDS:
         return
-    gap = ("the TVλ model's extended smoother is not built" if kind == _p.KIND_TVL
+    gap = ("the TVλ model's extended smoother is tvl_smooth_batch" if kind == _p.KIND_TVL
            else "the λ and neural kinds are not Kalman filters and have no state covariance to smooth")
     raise NotImplementedError(f"{what} is built for the DNS and GNS5 models only (model kind {kind}): {gap}")
 
@@ -44,6 +44,63 @@ def smooth_(model, data, params) -> dict:
     out = {k: v[..., 0] for k, v in r.items()}
     out["available"] = bool(r["available"][0])
     return out
+
+
+def _check_tvl(kind, what):
+    if kind == _p.KIND_TVL:
+        return
+    gap = ("the fixed-loading models' smoother is smooth_batch" if kind in SMOOTH_KINDS
+           else "the λ and neural kinds are not Kalman filters: there is nothing to smooth")
+    raise NotImplementedError(f"{what} is built for the TVλ model only (model kind {kind}): {gap}")
+
+
+def lambda_path(factors, cov):
+    """(λ̂, its standard deviation) from TVλ smoothed arrays (4, T[, B]) and (4, 4, T[, B]): λ̂_t = 0.01 + exp(β̂₄,ₜ) and,
+    by the delta method, sd λ̂_t = (λ̂_t − 0.01)·√V₄₄,ₜ.  NaN where the inputs are."""
+    f = np.asarray(factors, dtype=np.float64)
+    V = np.asarray(cov, dtype=np.float64)
+    e = np.exp(f[3])
+    with np.errstate(invalid="ignore"):
+        return 0.01 + e, e * np.sqrt(V[3, 3])
+
+
+def tvl_smooth_batch(model, data, theta_c, T_use=None) -> dict:
+    """The extended Kalman smoother of the TVλ model at the estimates θ_c (31×B constrained; column b on the window
+    ``data[:, :T_use[b]]``), linearised once at the forward pass's predicted states (include/yfm.h
+    yfm_tvl_smooth_batch).  Returns the dict of :func:`smooth_batch` — ``factors`` (4, T, B), ``cov`` (4, 4, T, B),
+    ``lag_one_cov`` (4, 4, T − 1, B), ``available`` (B,) — and the path of the decay parameter given all the data:
+    ``lambda_`` (T, B), λ̂_t = 0.01 + exp(β̂₄,ₜ), and ``lambda_sd`` (T, B), its delta-method standard deviation
+    (λ̂_t − 0.01)·√V₄₄,ₜ."""
+    from . import models as _m
+    _check_tvl(model.kind, "tvl_smooth_batch")
+    Th = np.asarray(theta_c, dtype=np.float64)
+    if Th.ndim == 1:
+        Th = Th[:, None]
+    eng = _m._engine(model, data)
+    bs, Vs, Cs = eng.tvl_smooth(model.kind, np.asfortranarray(Th), space=_p.SPACE_CONSTRAINED, T_use=T_use)
+    lam, sd = lambda_path(bs, Vs)
+    return dict(factors=bs, cov=Vs, lag_one_cov=Cs, available=np.isfinite(bs[0, 0, :]), lambda_=lam, lambda_sd=sd)
+
+
+def tvl_smooth_(model, data, params) -> dict:
+    """:func:`tvl_smooth_batch` for one constrained parameter vector: the same dict without the batch axis."""
+    r = tvl_smooth_batch(model, data, np.asarray(params, dtype=np.float64).reshape(-1, 1))
+    out = {k: v[..., 0] for k, v in r.items()}
+    out["available"] = bool(r["available"][0])
+    return out
+
+
+def tvl_smoothed_yields(model, factors) -> np.ndarray:
+    """The fitted curves of the TVλ model (N × T) from one candidate's ``factors`` (4 × T): column t is
+    Z(λ̂_t)[:, 1:3]·β̂_t[1:3] with λ̂_t = 0.01 + exp(β̂₄,ₜ) (tvλdns.jl:53-64); NaN columns stay NaN."""
+    _check_tvl(model.kind, "tvl_smoothed_yields")
+    f = np.asarray(factors, dtype=np.float64)
+    m = np.asarray(model.base.maturities, dtype=np.float64)[:, None]
+    with np.errstate(all="ignore"):
+        tau = (0.01 + np.exp(f[3]))[None, :] * m
+        z = np.exp(-tau)
+        s = (1.0 - z) / tau
+        return f[0][None, :] + s * f[1][None, :] + (s - z) * f[2][None, :]
 
 
 def loadings(model, theta_c) -> np.ndarray:

@@ -15,7 +15,8 @@
 //   2. every lane runs the short serial chain r_{t−1} = s_t + L_t'r_t, N_{t−1} = W_t + L_t'N_tL_t over the chunk's
 //      columns on wave-uniform values (r and N stay in registers across chunks) and keeps r_t, N_t of its own column
 //      as the chain passes it;
-//   3. lane ℓ forms β̂_t, V_t and C_t of its column and stores them.
+//   3. lane ℓ forms a_{t|t} = G⁻¹u_t (G⁻¹ from LDS; u_t = Z'y_t − σ²s_t kept from phase 1), then β̂_t, V_t and C_t of its
+//      column, and stores them.
 // Slots past a candidate's window are written as NaN by the same wave, and all of an unavailable candidate's slots:
 // a loglik that is not finite (−Inf, or NaN where initialize_filter throws), a candidate on the deferral list (`skip`),
 // an output that is not finite.  Those candidates raise flags[5].  No memset of the outputs is needed.
@@ -66,6 +67,7 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
   __shared__ double zs[64 * M];                       // Z, row i at zs[i M …]
   __shared__ double init_lds[sm::InitCov<M>::kDoubles];  // the P_1 system
   __shared__ double ops[kOps * kSmoothChunk];          // operand k of column j at ops[64 k + j]
+  __shared__ double gis[M * M];                        // G⁻¹, row-major
 
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
@@ -108,6 +110,15 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
   for (int j = 0; j < M; ++j)
 #pragma unroll
     for (int k = j + 1; k < M; ++k) G[k][j] = G[j][k];
+
+  {  // G⁻¹ for the filtered mean: wave-uniform, formed once and read from LDS as broadcasts
+    double Ginv[M * M];
+    sm::gram_inverse<M>(G, Ginv);
+#pragma unroll
+    for (int k = 0; k < M * M; ++k)
+      if (lane == 0) gis[k] = Ginv[k];
+  }
+  wave_lds_sync();
 
   double a1[M], P1[M][M];
   bool ok = sm::init_mean<M>(m, a1);
@@ -160,10 +171,9 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
     double af[M], Pf[M][M];
     {
       sm::StepOps<M> o;
-      sm::step_operands<M>(m, G, a, Pm, zy, missing, o);
+      sm::step_operands_core<M>(m, G, a, Pm, zy, missing, o);
 #pragma unroll
       for (int i = 0; i < M; ++i) {
-        af[i] = o.af[i];
         ops[kSmoothChunk * i + lane] = o.s[i];
 #pragma unroll
         for (int j = 0; j < M; ++j) {
@@ -172,6 +182,9 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
           ops[kSmoothChunk * (M + M * M + i * M + j) + lane] = o.L[i][j];
         }
       }
+      // a_{t|t} waits for phase 3, where the chain's registers are free: a (missing column) or G a_{t|t} until then
+#pragma unroll
+      for (int i = 0; i < M; ++i) af[i] = missing ? a[i] : o.u[i];
     }
     wave_lds_sync();
     // 2. the chain over the chunk's columns, last to first; this lane keeps r_t, N_t of its own column
@@ -208,6 +221,12 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
       for (int i = 0; i < M; ++i)
 #pragma unroll
         for (int j = 0; j < M; ++j) Pn[i][j] = lag ? pp[j * M + i] : 0.0;
+    }
+    {  // af holds a_t (missing column) or u_t = G a_{t|t} since phase 1
+      double ga[M];
+#pragma unroll
+      for (int i = 0; i < M; ++i) ga[i] = af[i];
+      sm::filtered_mean<M>(gis, ga, ga, missing, af);
     }
     double bs[M], V[M][M], C[M][M];
     const bool fin = sm::step_outputs<M>(m, af, Pf, rt, Nt, lag, Pn, bs, V, C);

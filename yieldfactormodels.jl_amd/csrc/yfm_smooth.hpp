@@ -8,8 +8,9 @@
 //     B_t = σ²I + G P_t,   s_t = B_t⁻¹(Z'y_t − G a_t),   W_t = B_t⁻¹G,   E_t = σ²B_t⁻¹,   L_t = Φ(I − P_tW_t) = ΦE_t',
 // a missing column s_t = 0, W_t = 0, L_t = Φ, and backwards from r_n = 0, N_n = 0
 //     r_{t−1} = s_t + L_t'r_t,   N_{t−1} = W_t + L_t'N_tL_t.
-// The outputs are taken from the filtered moments a_{t|t} = a_t + P_ts_t and P_{t|t} = P_t − P_tW_tP_t = P_tE_t, which
-// never form I − P_tW_t by subtraction: with X_t = L_tP_t = ΦP_{t|t},
+// The outputs are taken from the filtered moments a_{t|t} = a_t + P_ts_t = G⁻¹(Z'y_t − σ²s_t) and
+// P_{t|t} = P_t − P_tW_tP_t = P_tE_t, which never form I − P_tW_t by subtraction nor add P_ts_t to a large a_t: with
+// X_t = L_tP_t = ΦP_{t|t},
 //     β̂_t = a_t + P_tr_{t−1} = a_{t|t} + X_t'r_t,
 //     V_t = P_t − P_tN_{t−1}P_t = P_{t|t} − X_t'N_tX_t,
 //     C_t = Cov(β_{t+1}, β_t | y_1..n) = (I − P_{t+1}N_t)X_t.
@@ -278,12 +279,48 @@ template <int M>
 struct StepOps {
   double s[M], W[M][M], L[M][M];  // the chain's operands
   double af[M], Pf[M][M];         // a_{t|t}, P_{t|t}
+  double u[M];                    // Z'y_t − σ²s_t = G a_{t|t}
 };
 
-// zy = Z'y_t (ignored at a missing column)
+// G⁻¹ (row-major M × M) by the pivoted elimination; false on an exact zero pivot
 template <int M>
-YFM_SHD void step_operands(const Model<M>& m, const double (&G)[M][M], const double (&a)[M], const double (&P)[M][M],
-                           const double (&zy)[M], bool missing, StepOps<M>& o) {
+YFM_SHD bool gram_inverse(const double (&G)[M][M], double (&Ginv)[M * M]) {
+  double A[M][M], X[M][M];
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) {
+      A[i][j] = G[i][j];
+      X[i][j] = (i == j) ? 1.0 : 0.0;
+    }
+  const bool ok = gauss_solve<M, M>(A, X);
+#pragma unroll
+  for (int i = 0; i < M; ++i)
+#pragma unroll
+    for (int j = 0; j < M; ++j) Ginv[i * M + j] = X[i][j];
+  return ok;
+}
+
+// a_{t|t} = G⁻¹(Z'y − σ²s), which is a + P s: G(a + P s) = G a + (B − σ²I)s = Z'y − σ²s.  It never adds P s to a, which
+// cancels where a_t is large beside β̂_t (column 1 of a candidate with an eigenvalue of Φ near or past 1).
+// Ginv = gram_inverse(G): the device forms it once per candidate and reads it from LDS
+template <int M>
+YFM_SHD void filtered_mean(const double* Ginv, const double (&a)[M], const double (&u)[M], bool missing,
+                           double (&af)[M]) {
+#pragma unroll
+  for (int i = 0; i < M; ++i) {
+    double x = 0.0;
+#pragma unroll
+    for (int k = 0; k < M; ++k) x = sfma(Ginv[i * M + k], u[k], x);
+    af[i] = missing ? a[i] : x;
+  }
+}
+
+// the chain's operands, P_{t|t} and u of a column (everything of StepOps but a_{t|t}); zy = Z'y_t (ignored at a missing
+// column)
+template <int M>
+YFM_SHD void step_operands_core(const Model<M>& m, const double (&G)[M][M], const double (&a)[M],
+                                const double (&P)[M][M], const double (&zy)[M], bool missing, StepOps<M>& o) {
   constexpr int R = 2 * M + 1;
   double Bm[M][M], X[M][R];
 #pragma unroll
@@ -306,6 +343,7 @@ YFM_SHD void step_operands(const Model<M>& m, const double (&G)[M][M], const dou
 #pragma unroll
   for (int i = 0; i < M; ++i) {
     o.s[i] = missing ? 0.0 : X[i][M];
+    o.u[i] = sfma(-m.sigma2, X[i][M], zy[i]);
 #pragma unroll
     for (int j = i; j < M; ++j) {
       const double w = 0.5 * (X[i][j] + X[j][i]);
@@ -323,13 +361,9 @@ YFM_SHD void step_operands(const Model<M>& m, const double (&G)[M][M], const dou
       for (int k = 0; k < M; ++k) s = sfma(m.Phi[i][k], X[j][M + 1 + k], s);
       o.L[i][j] = missing ? m.Phi[i][j] : s;
     }
-  // a_{t|t} = a + P s,  P_{t|t} = P E (upper triangle, mirrored)
+  // P_{t|t} = P E (upper triangle, mirrored)
 #pragma unroll
   for (int i = 0; i < M; ++i) {
-    double s = a[i];
-#pragma unroll
-    for (int k = 0; k < M; ++k) s = sfma(P[i][k], X[k][M], s);
-    o.af[i] = missing ? a[i] : s;
 #pragma unroll
     for (int j = i; j < M; ++j) {
       double p = 0.0;
@@ -339,6 +373,16 @@ YFM_SHD void step_operands(const Model<M>& m, const double (&G)[M][M], const dou
       o.Pf[j][i] = o.Pf[i][j];
     }
   }
+}
+
+// all of StepOps, with G⁻¹ formed here (the host driver's call; the device calls the two pieces)
+template <int M>
+YFM_SHD void step_operands(const Model<M>& m, const double (&G)[M][M], const double (&a)[M], const double (&P)[M][M],
+                           const double (&zy)[M], bool missing, StepOps<M>& o) {
+  double Ginv[M * M];
+  gram_inverse<M>(G, Ginv);
+  step_operands_core<M>(m, G, a, P, zy, missing, o);
+  filtered_mean<M>(Ginv, a, o.u, missing, o.af);
 }
 
 // r ← s + L'r,  N ← W + L'NL (upper triangle, mirrored)

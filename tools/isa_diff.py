@@ -1,13 +1,14 @@
 """Compare the gfx950 device code of this tree with a git revision's, kernel by kernel — the acceptance gate for a
 refactor that must not change what the compiler emits.
 
-    python tools/isa_diff.py [<rev>] [<tu> ...]
+    python tools/isa_diff.py [--keep <dir>] [<rev>] [<tu> ...]
 
 (rev defaults to HEAD~1; tu = a csrc file stem, e.g. yfm_kernels; default: every csrc/*.hip.)  Each translation
 unit of both trees is compiled with build_native's compiler and flags plus --cuda-device-only -S.  Per symbol, the
 instruction stream (comments dropped, .LBB<n>_<m> labels renumbered) and the kernel descriptor's .amdhsa_* lines
 are compared as text; nothing is looked for inside them.  Exits non-zero on any difference or on a symbol present
-on one side only.  yfm_kernels alone takes about two minutes per side."""
+on one side only.  yfm_kernels alone takes about two minutes per side.  With --keep, the two streams compared for
+each differing symbol are written to <dir>/<tu>/<symbol>.{old,new}.s, for a plain diff to show what moved."""
 import re
 import subprocess
 import sys
@@ -58,6 +59,14 @@ def symbols(path: Path) -> dict:
 
 def main() -> int:
     args = sys.argv[1:]
+    keep = None
+    if "--keep" in args:
+        i = args.index("--keep")
+        if i + 1 >= len(args):
+            print("--keep takes a directory", file=sys.stderr)
+            return 2
+        keep = Path(args[i + 1])
+        del args[i:i + 2]
     rev = args.pop(0) if args else "HEAD~1"
     stems = args or sorted(p.stem for p in BN.CSRC.glob("*.hip"))
     bad = 0
@@ -83,6 +92,10 @@ def main() -> int:
                     verdict = "same"
                 else:
                     verdict = f"differs (lines {len(a[name])} → {len(b[name])})"
+                    if keep:
+                        (keep / stem).mkdir(parents=True, exist_ok=True)
+                        for side, lines in (("old", a[name]), ("new", b[name])):
+                            (keep / stem / f"{name}.{side}.s").write_text("\n".join(lines) + "\n")
                 bad += verdict != "same"
                 print(f"{stem} {name}: {verdict}")
     print(f"{bad} differing" if bad else "all same")

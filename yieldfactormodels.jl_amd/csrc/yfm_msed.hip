@@ -31,13 +31,14 @@
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
 #include "yfm_msed.hpp"
-#include "yfm_msed_tree.hpp"
+#include "yfm_msed_pass.hpp"
 
 namespace yfm {
 
 namespace {
 
 using namespace msedtree;  // the mapping's constants and the summation tree (yfm_msed_tree.hpp)
+using namespace msedpass;  // the staging, the epilogue and the host dispatch (yfm_msed_pass.hpp)
 
 using namespace msed;
 
@@ -151,25 +152,11 @@ __global__ __launch_bounds__(kMsedBlock) void msed_kernel(const double* __restri
   const int niter = s_iters_max;
   const int CHY = TC * N;
 
-  // ---- panel staging: chunk c (columns cTC .. cTC+TC−1) in LDS, chunk c+1 in registers ----
+  // ---- panel staging: chunk c (columns cTC .. cTC+TC−1) in LDS, chunk c+1 in registers (yfm_msed_pass.hpp, which
+  // says why the two lambdas stay) ----
   double pre[kMsedPre];
-  auto load_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      const size_t g = base + e;
-      pre[r] = (e < CHY && g < lim) ? Y[g] : 0.0;
-    }
-  };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      if (e < CHY) s_y[e] = pre[r];
-    }
-  };
+  auto load_chunk = [&](int c) { chunk_load(Y, c, CHY, T, N, tid, pre); };
+  auto store_chunk = [&]() { chunk_store(s_y, CHY, tid, pre); };
   if (niter > 0) {
     load_chunk(0);
     store_chunk();
@@ -337,12 +324,7 @@ __global__ __launch_bounds__(kMsedBlock) void msed_kernel(const double* __restri
     if (traj) return;
   }
   if (j != 0) return;
-  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
-  if (fail) {
-    ll = -__builtin_inf();
-    atomicAdd(&flags[1], 1u);
-  }
-  out[b] = ll;
+  out[b] = finish_loss(mse, fN, nobs, fail, flags);
 }
 
 // The first pass's statistics with Z'v of the comparison (yfm_msed.hpp, ∂loss/∂(δ, Φ)) through the same tree.
@@ -421,23 +403,8 @@ __global__ __launch_bounds__(kMsedBlock) void lambda_grad_kernel(const double* _
 
   // ---- panel staging, as msed_kernel ----
   double pre[kMsedPre];
-  auto load_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      const size_t gi = base + e;
-      pre[r] = (e < CHY && gi < lim) ? Y[gi] : 0.0;
-    }
-  };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      if (e < CHY) s_y[e] = pre[r];
-    }
-  };
+  auto load_chunk = [&](int c) { chunk_load(Y, c, CHY, T, N, tid, pre); };
+  auto store_chunk = [&]() { chunk_store(s_y, CHY, tid, pre); };
   if (niter > 0) {
     load_chunk(0);
     store_chunk();
@@ -551,39 +518,11 @@ __global__ __launch_bounds__(kMsedBlock) void lambda_grad_kernel(const double* _
   }
 
   if (!live || j != 0) return;
-  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
-  if (fail) {
-    ll = -__builtin_inf();
-    atomicAdd(&flags[1], 1u);
-  }
-  out[b] = ll;
+  out[b] = finish_loss(mse, fN, nobs, fail, flags);
   double go[kGrad];
   grad_finish(g, th, P, space, fN, nobs, fail, go);
 #pragma unroll
   for (int k = 0; k < kGrad; ++k) grad[(size_t)b * kGrad + k] = go[k];
-}
-
-template <int L, bool STATIC, bool HASB, bool SCALED>
-hipError_t launch_grad_variant(const LaunchArgs& a, int TC, double* grad) {
-  constexpr int GPB = kMsedBlock / L;
-  const int grid = (a.B + GPB - 1) / GPB;
-  const size_t shmem = sizeof(double) * (size_t)(2 * a.N + TC * a.N);
-  hipLaunchKernelGGL((lambda_grad_kernel<L, STATIC, HASB, SCALED>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
-                     a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, grad, a.flags,
-                     a.flags_next);
-  return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_grad_lanes(int kind, const LaunchArgs& a, int TC, double* grad) {
-  switch (kind) {
-    case YFM_MODEL_NS: return launch_grad_variant<L, true, false, false>(a, TC, grad);
-    case YFM_MODEL_SD_NS: return launch_grad_variant<L, false, true, false>(a, TC, grad);
-    case YFM_MODEL_RWSD_NS: return launch_grad_variant<L, false, false, false>(a, TC, grad);
-    case YFM_MODEL_SSD_NS: return launch_grad_variant<L, false, true, true>(a, TC, grad);
-    case YFM_MODEL_SRWSD_NS: return launch_grad_variant<L, false, false, true>(a, TC, grad);
-  }
-  return hipErrorInvalidValue;
 }
 
 // The statistics of the full gradient's first pass: the δ/Φ gradient's (the same sums through the same tree, the
@@ -704,23 +643,8 @@ __global__ __launch_bounds__(kMsedBlock) void lambda_fullgrad_kernel(const doubl
 
   // ---- panel staging, as msed_kernel ----
   double pre[kMsedPre];
-  auto load_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      const size_t gi = base + e;
-      pre[r] = (e < CHY && gi < lim) ? Y[gi] : 0.0;
-    }
-  };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      if (e < CHY) s_y[e] = pre[r];
-    }
-  };
+  auto load_chunk = [&](int c) { chunk_load(Y, c, CHY, T, N, tid, pre); };
+  auto store_chunk = [&]() { chunk_store(s_y, CHY, tid, pre); };
   if (niter > 0) {
     load_chunk(0);
     store_chunk();
@@ -856,78 +780,54 @@ __global__ __launch_bounds__(kMsedBlock) void lambda_fullgrad_kernel(const doubl
   }
 
   if (!live || j != 0) return;
-  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
-  if (fail) {
-    ll = -__builtin_inf();
-    atomicAdd(&flags[1], 1u);
-  }
-  out[b] = ll;
+  out[b] = finish_loss(mse, fN, nobs, fail, flags);
   double go[K + kGrad];
   if (fullgrad_finish<STATIC, HASB>(mdl, tn, g, th, P, space, fN, nobs, fail, go)) atomicAdd(&flags[5], 1u);
 #pragma unroll
   for (int k = 0; k < K + kGrad; ++k) grad[(size_t)b * (K + kGrad) + k] = go[k];
 }
 
-template <int L, bool STATIC, bool HASB, bool SCALED>
-hipError_t launch_fullgrad_variant(const LaunchArgs& a, int TC, double* grad) {
-  constexpr int GPB = kMsedBlock / L;
-  const int grid = (a.B + GPB - 1) / GPB;
-  const size_t shmem = sizeof(double) * (size_t)(2 * a.N + TC * a.N);
-  hipLaunchKernelGGL((lambda_fullgrad_kernel<L, STATIC, HASB, SCALED>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
-                     a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, grad, a.flags,
-                     a.flags_next);
-  return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_fullgrad_lanes(int kind, const LaunchArgs& a, int TC, double* grad) {
+// ---- host dispatch: one table over the kinds and one launch shape for the three kernels ----
+// f(Variant<L, STATIC, HASB, SCALED>) for a λ kind
+template <int L, class F>
+hipError_t with_kind(int kind, F&& f) {
   switch (kind) {
-    case YFM_MODEL_NS: return launch_fullgrad_variant<L, true, false, false>(a, TC, grad);
-    case YFM_MODEL_SD_NS: return launch_fullgrad_variant<L, false, true, false>(a, TC, grad);
-    case YFM_MODEL_RWSD_NS: return launch_fullgrad_variant<L, false, false, false>(a, TC, grad);
-    case YFM_MODEL_SSD_NS: return launch_fullgrad_variant<L, false, true, true>(a, TC, grad);
-    case YFM_MODEL_SRWSD_NS: return launch_fullgrad_variant<L, false, false, true>(a, TC, grad);
+    case YFM_MODEL_NS: return f(Variant<L, true, false, false>{});
+    case YFM_MODEL_SD_NS: return f(Variant<L, false, true, false>{});
+    case YFM_MODEL_RWSD_NS: return f(Variant<L, false, false, false>{});
+    case YFM_MODEL_SSD_NS: return f(Variant<L, false, true, true>{});
+    case YFM_MODEL_SRWSD_NS: return f(Variant<L, false, false, true>{});
   }
   return hipErrorInvalidValue;
 }
 
-template <int L, bool STATIC, bool HASB, bool SCALED>
-hipError_t launch_variant(const LaunchArgs& a, int TC, const MsedOut* ro) {
-  constexpr int GPB = kMsedBlock / L;
-  const int grid = (a.B + GPB - 1) / GPB;
+// launch(Variant, grid, shared-memory bytes, TC) starts the kernel of a kind at a lane count on a's batch and panel
+template <class F>
+hipError_t launch_with(int kind, const LaunchArgs& a, int lanes, F&& launch) {
+  const int TC = chunk_columns(a.N);
+  if (TC < 1) return hipErrorInvalidValue;
   const size_t shmem = sizeof(double) * (size_t)(2 * a.N + TC * a.N);
-  if (ro) {
-    hipLaunchKernelGGL((msed_kernel<L, STATIC, HASB, SCALED, true>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
-                       a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags, a.flags_next,
-                       *ro);
-  } else {
-    hipLaunchKernelGGL((msed_kernel<L, STATIC, HASB, SCALED, false>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
-                       a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags, a.flags_next,
-                       MsedOut{});
-  }
-  return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_lanes(int kind, const LaunchArgs& a, int TC, const MsedOut* ro) {
-  switch (kind) {
-    case YFM_MODEL_NS: return launch_variant<L, true, false, false>(a, TC, ro);
-    case YFM_MODEL_SD_NS: return launch_variant<L, false, true, false>(a, TC, ro);
-    case YFM_MODEL_RWSD_NS: return launch_variant<L, false, false, false>(a, TC, ro);
-    case YFM_MODEL_SSD_NS: return launch_variant<L, false, true, true>(a, TC, ro);
-    case YFM_MODEL_SRWSD_NS: return launch_variant<L, false, false, true>(a, TC, ro);
-  }
-  return hipErrorInvalidValue;
+  return with_lanes(lanes, [&](auto ln) {
+    return with_kind<decltype(ln)::value>(kind, [&](auto v) {
+      launch(v, grid_blocks(a.B, decltype(v)::L), shmem, TC);
+      return hipGetLastError();
+    });
+  });
 }
 
 hipError_t launch_any(int kind, const LaunchArgs& a, int lanes, const MsedOut* ro) {
-  const int TC = chunk_columns(a.N);
-  if (TC < 1) return hipErrorInvalidValue;
-  switch (lanes) {
-    case 4: return launch_lanes<4>(kind, a, TC, ro);
-    case 16: return launch_lanes<16>(kind, a, TC, ro);
-  }
-  return hipErrorInvalidValue;
+  return launch_with(kind, a, lanes, [&](auto v, dim3 grid, size_t shmem, int TC) {
+    using V = decltype(v);
+    if (ro) {
+      hipLaunchKernelGGL((msed_kernel<V::L, V::STATIC, V::HASB, V::SCALED, true>), grid, dim3(kMsedBlock), shmem,
+                         a.stream, a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags,
+                         a.flags_next, *ro);
+    } else {
+      hipLaunchKernelGGL((msed_kernel<V::L, V::STATIC, V::HASB, V::SCALED, false>), grid, dim3(kMsedBlock), shmem,
+                         a.stream, a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags,
+                         a.flags_next, MsedOut{});
+    }
+  });
 }
 
 }  // namespace
@@ -961,24 +861,22 @@ hipError_t launch_msed(int kind, const LaunchArgs& a, int lanes) {
 
 hipError_t launch_msed_grad(int kind, const LaunchArgs& a, int lanes, double* grad) {
   if (msedn_kind(kind)) return launch_msedn_grad(kind, a, lanes, grad);
-  const int TC = chunk_columns(a.N);
-  if (TC < 1) return hipErrorInvalidValue;
-  switch (lanes) {
-    case 4: return launch_grad_lanes<4>(kind, a, TC, grad);
-    case 16: return launch_grad_lanes<16>(kind, a, TC, grad);
-  }
-  return hipErrorInvalidValue;
+  return launch_with(kind, a, lanes, [&](auto v, dim3 grid, size_t shmem, int TC) {
+    using V = decltype(v);
+    hipLaunchKernelGGL((lambda_grad_kernel<V::L, V::STATIC, V::HASB, V::SCALED>), grid, dim3(kMsedBlock), shmem,
+                       a.stream, a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, grad, a.flags,
+                       a.flags_next);
+  });
 }
 
 hipError_t launch_msed_fullgrad(int kind, const LaunchArgs& a, int lanes, double* grad) {
   if (!msed::kind_known(kind) || a.P != msed::kind_params(kind)) return hipErrorInvalidValue;
-  const int TC = chunk_columns(a.N);
-  if (TC < 1) return hipErrorInvalidValue;
-  switch (lanes) {
-    case 4: return launch_fullgrad_lanes<4>(kind, a, TC, grad);
-    case 16: return launch_fullgrad_lanes<16>(kind, a, TC, grad);
-  }
-  return hipErrorInvalidValue;
+  return launch_with(kind, a, lanes, [&](auto v, dim3 grid, size_t shmem, int TC) {
+    using V = decltype(v);
+    hipLaunchKernelGGL((lambda_fullgrad_kernel<V::L, V::STATIC, V::HASB, V::SCALED>), grid, dim3(kMsedBlock), shmem,
+                       a.stream, a.theta, a.P, a.B, a.space, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, grad, a.flags,
+                       a.flags_next);
+  });
 }
 
 hipError_t launch_msed_record(int kind, const LaunchArgs& a, int lanes, const MsedRecord& r) {

@@ -28,67 +28,17 @@
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
 #include "yfm_msedn.hpp"
-#include "yfm_msed_tree.hpp"
+#include "yfm_msed_pass.hpp"
 
 namespace yfm {
 
 namespace {
 
 using namespace msedtree;
+using namespace msedpass;
 using namespace msedn;
 
 constexpr int kConsts = 4 * kG;  // A, B, ν and the score's EWMA of one candidate in LDS
-
-template <int NV>
-struct Sums {
-  double v[NV];
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = 0.0;
-  }
-  __device__ __forceinline__ void add(const Sums& a, const Sums& b) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = a.v[k] + b.v[k];
-  }
-  template <int L>
-  __device__ __forceinline__ void reduce() {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = group_sum_desc<L>(v[k]);
-  }
-};
-
-// the statistics of an OLS pass, with the comparison's sum of squares
-struct PassStats {
-  double o[NOLS];
-  double vv;
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int k = 0; k < NOLS; ++k) o[k] = 0.0;
-    vv = 0.0;
-  }
-  __device__ __forceinline__ void add(const PassStats& a, const PassStats& b) {
-#pragma unroll
-    for (int k = 0; k < NOLS; ++k) o[k] = a.o[k] + b.o[k];
-    vv = a.vv + b.vv;
-  }
-};
-
-// Scal and (WITH_H) the score's data-free sums at the state's γ, by the whole group
-template <int L, bool WITH_H>
-__device__ __forceinline__ void prepare_group(State& st, bool anchored, const Ends& e, const double* s_m, int N, int j) {
-  constexpr int NV = WITH_H ? NAUX : 1;
-  anchors(st.gamma, anchored, e, st.sc);
-  Sums<NV> sa;
-  auto leaf = [&](int c, Sums<NV>& s) {
-    s.zero();
-    for (int i = c; i < N; i += kMsedClasses) accum_aux<WITH_H>(s.v, st.gamma, st.sc, i, N, s_m[i]);
-  };
-  class_tree<log_classes_per_lane<L>()>(j, leaf, sa);
-  sa.template reduce<L>();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) st.aux[k] = sa.v[k];
-  finish_scale(st.aux[AQ], anchored, st.sc);
-}
 
 template <int L, bool STATIC, bool HASB, bool SCALED, bool RECORD>
 __global__ __launch_bounds__(kMsedBlock) void msedn_kernel(const double* __restrict__ theta, int P, int B, int space,
@@ -159,16 +109,7 @@ __global__ __launch_bounds__(kMsedBlock) void msedn_kernel(const double* __restr
   // ---- panel staging: chunk c (columns cTC .. cTC+TC−1) in LDS.  No register prefetch of the next chunk, unlike
   // the λ kernel: a step here is thousands of instructions, so one exposed load per TC steps costs nothing, and the
   // 16 registers are better spent on the score pass ----
-  auto stage_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      const size_t g = base + e;
-      if (e < CHY) s_y[e] = g < lim ? Y[g] : 0.0;
-    }
-  };
+  auto stage_chunk = [&](int c) { chunk_stage(Y, s_y, c, CHY, T, N, tid); };
   if (niter > 0) {
     stage_chunk(0);
     __syncthreads();
@@ -323,29 +264,8 @@ __global__ __launch_bounds__(kMsedBlock) void msedn_kernel(const double* __restr
     if (traj) return;
   }
   if (j != 0) return;
-  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
-  if (fail) {
-    ll = -__builtin_inf();
-    atomicAdd(&flags[1], 1u);
-  }
-  out[b] = ll;
+  out[b] = finish_loss(mse, fN, nobs, fail, flags);
 }
-
-// The statistics of pass A with Z'v of the comparison (yfm_msed.hpp, ∂loss/∂(δ, Φ)) through the same tree.
-struct GradPassStats {
-  PassStats s;
-  double zv[kM];
-  __device__ __forceinline__ void zero() {
-    s.zero();
-#pragma unroll
-    for (int k = 0; k < kM; ++k) zv[k] = 0.0;
-  }
-  __device__ __forceinline__ void add(const GradPassStats& a, const GradPassStats& b) {
-    s.add(a.s, b.s);
-#pragma unroll
-    for (int k = 0; k < kM; ++k) zv[k] = a.zv[k] + b.zv[k];
-  }
-};
 
 // get_loss and its gradient with respect to δ and Φ in one pass: msedn_kernel's loss mode — the same mapping, LDS
 // record, staging, passes and sums, so the loss is the same bits — whose pass A also forms s = Z'v at the loadings
@@ -422,16 +342,7 @@ __global__ __launch_bounds__(kMsedBlock) void neural_grad_kernel(const double* _
   if (live) prepare_group<L, !STATIC>(st, anchored, ends, s_m, N, j);
 
   // ---- panel staging, as msedn_kernel ----
-  auto stage_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      const size_t gi = base + e;
-      if (e < CHY) s_y[e] = gi < lim ? Y[gi] : 0.0;
-    }
-  };
+  auto stage_chunk = [&](int c) { chunk_stage(Y, s_y, c, CHY, T, N, tid); };
   if (niter > 0) {
     stage_chunk(0);
     __syncthreads();
@@ -533,67 +444,25 @@ __global__ __launch_bounds__(kMsedBlock) void neural_grad_kernel(const double* _
   }
 
   if (!live || j != 0) return;
-  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
-  if (fail) {
-    ll = -__builtin_inf();
-    atomicAdd(&flags[1], 1u);
-  }
-  out[b] = ll;
+  out[b] = finish_loss(mse, fN, nobs, fail, flags);
   double go[msed::kGrad];
   msed::grad_finish(g, th, P, space, fN, nobs, fail, go);
 #pragma unroll
   for (int k = 0; k < msed::kGrad; ++k) grad[(size_t)b * msed::kGrad + k] = go[k];
 }
 
-size_t shmem_bytes(int L, int N, int TC) {
-  return sizeof(double) * ((size_t)N + (size_t)TC * N + (size_t)(kMsedBlock / L) * kConsts);
-}
-
-template <int L, bool STATIC, bool HASB, bool SCALED>
-hipError_t launch_variant(int kind, const LaunchArgs& a, int TC, const MsedRecord* ro) {
-  constexpr int GPB = kMsedBlock / L;
-  const int grid = (a.B + GPB - 1) / GPB;
-  const size_t shmem = shmem_bytes(L, a.N, TC);
-  if (ro) {
-    hipLaunchKernelGGL((msedn_kernel<L, STATIC, HASB, SCALED, true>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
-                       a.theta, a.P, a.B, a.space, kind, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags,
-                       a.flags_next, *ro);
-  } else {
-    hipLaunchKernelGGL((msedn_kernel<L, STATIC, HASB, SCALED, false>), dim3(grid), dim3(kMsedBlock), shmem, a.stream,
-                       a.theta, a.P, a.B, a.space, kind, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags,
-                       a.flags_next, MsedRecord{});
-  }
-  return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_lanes(int kind, const LaunchArgs& a, int TC, const MsedRecord* ro) {
-  if (kind_static(kind)) return launch_variant<L, true, false, false>(kind, a, TC, ro);
-  const bool hb = kind_has_b(kind), sc = kind_scaled(kind);
-  if (hb && sc) return launch_variant<L, false, true, true>(kind, a, TC, ro);
-  if (hb) return launch_variant<L, false, true, false>(kind, a, TC, ro);
-  if (sc) return launch_variant<L, false, false, true>(kind, a, TC, ro);
-  return launch_variant<L, false, false, false>(kind, a, TC, ro);
-}
-
-template <int L, bool STATIC, bool HASB, bool SCALED>
-hipError_t launch_grad_variant(int kind, const LaunchArgs& a, int TC, double* grad) {
-  constexpr int GPB = kMsedBlock / L;
-  const int grid = (a.B + GPB - 1) / GPB;
-  hipLaunchKernelGGL((neural_grad_kernel<L, STATIC, HASB, SCALED>), dim3(grid), dim3(kMsedBlock),
-                     shmem_bytes(L, a.N, TC), a.stream, a.theta, a.P, a.B, a.space, kind, a.raw, a.T, a.N, TC, a.mats,
-                     a.T_use, a.out, grad, a.flags, a.flags_next);
-  return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_grad_lanes(int kind, const LaunchArgs& a, int TC, double* grad) {
-  if (kind_static(kind)) return launch_grad_variant<L, true, false, false>(kind, a, TC, grad);
-  const bool hb = kind_has_b(kind), sc = kind_scaled(kind);
-  if (hb && sc) return launch_grad_variant<L, false, true, true>(kind, a, TC, grad);
-  if (hb) return launch_grad_variant<L, false, true, false>(kind, a, TC, grad);
-  if (sc) return launch_grad_variant<L, false, false, true>(kind, a, TC, grad);
-  return launch_grad_variant<L, false, false, false>(kind, a, TC, grad);
+// launch(Variant, grid, shared-memory bytes, TC) starts the kernel of a kind at a lane count on a's batch and panel
+template <class F>
+hipError_t launch_with(int kind, const LaunchArgs& a, int lanes, F&& launch) {
+  const int TC = chunk_columns(a.N);
+  if (TC < 1) return hipErrorInvalidValue;
+  return with_lanes(lanes, [&](auto ln) {
+    constexpr int L = decltype(ln)::value;
+    return with_neural_kind<L>(kind, [&](auto v) {
+      launch(v, grid_blocks(a.B, L), neural_shmem(L, a.N, TC, kConsts), TC);
+      return hipGetLastError();
+    });
+  });
 }
 
 }  // namespace
@@ -612,24 +481,28 @@ int msedn_grad_max_n() { return msedn_max_n(); }
 
 hipError_t launch_msedn(int kind, const LaunchArgs& a, int lanes, const MsedRecord* r) {
   if (!msedn::kind_known(kind) || a.N < msedn_min_n() || a.N > msedn_max_n()) return hipErrorInvalidValue;
-  const int TC = chunk_columns(a.N);
-  if (TC < 1) return hipErrorInvalidValue;
-  switch (lanes) {
-    case 4: return launch_lanes<4>(kind, a, TC, r);
-    case 16: return launch_lanes<16>(kind, a, TC, r);
-  }
-  return hipErrorInvalidValue;
+  return launch_with(kind, a, lanes, [&](auto v, dim3 grid, size_t shmem, int TC) {
+    using V = decltype(v);
+    if (r) {
+      hipLaunchKernelGGL((msedn_kernel<V::L, V::STATIC, V::HASB, V::SCALED, true>), grid, dim3(kMsedBlock), shmem,
+                         a.stream, a.theta, a.P, a.B, a.space, kind, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out,
+                         a.flags, a.flags_next, *r);
+    } else {
+      hipLaunchKernelGGL((msedn_kernel<V::L, V::STATIC, V::HASB, V::SCALED, false>), grid, dim3(kMsedBlock), shmem,
+                         a.stream, a.theta, a.P, a.B, a.space, kind, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out,
+                         a.flags, a.flags_next, MsedRecord{});
+    }
+  });
 }
 
 hipError_t launch_msedn_grad(int kind, const LaunchArgs& a, int lanes, double* grad) {
   if (!msedn::kind_known(kind) || a.N < msedn_min_n() || a.N > msedn_grad_max_n()) return hipErrorInvalidValue;
-  const int TC = chunk_columns(a.N);
-  if (TC < 1) return hipErrorInvalidValue;
-  switch (lanes) {
-    case 4: return launch_grad_lanes<4>(kind, a, TC, grad);
-    case 16: return launch_grad_lanes<16>(kind, a, TC, grad);
-  }
-  return hipErrorInvalidValue;
+  return launch_with(kind, a, lanes, [&](auto v, dim3 grid, size_t shmem, int TC) {
+    using V = decltype(v);
+    hipLaunchKernelGGL((neural_grad_kernel<V::L, V::STATIC, V::HASB, V::SCALED>), grid, dim3(kMsedBlock), shmem,
+                       a.stream, a.theta, a.P, a.B, a.space, kind, a.raw, a.T, a.N, TC, a.mats, a.T_use, a.out, grad,
+                       a.flags, a.flags_next);
+  });
 }
 
 }  // namespace yfm

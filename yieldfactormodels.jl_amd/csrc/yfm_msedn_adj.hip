@@ -19,13 +19,14 @@
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
 #include "yfm_msedn_adj.hpp"
-#include "yfm_msed_tree.hpp"
+#include "yfm_msed_pass.hpp"
 
 namespace yfm {
 
 namespace {
 
 using namespace msedtree;
+using namespace msedpass;
 using namespace msedn;
 
 constexpr int kConsts = 4 * kG;  // the forward sweep's record: A, B, ν and the score's EWMA
@@ -56,24 +57,6 @@ struct Fit {
 };
 static_assert(sizeof(Fit) <= 30 * sizeof(double) && sizeof(Model) <= 16 * sizeof(double), "record slots");
 
-template <int NV>
-struct Sums {
-  double v[NV];
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = 0.0;
-  }
-  __device__ __forceinline__ void add(const Sums& a, const Sums& b) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = a.v[k] + b.v[k];
-  }
-  template <int L>
-  __device__ __forceinline__ void reduce() {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) v[k] = group_sum_desc<L>(v[k]);
-  }
-};
-
 template <int NV, int NW>
 struct DualSums {
   Dual v[NV];
@@ -98,53 +81,6 @@ struct DualSums {
     for (int k = 0; k < NW; ++k) w[k] = group_sum_desc<L>(w[k]);
   }
 };
-
-struct PassStats {
-  double o[NOLS];
-  double vv;
-  __device__ __forceinline__ void zero() {
-#pragma unroll
-    for (int k = 0; k < NOLS; ++k) o[k] = 0.0;
-    vv = 0.0;
-  }
-  __device__ __forceinline__ void add(const PassStats& a, const PassStats& b) {
-#pragma unroll
-    for (int k = 0; k < NOLS; ++k) o[k] = a.o[k] + b.o[k];
-    vv = a.vv + b.vv;
-  }
-};
-
-struct GradPassStats {
-  PassStats s;
-  double zv[kM];
-  __device__ __forceinline__ void zero() {
-    s.zero();
-#pragma unroll
-    for (int k = 0; k < kM; ++k) zv[k] = 0.0;
-  }
-  __device__ __forceinline__ void add(const GradPassStats& a, const GradPassStats& b) {
-    s.add(a.s, b.s);
-#pragma unroll
-    for (int k = 0; k < kM; ++k) zv[k] = a.zv[k] + b.zv[k];
-  }
-};
-
-// Scal and (WITH_H) the score's data-free sums at the state's γ, by the whole group (msedn_kernel's)
-template <int L, bool WITH_H>
-__device__ __forceinline__ void prepare_state(State& st, bool anchored, const Ends& e, const double* s_m, int N, int j) {
-  constexpr int NV = WITH_H ? NAUX : 1;
-  anchors(st.gamma, anchored, e, st.sc);
-  Sums<NV> sa;
-  auto leaf = [&](int c, Sums<NV>& s) {
-    s.zero();
-    for (int i = c; i < N; i += kMsedClasses) accum_aux<WITH_H>(s.v, st.gamma, st.sc, i, N, s_m[i]);
-  };
-  class_tree<log_classes_per_lane<L>()>(j, leaf, sa);
-  sa.template reduce<L>();
-#pragma unroll
-  for (int k = 0; k < NV; ++k) st.aux[k] = sa.v[k];
-  finish_scale(st.aux[AQ], anchored, st.sc);
-}
 
 // ---- the forward sweep -------------------------------------------------------------------------------------------
 // neural_grad_kernel with the trajectory: before step t the group stores the γ (and e) it enters with to
@@ -217,18 +153,9 @@ __global__ __launch_bounds__(kMsedBlock) void nns_sweep_kernel(const double* __r
   __syncthreads();
   const int niter = s_iters_max;
   const int CHY = TC * N;
-  if (live) prepare_state<L, !STATIC>(st, anchored, ends, s_m, N, j);
+  if (live) prepare_group<L, !STATIC>(st, anchored, ends, s_m, N, j);
 
-  auto stage_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int r = 0; r < kMsedPre; ++r) {
-      const int e = r * kMsedBlock + tid;
-      const size_t gi = base + e;
-      if (e < CHY) s_y[e] = gi < lim ? Y[gi] : 0.0;
-    }
-  };
+  auto stage_chunk = [&](int c) { chunk_stage(Y, s_y, c, CHY, T, N, tid); };
   if (niter > 0) {
     stage_chunk(0);
     __syncthreads();
@@ -286,7 +213,7 @@ __global__ __launch_bounds__(kMsedBlock) void nns_sweep_kernel(const double* __r
         pred_fail = false;
         if (pred_only) {
           advance<HASB>(mdl, cB, cNu, st);
-          if constexpr (HASB) prepare_state<L, true>(st, anchored, ends, s_m, N, j);
+          if constexpr (HASB) prepare_group<L, true>(st, anchored, ends, s_m, N, j);
         } else if (!msed::ols(sa.s.o, fN, st.beta)) {
           pred_fail = true;
         } else {
@@ -304,7 +231,7 @@ __global__ __launch_bounds__(kMsedBlock) void nns_sweep_kernel(const double* __r
               finish_score(sc.v, st.aux, st.gamma, st.sc, anchored, ends, gg);
               update_gamma<SCALED>(cA, cEw, st, gg);
             }
-            prepare_state<L, !HASB>(st, anchored, ends, s_m, N, j);
+            prepare_group<L, !HASB>(st, anchored, ends, s_m, N, j);
             Sums<NOLS> sb;
             auto leaf_b = [&](int c, Sums<NOLS>& s) {
               s.zero();
@@ -323,10 +250,10 @@ __global__ __launch_bounds__(kMsedBlock) void nns_sweep_kernel(const double* __r
 #pragma unroll
             for (int k = 0; k < kM; ++k) bpost[k] = st.beta[k];
             advance<HASB>(mdl, cB, cNu, st);
-            if constexpr (HASB) prepare_state<L, true>(st, anchored, ends, s_m, N, j);
+            if constexpr (HASB) prepare_group<L, true>(st, anchored, ends, s_m, N, j);
           } else {
             pred_fail = true;
-            if constexpr (HASB) prepare_state<L, true>(st, anchored, ends, s_m, N, j);
+            if constexpr (HASB) prepare_group<L, true>(st, anchored, ends, s_m, N, j);
           }
         }
       }
@@ -339,12 +266,7 @@ __global__ __launch_bounds__(kMsedBlock) void nns_sweep_kernel(const double* __r
   }
 
   if (!live || j != 0) return;
-  double ll = mse / fN / (double)nobs;  // filter.jl:242 (nobs, not nobs − 1)
-  if (fail) {
-    ll = -__builtin_inf();
-    atomicAdd(&flags[1], 1u);
-  }
-  out[b] = ll;
+  out[b] = finish_loss(mse, fN, nobs, fail, flags);
   double go[msed::kGrad];
   msed::grad_finish(g, th, P, space, fN, nobs, fail, go);
 #pragma unroll
@@ -674,13 +596,6 @@ __global__ __launch_bounds__(kMsedBlock) void nns_adjoint_kernel(const double* _
     atomicAdd(&flags[5], 1u);
 }
 
-size_t sweep_shmem(int L, int N, int TC) {
-  return sizeof(double) * ((size_t)N + (size_t)TC * N + (size_t)(kMsedBlock / L) * kConsts);
-}
-size_t adjoint_shmem(int L, int N, int TC) {
-  return sizeof(double) * ((size_t)N + (size_t)TC * N + (size_t)(kMsedBlock / L) * NREC);
-}
-
 struct ChunkArgs {
   const double* theta;
   const int* T_use;
@@ -695,29 +610,23 @@ struct ChunkArgs {
 // and a candidate's outputs do not depend on L.
 constexpr int kAdjLanes = 16;
 
-template <int L, bool STATIC, bool HASB, bool SCALED>
-hipError_t launch_pair(int kind, const LaunchArgs& a, const ChunkArgs& c, int TC, double* traj) {
-  constexpr int GPB = kMsedBlock / L;
-  constexpr int GPA = kMsedBlock / kAdjLanes;
-  hipLaunchKernelGGL((nns_sweep_kernel<L, STATIC, HASB, SCALED>), dim3((c.B + GPB - 1) / GPB), dim3(kMsedBlock),
-                     sweep_shmem(L, a.N, TC), a.stream, c.theta, a.P, c.B, a.space, kind, a.raw, a.T, a.N, TC, a.mats,
-                     c.T_use, c.out, c.grad, traj, a.flags, c.flags_next);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((nns_adjoint_kernel<kAdjLanes, STATIC, HASB, SCALED>), dim3((c.B + GPA - 1) / GPA),
-                     dim3(kMsedBlock), adjoint_shmem(kAdjLanes, a.N, TC), a.stream, c.theta, a.P, c.B, a.space, kind,
-                     a.raw, a.T, a.N, TC, a.mats, c.T_use, c.out, c.grad, traj, a.flags);
-  return hipGetLastError();
-}
-
-template <int L>
-hipError_t launch_pair_lanes(int kind, const LaunchArgs& a, const ChunkArgs& c, int TC, double* traj) {
-  if (kind_static(kind)) return launch_pair<L, true, false, false>(kind, a, c, TC, traj);
-  const bool hb = kind_has_b(kind), sc = kind_scaled(kind);
-  if (hb && sc) return launch_pair<L, false, true, true>(kind, a, c, TC, traj);
-  if (hb) return launch_pair<L, false, true, false>(kind, a, c, TC, traj);
-  if (sc) return launch_pair<L, false, false, true>(kind, a, c, TC, traj);
-  return launch_pair<L, false, false, false>(kind, a, c, TC, traj);
+// the forward sweep of chunk c at `lanes` lanes, then its backward sweep
+hipError_t launch_pair(int kind, const LaunchArgs& a, const ChunkArgs& c, int lanes, int TC, double* traj) {
+  return with_lanes(lanes, [&](auto ln) {
+    constexpr int L = decltype(ln)::value;
+    return with_neural_kind<L>(kind, [&](auto v) {
+      using V = decltype(v);
+      hipLaunchKernelGGL((nns_sweep_kernel<L, V::STATIC, V::HASB, V::SCALED>), grid_blocks(c.B, L), dim3(kMsedBlock),
+                         neural_shmem(L, a.N, TC, kConsts), a.stream, c.theta, a.P, c.B, a.space, kind, a.raw, a.T, a.N,
+                         TC, a.mats, c.T_use, c.out, c.grad, traj, a.flags, c.flags_next);
+      const hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL((nns_adjoint_kernel<kAdjLanes, V::STATIC, V::HASB, V::SCALED>), grid_blocks(c.B, kAdjLanes),
+                         dim3(kMsedBlock), neural_shmem(kAdjLanes, a.N, TC, NREC), a.stream, c.theta, a.P, c.B, a.space,
+                         kind, a.raw, a.T, a.N, TC, a.mats, c.T_use, c.out, c.grad, traj, a.flags);
+      return hipGetLastError();
+    });
+  });
 }
 
 // bytes of trajectory one candidate takes on a panel of T columns
@@ -765,7 +674,7 @@ hipError_t launch_msedn_fullgrad(int kind, const LaunchArgs& a, int lanes, doubl
     c.grad = grad + (size_t)b0 * a.P;
     c.B = a.B - b0 < nb ? a.B - b0 : nb;
     c.flags_next = b0 == 0 ? a.flags_next : nullptr;
-    const hipError_t e = lanes == 4 ? launch_pair_lanes<4>(kind, a, c, TC, traj) : launch_pair_lanes<16>(kind, a, c, TC, traj);
+    const hipError_t e = launch_pair(kind, a, c, lanes, TC, traj);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

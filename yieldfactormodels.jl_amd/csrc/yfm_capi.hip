@@ -319,6 +319,26 @@ Launch loglik_launch(int kind, int space, const double* d_theta, int P, int B, c
   return q;
 }
 
+// What every kernel of the launch q reads of q and of the context: θ, the windows, the panel and the stream.  The
+// outputs, counters and work buffers are the caller's to add.
+yfm::LaunchArgs base_args(const yfm_ctx* ctx, const Launch& q) {
+  yfm::LaunchArgs a{};
+  a.theta = q.theta;
+  a.P = q.P;
+  a.B = q.B;
+  a.space = q.space;
+  a.panel = static_cast<const double*>(ctx->panel.p);
+  a.raw = static_cast<const double*>(ctx->raw.p);
+  a.T = ctx->T;
+  a.N = ctx->N;
+  a.np = ctx->np;
+  a.ldp = ctx->ldp;
+  a.mats = static_cast<const double*>(ctx->mats.p);
+  a.T_use = q.T_use;
+  a.stream = q.stream;
+  return a;
+}
+
 // Enqueue the kernels of one launch on q.stream, with the work buffers of w.
 int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
   const int B = q.B;
@@ -334,25 +354,12 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
     YFM_HIP_CHECK(hipMemsetAsync(w.flags.p, 0, 2 * yfm::kFlagsPerBank * sizeof(unsigned int), s));
     return YFM_OK;
   }
-  yfm::LaunchArgs a;
-  a.theta = q.theta;
-  a.P = q.P;
-  a.B = B;
-  a.space = q.space;
-  a.panel = static_cast<const double*>(ctx->panel.p);
-  a.raw = static_cast<const double*>(ctx->raw.p);
-  a.T = ctx->T;
-  a.N = ctx->N;
-  a.np = ctx->np;
-  a.ldp = ctx->ldp;
-  a.mats = static_cast<const double*>(ctx->mats.p);
-  a.T_use = q.T_use;
+  yfm::LaunchArgs a = base_args(ctx, q);
   a.out = q.out;
   a.flags = w.bank_ptr(bank);
   a.flags_next = flags_next;
   a.rec_beta = q.rec_beta;
   a.rec_P = q.rec_P;
-  a.scratch = nullptr;
   a.horizon = q.horizon;
   a.rec_len = q.rec_beta ? (q.rec_len > 0 ? q.rec_len : ctx->T - 1) : 0;
   if (q.panel) {
@@ -360,7 +367,6 @@ int enqueue(yfm_ctx* ctx, const Launch& q, yfm::Workspace& w) {
     a.panel = q.panel->panel;
     a.T = q.panel->T;
   }
-  a.stream = s;
   hipError_t e;
   if (yfm::msed_kind(q.kind)) {
     const int lanes = yfm::msed_lanes_for(B);
@@ -532,22 +538,9 @@ int check_neural_fullgrad(yfm_ctx* ctx, int kind, int space, int P, int B) {
 // inputs, its counter bank and its deferral list.
 yfm::LaunchArgs tangent_args(yfm_ctx* ctx, const Launch& q) {
   yfm::Workspace& w = ctx->own;
-  yfm::LaunchArgs a{};
-  a.theta = q.theta;
-  a.P = q.P;
-  a.B = q.B;
-  a.space = q.space;
-  a.panel = static_cast<const double*>(ctx->panel.p);
-  a.raw = static_cast<const double*>(ctx->raw.p);
-  a.T = ctx->T;
-  a.N = ctx->N;
-  a.np = ctx->np;
-  a.ldp = ctx->ldp;
-  a.mats = static_cast<const double*>(ctx->mats.p);
-  a.T_use = q.T_use;
+  yfm::LaunchArgs a = base_args(ctx, q);
   a.flags = w.bank_ptr(w.bank);  // the bank of the loglik launch just enqueued
   a.defer_list = static_cast<int*>(w.defer.p);
-  a.stream = q.stream;
   return a;
 }
 
@@ -599,9 +592,8 @@ int run_trajectory(yfm_ctx* ctx, Launch q) {
   return YFM_OK;
 }
 
-// The emit kernels' view of the trajectory that run_trajectory(ctx, q) recorded.
-yfm::PredictArgs predict_args(yfm_ctx* ctx, const Launch& q, int horizon) {
-  yfm::PredictArgs a{};
+// The emit kernels' view of the trajectory that run_trajectory(ctx, q) recorded; `a` brings the output pointers.
+yfm::PredictArgs predict_args(yfm_ctx* ctx, const Launch& q, int horizon, yfm::PredictArgs a) {
   a.kind = q.kind;
   a.M = state_dim(q.kind);
   a.L = gamma_dim(q.kind);
@@ -621,6 +613,23 @@ yfm::PredictArgs predict_args(yfm_ctx* ctx, const Launch& q, int horizon) {
   return a;
 }
 
+// Record mode of the λ and neural kinds: the kernel writes the trajectory outputs of `o` itself, into the NaN-filled
+// block of `bytes` that starts at o.preds.
+int launch_record(yfm_ctx* ctx, Launch q, int mode, int horizon, int ncol, const yfm::PredictArgs& o, size_t bytes) {
+  YFM_HIP_CHECK(hipMemsetAsync(o.preds, 0xff, bytes, ctx->stream));
+  yfm::MsedRecord rec;
+  rec.mode = mode;
+  rec.horizon = horizon;
+  rec.ncol = ncol;
+  rec.preds = o.preds;
+  rec.factors = o.factors;
+  rec.states = o.states;
+  rec.load1 = o.load1;
+  rec.load2 = o.load2;
+  q.msed_rec = &rec;
+  return launch(ctx, q);
+}
+
 // The counters of the context's last launch (layout: yfm_flags.hpp).
 int read_flags(yfm_ctx* ctx, unsigned int (&h)[yfm::kFlagsPerBank]) {
   if (int r = check_ctx(ctx)) return r;
@@ -638,23 +647,44 @@ int validate_tuse(const int* T_use, int B, int T) {
 
 using GradCheck = int (*)(yfm_ctx*, int, int, int, int);
 
-// yfm_lambda_loss_grad_batch and yfm_neural_loss_grad_batch: one launch path, each with its own model check
-int loss_grad_batch(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
-                    const int* T_use, double* loss_out, double* grad_out, bool full = false) {
+// A gradient call family: its model check, what its value is called in messages, the rows of its gradient and how its
+// launch is made.
+struct GradFamily {
+  GradCheck check;
+  const char* value;  // "loglik" or "loss"
+  int rows;           // gradient rows per candidate (0: one per row of θ)
+  enum { kTangent, kMsedGrad, kMsedFullGrad } how;  // launch_grad, or launch with msed_grad / msed_fullgrad set
+};
+const GradFamily kDnsGrad{check_grad, "loglik", 0, GradFamily::kTangent};
+const GradFamily kTvlGrad{check_tvl_grad, "loglik", 0, GradFamily::kTangent};
+const GradFamily kLambdaGrad{check_lambda_grad, "loss", yfm::kMsedGrad, GradFamily::kMsedGrad};
+const GradFamily kLambdaFullGrad{check_lambda_fullgrad, "loss", 0, GradFamily::kMsedFullGrad};
+const GradFamily kNeuralGrad{check_neural_grad, "loss", yfm::kMsedGrad, GradFamily::kMsedGrad};
+const GradFamily kNeuralFullGrad{check_neural_fullgrad, "loss", 0, GradFamily::kMsedFullGrad};
+
+// The launch of family f for q, the gradient to go to d_grad.
+int launch_family(yfm_ctx* ctx, const GradFamily& f, Launch q, double* d_grad) {
+  if (f.how == GradFamily::kTangent) return launch_grad(ctx, q, d_grad);
+  (f.how == GradFamily::kMsedFullGrad ? q.msed_fullgrad : q.msed_grad) = d_grad;
+  return launch(ctx, q);
+}
+
+// The six host-pointer gradient entry points: one path, each family with its own model check and launch.
+int grad_batch(const GradFamily& f, yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+               const int* T_use, double* value_out, double* grad_out) {
   if (int r = check_ctx(ctx)) return r;
-  if (int r = check(ctx, model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!theta || !loss_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loss_out or grad_out");
+  if (int r = f.check(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !value_out || !grad_out))
+    return set_error(YFM_EINVAL, "null theta, %s_out or grad_out", f.value);
   if (int r = validate_tuse(T_use, B, ctx->T)) return r;
   Launch q;
   if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  const size_t rows = full ? (size_t)P : (size_t)yfm::kMsedGrad;  // full: every row of θ
-  const size_t gb = sizeof(double) * rows * (size_t)(B > 0 ? B : 1);
-  YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
+  const size_t rows = f.rows > 0 ? (size_t)f.rows : (size_t)P;
+  YFM_HIP_CHECK(ctx->own.grad.ensure(sizeof(double) * rows * (size_t)(B > 0 ? B : 1)));
   double* const d_grad = static_cast<double*>(ctx->own.grad.p);
-  (full ? q.msed_fullgrad : q.msed_grad) = d_grad;
-  if (int r = launch(ctx, q)) return r;
+  if (int r = launch_family(ctx, f, q, d_grad)) return r;
   if (B > 0) {
-    YFM_HIP_CHECK(hipMemcpyAsync(loss_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(value_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
     YFM_HIP_CHECK(hipMemcpyAsync(grad_out, d_grad, sizeof(double) * rows * (size_t)B, hipMemcpyDeviceToHost,
                                  ctx->stream));
   }
@@ -662,51 +692,16 @@ int loss_grad_batch(GradCheck check, yfm_ctx* ctx, int model_kind, int param_spa
   return YFM_OK;
 }
 
-int loss_grad_batch_device(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta,
-                           int P, int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
-                           void* hip_stream, bool full = false) {
+// Their device-pointer twins: the launch alone, asynchronous on the caller's stream.
+int grad_batch_device(const GradFamily& f, yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                      int B, const int* d_T_use, double* d_value_out, double* d_grad_out, void* hip_stream) {
   if (int r = check_ctx(ctx)) return r;
-  if (int r = check(ctx, model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!d_theta || !d_loss_out || !d_grad_out))
-    return set_error(YFM_EINVAL, "null d_theta, d_loss_out or d_grad_out");
-  Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
-                           static_cast<hipStream_t>(hip_stream));
-  (full ? q.msed_fullgrad : q.msed_grad) = d_grad_out;
-  return launch(ctx, q);
+  if (int r = f.check(ctx, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_value_out || !d_grad_out))
+    return set_error(YFM_EINVAL, "null d_theta, d_%s_out or d_grad_out", f.value);
+  return launch_family(ctx, f, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_value_out,
+                                             static_cast<hipStream_t>(hip_stream)), d_grad_out);
 }
-
-// yfm_loglik_grad_batch and yfm_tvl_loglik_grad_batch: one launch path, each with its own model check
-int loglik_grad_batch(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
-                      const int* T_use, double* loglik_out, double* grad_out) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check(ctx, model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!theta || !loglik_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loglik_out or grad_out");
-  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
-  Launch q;
-  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  const size_t gb = sizeof(double) * (size_t)P * (size_t)(B > 0 ? B : 1);
-  YFM_HIP_CHECK(ctx->own.grad.ensure(gb));
-  if (int r = launch_grad(ctx, q, static_cast<double*>(ctx->own.grad.p))) return r;
-  if (B > 0) {
-    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
-    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, ctx->own.grad.p, sizeof(double) * (size_t)P * B, hipMemcpyDeviceToHost,
-                                 ctx->stream));
-  }
-  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return YFM_OK;
-}
-
-int loglik_grad_batch_device(GradCheck check, yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta,
-                             int P, int B, const int* d_T_use, double* d_loglik_out, double* d_grad_out,
-                             void* hip_stream) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check(ctx, model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!d_theta || !d_loglik_out || !d_grad_out))
-    return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_grad_out");
-  return launch_grad(ctx, loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
-                                        static_cast<hipStream_t>(hip_stream)), d_grad_out);
-}
-
 
 // The score / information entry points' model check: they run the DNS tangent recursion, so its limits hold.
 int check_info(yfm_ctx* ctx, const char* what, int kind, int space, int P, int B) {
@@ -758,18 +753,26 @@ int for_score_chunks(yfm_ctx* ctx, const Launch& q, bool count, size_t out_per, 
   return YFM_OK;
 }
 
+// The chunk `start` shrunk until need(chunk), the bytes a launch of that many candidates allocates, is within
+// kInfoChunkBytes (or one candidate is left).
+template <class F>
+int fit_chunk(int start, F&& need) {
+  int chunk = start;
+  while (chunk > 1) {
+    const size_t nb = need(chunk);
+    if (nb <= kInfoChunkBytes) break;
+    const int fit = (int)((double)chunk * ((double)kInfoChunkBytes / (double)nb));
+    chunk = std::max(1, std::min(chunk - 1, fit));
+  }
+  return chunk;
+}
+
 // Candidates per Hessian chunk: the 4P perturbed θ and their gradients (P doubles per point each), and everything the
 // loglik launch of the chunk's 4P·nb points allocates, each within kInfoChunkBytes.
 int hessian_chunk(int kind, int P, int B) {
   const size_t np = 4 * (size_t)P;
-  int chunk = info_chunk(sizeof(double) * (size_t)P * np, B);
-  while (chunk > 1) {
-    const size_t need = fixedz_launch_bytes(kind, (int)(np * chunk));
-    if (need <= kInfoChunkBytes) break;
-    const int fit = (int)((double)chunk * ((double)kInfoChunkBytes / (double)need));
-    chunk = std::max(1, std::min(chunk - 1, fit));
-  }
-  return chunk;
+  return fit_chunk(info_chunk(sizeof(double) * (size_t)P * np, B),
+                   [&](int n) { return fixedz_launch_bytes(kind, (int)(np * n)); });
 }
 
 // H of every candidate of the staged launch q, chunk by chunk: the perturbed points, their logliks and gradients (the
@@ -842,14 +845,7 @@ int check_tvl_smooth(yfm_ctx* ctx, const char* what, int kind, int space, int P,
 int smooth_chunk(int kind, int M, int T, int B) {
   const size_t rec = sizeof(double) * (size_t)(M + M * M) * (size_t)std::max(T - 1, 1);
   const size_t out = sizeof(double) * (size_t)M * M * (size_t)T;
-  int chunk = info_chunk(std::max(rec, out), B);
-  while (chunk > 1) {
-    const size_t need = fixedz_launch_bytes(kind, chunk);
-    if (need <= kInfoChunkBytes) break;
-    const int fit = (int)((double)chunk * ((double)kInfoChunkBytes / (double)need));
-    chunk = std::max(1, std::min(chunk - 1, fit));
-  }
-  return chunk;
+  return fit_chunk(info_chunk(std::max(rec, out), B), [&](int n) { return fixedz_launch_bytes(kind, n); });
 }
 
 // The same for the TVλ extended smoother (M = 4): the record (20 doubles × (T − 1)), each output array and the work
@@ -857,15 +853,9 @@ int smooth_chunk(int kind, int M, int T, int B) {
 int tvl_smooth_chunk(const yfm_ctx* ctx, int T, int B) {
   const size_t rec = sizeof(double) * 20 * (size_t)std::max(T - 1, 1);
   const size_t out = sizeof(double) * 16 * (size_t)T;
-  int chunk = info_chunk(std::max(rec, out), B);
-  while (chunk > 1) {
-    const size_t need = ctx->precision == YFM_PREC_CERTIFIED ? yfm::tvl_dd_scratch_bytes(chunk)
-                                                             : yfm::tvl_scratch_bytes(chunk);
-    if (need <= kInfoChunkBytes) break;
-    const int fit = (int)((double)chunk * ((double)kInfoChunkBytes / (double)need));
-    chunk = std::max(1, std::min(chunk - 1, fit));
-  }
-  return chunk;
+  return fit_chunk(info_chunk(std::max(rec, out), B), [&](int n) {
+    return ctx->precision == YFM_PREC_CERTIFIED ? yfm::tvl_dd_scratch_bytes(n) : yfm::tvl_scratch_bytes(n);
+  });
 }
 
 // The smoother over the candidates of q (θ, T_use and the logliks q.out on the device), chunk by chunk on q.stream:
@@ -928,6 +918,39 @@ int smooth_chunks(yfm_ctx* ctx, const Launch& q, double* d_beta, double* d_V, do
     }
   }
   return YFM_OK;
+}
+
+using SmoothCheck = int (*)(yfm_ctx*, const char*, int, int, int, int);
+
+// yfm_smooth_batch and yfm_tvl_smooth_batch: one path, each with its own model check (`what`: the entry point's name)
+int smooth_batch(SmoothCheck check, const char* what, yfm_ctx* ctx, int model_kind, int param_space,
+                 const double* theta, int P, int B, const int* T_use, double* beta_s, double* V_s, double* C_s) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check(ctx, what, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !beta_s || !V_s)) return set_error(YFM_EINVAL, "null theta, beta_s or V_s");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  if (B == 0) {
+    if (int r = launch(ctx, q)) return r;
+  } else if (int r = smooth_chunks(ctx, q, nullptr, nullptr, nullptr, beta_s, V_s, C_s, C_s != nullptr)) {
+    return r;
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+int smooth_batch_device(SmoothCheck check, const char* what, yfm_ctx* ctx, int model_kind, int param_space,
+                        const double* d_theta, int P, int B, const int* d_T_use, double* d_beta_s, double* d_V_s,
+                        double* d_C_s, void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = check(ctx, what, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_beta_s || !d_V_s)) return set_error(YFM_EINVAL, "null d_theta, d_beta_s or d_V_s");
+  YFM_HIP_CHECK(ctx->own.smooth_ll.ensure(sizeof(double) * (size_t)(B > 0 ? B : 1)));
+  const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use,
+                                 static_cast<double*>(ctx->own.smooth_ll.p), static_cast<hipStream_t>(hip_stream));
+  if (B == 0) return launch(ctx, q);
+  return smooth_chunks(ctx, q, d_beta_s, d_V_s, d_C_s, nullptr, nullptr, nullptr, false);
 }
 
 }  // namespace
@@ -1120,75 +1143,73 @@ int yfm_loglik_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const
 
 int yfm_loglik_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                           const int* T_use, double* loglik_out, double* grad_out) {
-  return loglik_grad_batch(check_grad, ctx, model_kind, param_space, theta, P, B, T_use, loglik_out, grad_out);
+  return grad_batch(kDnsGrad, ctx, model_kind, param_space, theta, P, B, T_use, loglik_out, grad_out);
 }
 
 int yfm_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
                                  const int* d_T_use, double* d_loglik_out, double* d_grad_out, void* hip_stream) {
-  return loglik_grad_batch_device(check_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
-                                  d_grad_out, hip_stream);
+  return grad_batch_device(kDnsGrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out, d_grad_out,
+                           hip_stream);
 }
 
 int yfm_tvl_loglik_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                               const int* T_use, double* loglik_out, double* grad_out) {
-  return loglik_grad_batch(check_tvl_grad, ctx, model_kind, param_space, theta, P, B, T_use, loglik_out, grad_out);
+  return grad_batch(kTvlGrad, ctx, model_kind, param_space, theta, P, B, T_use, loglik_out, grad_out);
 }
 
 int yfm_tvl_loglik_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
                                      int B, const int* d_T_use, double* d_loglik_out, double* d_grad_out,
                                      void* hip_stream) {
-  return loglik_grad_batch_device(check_tvl_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
-                                  d_grad_out, hip_stream);
+  return grad_batch_device(kTvlGrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out, d_grad_out,
+                           hip_stream);
 }
 
 int yfm_lambda_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                                const int* T_use, double* loss_out, double* grad_out) {
-  return loss_grad_batch(check_lambda_grad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out);
+  return grad_batch(kLambdaGrad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out);
 }
 
 int yfm_lambda_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
                                       int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                       void* hip_stream) {
-  return loss_grad_batch_device(check_lambda_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
-                                d_grad_out, hip_stream);
+  return grad_batch_device(kLambdaGrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out, d_grad_out,
+                           hip_stream);
 }
 
 int yfm_lambda_loss_fullgrad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                                    const int* T_use, double* loss_out, double* grad_out) {
-  return loss_grad_batch(check_lambda_fullgrad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out,
-                         true);
+  return grad_batch(kLambdaFullGrad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out);
 }
 
 int yfm_lambda_loss_fullgrad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
                                           int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                           void* hip_stream) {
-  return loss_grad_batch_device(check_lambda_fullgrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use,
-                                d_loss_out, d_grad_out, hip_stream, true);
+  return grad_batch_device(kLambdaFullGrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
+                           d_grad_out, hip_stream);
 }
 
 int yfm_neural_loss_grad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                                const int* T_use, double* loss_out, double* grad_out) {
-  return loss_grad_batch(check_neural_grad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out);
+  return grad_batch(kNeuralGrad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out);
 }
 
 int yfm_neural_loss_grad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
                                       int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                       void* hip_stream) {
-  return loss_grad_batch_device(check_neural_grad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
-                                d_grad_out, hip_stream);
+  return grad_batch_device(kNeuralGrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out, d_grad_out,
+                           hip_stream);
 }
 
 int yfm_neural_loss_fullgrad_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                                    const int* T_use, double* loss_out, double* grad_out) {
-  return loss_grad_batch(check_neural_fullgrad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out,
-                         true);
+  return grad_batch(kNeuralFullGrad, ctx, model_kind, param_space, theta, P, B, T_use, loss_out, grad_out);
 }
 
 int yfm_neural_loss_fullgrad_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
                                           int B, const int* d_T_use, double* d_loss_out, double* d_grad_out,
                                           void* hip_stream) {
-  return loss_grad_batch_device(check_neural_fullgrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use,
-                                d_loss_out, d_grad_out, hip_stream, true);
+  return grad_batch_device(kNeuralFullGrad, ctx, model_kind, param_space, d_theta, P, B, d_T_use, d_loss_out,
+                           d_grad_out, hip_stream);
 }
 
 int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n) {
@@ -1300,60 +1321,26 @@ int yfm_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const d
 
 int yfm_smooth_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                      const int* T_use, double* beta_s, double* V_s, double* C_s) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_smooth(ctx, "yfm_smooth_batch", model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!theta || !beta_s || !V_s)) return set_error(YFM_EINVAL, "null theta, beta_s or V_s");
-  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
-  Launch q;
-  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  if (B == 0) {
-    if (int r = launch(ctx, q)) return r;
-  } else if (int r = smooth_chunks(ctx, q, nullptr, nullptr, nullptr, beta_s, V_s, C_s, C_s != nullptr)) {
-    return r;
-  }
-  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return YFM_OK;
+  return smooth_batch(check_smooth, "yfm_smooth_batch", ctx, model_kind, param_space, theta, P, B, T_use, beta_s, V_s,
+                      C_s);
 }
 
 int yfm_smooth_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
                             const int* d_T_use, double* d_beta_s, double* d_V_s, double* d_C_s, void* hip_stream) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_smooth(ctx, "yfm_smooth_batch_device", model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!d_theta || !d_beta_s || !d_V_s)) return set_error(YFM_EINVAL, "null d_theta, d_beta_s or d_V_s");
-  YFM_HIP_CHECK(ctx->own.smooth_ll.ensure(sizeof(double) * (size_t)(B > 0 ? B : 1)));
-  const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use,
-                                 static_cast<double*>(ctx->own.smooth_ll.p), static_cast<hipStream_t>(hip_stream));
-  if (B == 0) return launch(ctx, q);
-  return smooth_chunks(ctx, q, d_beta_s, d_V_s, d_C_s, nullptr, nullptr, nullptr, false);
+  return smooth_batch_device(check_smooth, "yfm_smooth_batch_device", ctx, model_kind, param_space, d_theta, P, B,
+                             d_T_use, d_beta_s, d_V_s, d_C_s, hip_stream);
 }
 
 int yfm_tvl_smooth_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                          const int* T_use, double* beta_s, double* V_s, double* C_s) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_tvl_smooth(ctx, "yfm_tvl_smooth_batch", model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!theta || !beta_s || !V_s)) return set_error(YFM_EINVAL, "null theta, beta_s or V_s");
-  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
-  Launch q;
-  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  if (B == 0) {
-    if (int r = launch(ctx, q)) return r;
-  } else if (int r = smooth_chunks(ctx, q, nullptr, nullptr, nullptr, beta_s, V_s, C_s, C_s != nullptr)) {
-    return r;
-  }
-  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return YFM_OK;
+  return smooth_batch(check_tvl_smooth, "yfm_tvl_smooth_batch", ctx, model_kind, param_space, theta, P, B, T_use,
+                      beta_s, V_s, C_s);
 }
 
 int yfm_tvl_smooth_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
                                 const int* d_T_use, double* d_beta_s, double* d_V_s, double* d_C_s, void* hip_stream) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_tvl_smooth(ctx, "yfm_tvl_smooth_batch_device", model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!d_theta || !d_beta_s || !d_V_s)) return set_error(YFM_EINVAL, "null d_theta, d_beta_s or d_V_s");
-  YFM_HIP_CHECK(ctx->own.smooth_ll.ensure(sizeof(double) * (size_t)(B > 0 ? B : 1)));
-  const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use,
-                                 static_cast<double*>(ctx->own.smooth_ll.p), static_cast<hipStream_t>(hip_stream));
-  if (B == 0) return launch(ctx, q);
-  return smooth_chunks(ctx, q, d_beta_s, d_V_s, d_C_s, nullptr, nullptr, nullptr, false);
+  return smooth_batch_device(check_tvl_smooth, "yfm_tvl_smooth_batch_device", ctx, model_kind, param_space, d_theta,
+                             P, B, d_T_use, d_beta_s, d_V_s, d_C_s, hip_stream);
 }
 
 int yfm_filter_states(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
@@ -1438,29 +1425,12 @@ int yfm_predict(yfm_ctx* ctx, int model_kind, int param_space, const double* the
   a.factors = d + 3 * nN;
   a.states = d + 3 * nN + nM;
   if (yfm::msed_kind(model_kind)) {
-    // the λ kernel writes the outputs itself, into a NaN-filled block
-    YFM_HIP_CHECK(hipMemsetAsync(d, 0xff, sizeof(double) * (3 * nN + nM + nL), ctx->stream));
-    yfm::MsedRecord rec;
-    rec.mode = 1;
-    rec.horizon = horizon;
-    rec.ncol = (int)ncol;
-    rec.preds = a.preds;
-    rec.factors = a.factors;
-    rec.states = a.states;
-    rec.load1 = a.load1;
-    rec.load2 = a.load2;
-    q.msed_rec = &rec;
-    if (int r = launch(ctx, q)) return r;
+    if (int r = launch_record(ctx, q, 1, horizon, (int)ncol, a, sizeof(double) * (3 * nN + nM + nL))) return r;
   } else {
     q.rec_len = ctx->T + horizon;  // every step of the longest candidate
     if (int r = run_trajectory(ctx, q)) return r;
-    yfm::PredictArgs full = predict_args(ctx, q, horizon);
-    full.preds = a.preds;
-    full.load1 = a.load1;
-    full.load2 = a.load2;
-    full.factors = a.factors;
-    full.states = a.states;
-    YFM_HIP_CHECK(yfm::launch_predict_emit(full));
+    a = predict_args(ctx, q, horizon, a);
+    YFM_HIP_CHECK(yfm::launch_predict_emit(a));
   }
   YFM_HIP_CHECK(hipMemcpyAsync(preds, a.preds, sizeof(double) * nN, hipMemcpyDeviceToHost, ctx->stream));
   if (loadings_1)
@@ -1490,19 +1460,11 @@ int yfm_forecast(yfm_ctx* ctx, int model_kind, int param_space, const double* th
   yfm::PredictArgs a{};
   a.preds = static_cast<double*>(ctx->rec_P.p);
   if (yfm::msed_kind(model_kind)) {
-    YFM_HIP_CHECK(hipMemsetAsync(a.preds, 0xff, sizeof(double) * n, ctx->stream));
-    yfm::MsedRecord rec;
-    rec.mode = 2;
-    rec.horizon = horizon;
-    rec.preds = a.preds;
-    q.msed_rec = &rec;
-    if (int r = launch(ctx, q)) return r;
+    if (int r = launch_record(ctx, q, 2, horizon, 0, a, sizeof(double) * n)) return r;
   } else {
     q.rec_len = horizon + 1;
     if (int r = run_trajectory(ctx, q)) return r;
-    double* const blocks = a.preds;
-    a = predict_args(ctx, q, horizon);
-    a.preds = blocks;
+    a = predict_args(ctx, q, horizon, a);
     YFM_HIP_CHECK(yfm::launch_forecast_emit(a));
   }
   YFM_HIP_CHECK(hipMemcpyAsync(out, a.preds, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
@@ -1528,14 +1490,10 @@ int yfm_loss_array(yfm_ctx* ctx, int model_kind, int param_space, const double* 
     // get_loss_array of filter.jl:245-281: the λ kernel writes the rows itself (NaN beyond each window)
     const size_t nb = sizeof(double) * (size_t)T1 * B;
     YFM_HIP_CHECK(ctx->rec_P.ensure(nb));
-    YFM_HIP_CHECK(hipMemsetAsync(ctx->rec_P.p, 0xff, nb, ctx->stream));
-    yfm::MsedRecord rec;
-    rec.mode = 3;
-    rec.ncol = T1;
-    rec.preds = static_cast<double*>(ctx->rec_P.p);
-    q.msed_rec = &rec;
-    if (int r = launch(ctx, q)) return r;
-    YFM_HIP_CHECK(hipMemcpyAsync(mse_out, rec.preds, nb, hipMemcpyDeviceToHost, ctx->stream));
+    yfm::PredictArgs a{};
+    a.preds = static_cast<double*>(ctx->rec_P.p);
+    if (int r = launch_record(ctx, q, 3, 1, T1, a, nb)) return r;
+    YFM_HIP_CHECK(hipMemcpyAsync(mse_out, a.preds, nb, hipMemcpyDeviceToHost, ctx->stream));
     YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return YFM_OK;
   }
@@ -1562,8 +1520,9 @@ int yfm_loss_array(yfm_ctx* ctx, int model_kind, int param_space, const double* 
   unsigned int* cur = ctx->own.bank_ptr(ctx->own.bank);
   YFM_HIP_CHECK(hipMemsetAsync(cur, 0, 2 * sizeof(unsigned int), ctx->stream));
   YFM_HIP_CHECK(ctx->rec_P.ensure(sizeof(double) * (size_t)T1 * B));
-  yfm::PredictArgs a = predict_args(ctx, q, 1);
+  yfm::PredictArgs a{};
   a.preds = static_cast<double*>(ctx->rec_P.p);
+  a = predict_args(ctx, q, 1, a);
   YFM_HIP_CHECK(yfm::launch_loss_array(a, static_cast<const double*>(ctx->raw.p), T1, K, cur));
   YFM_HIP_CHECK(hipMemcpyAsync(mse_out, a.preds, sizeof(double) * (size_t)T1 * B, hipMemcpyDeviceToHost, ctx->stream));
   YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));

@@ -27,69 +27,44 @@ SIGNATURES = {
     "yfm_create": (_V, [ctypes.c_int]),
     "yfm_destroy": (None, [_V]),
     "yfm_set_panel": (ctypes.c_int, [_V, _D, ctypes.c_int, ctypes.c_int, _D]),
-    "yfm_loglik_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D]),
-    "yfm_loglik_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int, _V,
-                                               _V, _V]),
-    "yfm_filter_states": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D, _D,
-                                         _D]),
     "yfm_last_batch_flags": (ctypes.c_int, [_V, _LL, _LL]),
     "yfm_last_batch_deferred": (ctypes.c_int, [_V, _LL]),
     "yfm_last_batch_steady": (ctypes.c_int, [_V, _LL]),
+    "yfm_last_batch_grad_unavailable": (ctypes.c_int, [_V, _LL]),
     "yfm_gamma_dim": (ctypes.c_int, [ctypes.c_int]),
-    "yfm_predict": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, ctypes.c_int,
-                                   _D, _D, _D, _D, _D]),
-    "yfm_forecast": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, ctypes.c_int,
-                                    _D]),
-    "yfm_estimate": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, ctypes.c_int,
-                                    ctypes.c_double, ctypes.c_int, ctypes.c_double, _D, _D, _D, _D, _I, _LL]),
     "yfm_alloc_host": (_V, [ctypes.c_size_t]),
     "yfm_free_host": (ctypes.c_int, [_V]),
     "yfm_set_precision": (ctypes.c_int, [_V, ctypes.c_int]),
     "yfm_get_precision": (ctypes.c_int, [_V]),
-    "yfm_loss_array": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, ctypes.c_int,
-                                      _D]),
-    "yfm_loglik_grad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D,
-                                             _D]),
-    "yfm_loglik_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int,
-                                                    _V, _V, _V, _V]),
-    "yfm_last_batch_grad_unavailable": (ctypes.c_int, [_V, _LL]),
     "yfm_nm_block": (ctypes.c_int, [_V, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _I, ctypes.c_int, ctypes.c_int,
                                     ctypes.c_double, _D, _LL]),
-    "yfm_lambda_loss_grad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I,
-                                                  _D, _D]),
-    "yfm_lambda_loss_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
-                                                         ctypes.c_int, _V, _V, _V, _V]),
-    "yfm_lambda_loss_fullgrad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int,
-                                                      _I, _D, _D]),
-    "yfm_lambda_loss_fullgrad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
-                                                             ctypes.c_int, _V, _V, _V, _V]),
-    "yfm_neural_loss_grad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I,
-                                                  _D, _D]),
-    "yfm_neural_loss_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
-                                                         ctypes.c_int, _V, _V, _V, _V]),
-    "yfm_neural_loss_fullgrad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int,
-                                                      _I, _D, _D]),
-    "yfm_neural_loss_fullgrad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
-                                                             ctypes.c_int, _V, _V, _V, _V]),
-    "yfm_tvl_loglik_grad_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I,
-                                                 _D, _D]),
-    "yfm_tvl_loglik_grad_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int,
-                                                        ctypes.c_int, _V, _V, _V, _V]),
-    "yfm_loglik_scores_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D,
-                                               _D]),
-    "yfm_loglik_scores_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int,
-                                                      _V, _V, _V, _V]),
-    "yfm_loglik_info_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I,
-                                             ctypes.c_int, ctypes.c_double, _D, _D, _D, _D]),
-    "yfm_smooth_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D, _D,
-                                        _D]),
-    "yfm_smooth_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int, _V, _V,
-                                               _V, _V, _V]),
-    "yfm_tvl_smooth_batch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I, _D, _D,
-                                            _D]),
-    "yfm_tvl_smooth_batch_device": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int, _V,
-                                                   _V, _V, _V, _V]),
 }
+
+# The batched calls open alike: (ctx, model_kind, param_space, theta, P, B, T_use), with host pointers or — the
+# `_device` twins, which end with the stream — raw device addresses.
+_HOST = [_V, ctypes.c_int, ctypes.c_int, _D, ctypes.c_int, ctypes.c_int, _I]
+_DEVICE = [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int, _V]
+# family with a device twin → the output arrays after the prefix; host-only call → what follows the prefix
+_BATCH = {
+    "yfm_loglik_batch": 1,
+    "yfm_loglik_grad_batch": 2, "yfm_tvl_loglik_grad_batch": 2, "yfm_loglik_scores_batch": 2,
+    "yfm_lambda_loss_grad_batch": 2, "yfm_lambda_loss_fullgrad_batch": 2,
+    "yfm_neural_loss_grad_batch": 2, "yfm_neural_loss_fullgrad_batch": 2,
+    "yfm_smooth_batch": 3, "yfm_tvl_smooth_batch": 3,
+}
+_HOST_ONLY = {
+    "yfm_filter_states": [_D, _D, _D],
+    "yfm_predict": [ctypes.c_int, _D, _D, _D, _D, _D],
+    "yfm_forecast": [ctypes.c_int, _D],
+    "yfm_loss_array": [ctypes.c_int, _D],
+    "yfm_loglik_info_batch": [ctypes.c_int, ctypes.c_double, _D, _D, _D, _D],
+    "yfm_estimate": [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, _D, _D, _D, _D, _I, _LL],
+}
+for _name, _n in _BATCH.items():
+    SIGNATURES[_name] = (ctypes.c_int, _HOST + [_D] * _n)
+    SIGNATURES[_name + "_device"] = (ctypes.c_int, _DEVICE + [_V] * (_n + 1))
+for _name, _tail in _HOST_ONLY.items():
+    SIGNATURES[_name] = (ctypes.c_int, _HOST + _tail)
 
 ABI_VERSION = 5
 

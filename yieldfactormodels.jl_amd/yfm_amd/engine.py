@@ -15,6 +15,11 @@ from . import _lib
 from .params import KIND_DNS, KIND_GNS, KIND_TVL, gamma_dim, n_params, state_dim
 
 
+def _vp(x):
+    """An optional raw address (``torch.Tensor.data_ptr()``, a stream handle) as a C pointer; None or 0: null."""
+    return ctypes.c_void_p(x) if x else None
+
+
 class Engine:
     """Owns one ``yfm_ctx`` (include/yfm.h) on ``device``."""
 
@@ -83,53 +88,74 @@ class Engine:
         return 0 if self._panel is None else self._panel.shape[1]
 
     # ---- batched evaluation ----------------------------------------------------------
+    # One path per call family: the public methods below forward to these with the library symbol and what differs.
+    def _grad_call(self, symbol, kind, theta, space, T_use, rows):
+        """A host-pointer value-and-gradient call: (value[B], grad[rows, B]); rows None: one per row of θ."""
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        val = np.empty(B, dtype=np.float64)
+        grad = np.empty((P if rows is None else rows, B), dtype=np.float64, order="F")
+        _lib.check(getattr(self.lib, symbol)(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                             _lib.iptr(self._tuse(T_use, B)), _lib.dptr(val), _lib.dptr(grad)))
+        return val, grad
+
+    def _grad_call_device(self, symbol, kind, d_theta, P, B, d_out, d_grad, space, d_T_use, stream):
+        """The device-pointer twin: raw addresses in, nothing returned, asynchronous on ``stream``."""
+        _lib.check(getattr(self.lib, symbol)(self.ctx, kind, space, _vp(d_theta), P, B, _vp(d_T_use), _vp(d_out),
+                                             _vp(d_grad), _vp(stream)))
+
+    def _smooth_call(self, symbol, guard, what, kind, theta, space, T_use, lag_one):
+        """A host-pointer smoother call: (beta_s[M, T, B], V_s[M, M, T, B], C_s[M, M, T−1, B] or None)."""
+        guard(kind, what)
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        M, T = state_dim(kind), self.T
+        bs = np.empty((M, T, B), dtype=np.float64, order="F")
+        Vs = np.empty((M, M, T, B), dtype=np.float64, order="F")
+        Cs = np.empty((M, M, max(T - 1, 0), B), dtype=np.float64, order="F") if lag_one else None
+        _lib.check(getattr(self.lib, symbol)(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                             _lib.iptr(self._tuse(T_use, B)), _lib.dptr(bs), _lib.dptr(Vs),
+                                             _lib.dptr(Cs) if lag_one else None))
+        return bs, Vs, Cs
+
+    def _smooth_call_device(self, symbol, guard, what, kind, d_theta, P, B, d_beta_s, d_V_s, d_C_s, space, d_T_use,
+                            stream):
+        """The device-pointer twin of :meth:`_smooth_call`."""
+        guard(kind, what)
+        _lib.check(getattr(self.lib, symbol)(self.ctx, kind, space, _vp(d_theta), P, B, _vp(d_T_use), _vp(d_beta_s),
+                                             _vp(d_V_s), _vp(d_C_s), _vp(stream)))
+
     def loglik(self, kind: int, theta, space: int = 0, T_use=None, out=None) -> np.ndarray:
         """Θ: P×B (or a length-P vector).  Returns B logliks (+loglik, get_loss sign), written into
         `out` when given (e.g. a page-locked `host_array`)."""
-        Th = np.asarray(theta, dtype=np.float64)
-        if Th.ndim == 1:
-            Th = Th[:, None]
-        Th = np.asfortranarray(Th)
+        Th = self._batch(theta, kind)
         P, B = Th.shape
-        if P != n_params(kind):
-            raise ValueError(f"theta has {P} rows, model kind {kind} needs {n_params(kind)}")
         if out is None:
             out = np.empty(B, dtype=np.float64)
         elif out.shape != (B,) or out.dtype != np.float64 or not out.flags.c_contiguous:
             raise ValueError("out must be a contiguous float64 vector of length B")
-        tu = None if T_use is None else np.ascontiguousarray(np.broadcast_to(T_use, (B,)), dtype=np.int32)
-        _lib.check(self.lib.yfm_loglik_batch(self.ctx, kind, space, _lib.dptr(Th), P, B, _lib.iptr(tu),
-                                             _lib.dptr(out)))
+        _lib.check(self.lib.yfm_loglik_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                             _lib.iptr(self._tuse(T_use, B)), _lib.dptr(out)))
         return out
 
     def loglik_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, space: int = 0,
                       d_T_use: int | None = None, stream: int | None = None) -> None:
         """Device-pointer variant (raw addresses, e.g. ``torch.Tensor.data_ptr()``); asynchronous on ``stream``."""
-        _lib.check(self.lib.yfm_loglik_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
-                                                    ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                    ctypes.c_void_p(d_out),
-                                                    ctypes.c_void_p(stream) if stream else None))
+        _lib.check(self.lib.yfm_loglik_batch_device(self.ctx, kind, space, _vp(d_theta), P, B, _vp(d_T_use),
+                                                    _vp(d_out), _vp(stream)))
 
     def loglik_grad(self, kind: int, theta, space: int = 0, T_use=None):
         """(ll[B], grad[P, B]): the logliks of :meth:`loglik` and ∂(+loglik)/∂θ in the space passed
         (include/yfm.h yfm_loglik_grad_batch; DNS with N ≤ 64).  A candidate's gradient is NaN where its loglik
         is −Inf or NaN, and where it was evaluated on the double-double path (:meth:`last_grad_unavailable`)."""
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        ll = np.empty(B, dtype=np.float64)
-        grad = np.empty((P, B), dtype=np.float64, order="F")
-        _lib.check(self.lib.yfm_loglik_grad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                  _lib.iptr(self._tuse(T_use, B)), _lib.dptr(ll), _lib.dptr(grad)))
-        return ll, grad
+        return self._grad_call("yfm_loglik_grad_batch", kind, theta, space, T_use, None)
 
     def loglik_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int, space: int = 0,
                            d_T_use: int | None = None, stream: int | None = None) -> None:
         """Device-pointer variant of :meth:`loglik_grad` (raw addresses; d_grad: P×B column-major); asynchronous
         on ``stream``."""
-        _lib.check(self.lib.yfm_loglik_grad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
-                                                         ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                         ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
-                                                         ctypes.c_void_p(stream) if stream else None))
+        self._grad_call_device("yfm_loglik_grad_batch_device", kind, d_theta, P, B, d_out, d_grad, space, d_T_use,
+                               stream)
 
     def loglik_scores(self, kind: int, theta, space: int = 0, T_use=None):
         """(ll[B], S[P, T−1, B]): the logliks of :meth:`loglik` and the score series S[d, k, b] = ∂ℓ_k/∂θ_d, ℓ_k the
@@ -149,10 +175,8 @@ class Engine:
         """Device-pointer variant of :meth:`loglik_scores` (raw addresses; d_scores: P×(T−1)×B column-major);
         asynchronous on ``stream``."""
         self._dns_only(kind, "loglik_scores_device")
-        _lib.check(self.lib.yfm_loglik_scores_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
-                                                           ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                           ctypes.c_void_p(d_out), ctypes.c_void_p(d_scores),
-                                                           ctypes.c_void_p(stream) if stream else None))
+        self._grad_call_device("yfm_loglik_scores_batch_device", kind, d_theta, P, B, d_out, d_scores, space, d_T_use,
+                               stream)
 
     def loglik_info(self, kind: int, theta, space: int = 0, T_use=None, lags: int = 0, step: float | None = None,
                     hessian: bool = True, opg: bool = True) -> dict:
@@ -189,44 +213,27 @@ class Engine:
         precision, and ∂(+loglik)/∂θ in the space passed from the FP64 tangent recursion (include/yfm.h
         yfm_tvl_loglik_grad_batch).  A candidate's gradient is NaN where its loglik is −Inf or NaN, and where the
         tangent recursion's own value or tangents are not usable (:meth:`last_grad_unavailable`)."""
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        ll = np.empty(B, dtype=np.float64)
-        grad = np.empty((P, B), dtype=np.float64, order="F")
-        _lib.check(self.lib.yfm_tvl_loglik_grad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                      _lib.iptr(self._tuse(T_use, B)), _lib.dptr(ll), _lib.dptr(grad)))
-        return ll, grad
+        return self._grad_call("yfm_tvl_loglik_grad_batch", kind, theta, space, T_use, None)
 
     def tvl_loglik_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int, space: int = 0,
                                d_T_use: int | None = None, stream: int | None = None) -> None:
         """Device-pointer variant of :meth:`tvl_loglik_grad` (raw addresses; d_grad: 31×B column-major); asynchronous
         on `stream`, with the ordering rules of :meth:`loglik_device`."""
-        _lib.check(self.lib.yfm_tvl_loglik_grad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
-                                                             ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                             ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
-                                                             ctypes.c_void_p(stream) if stream else None))
+        self._grad_call_device("yfm_tvl_loglik_grad_batch_device", kind, d_theta, P, B, d_out, d_grad, space,
+                               d_T_use, stream)
 
     def lambda_loss_grad(self, kind: int, theta, space: int = 0, T_use=None):
         """(loss[B], grad[12, B]) of a λ model: get_loss as :meth:`loglik` returns it, bit for bit, and its
         derivative with respect to δ(3) and vec Φ(9, column-major) — θ's last 12 rows — in the space passed
         (include/yfm.h yfm_lambda_loss_grad_batch).  A candidate's gradient is NaN where its loss is −Inf."""
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        loss = np.empty(B, dtype=np.float64)
-        grad = np.empty((12, B), dtype=np.float64, order="F")
-        _lib.check(self.lib.yfm_lambda_loss_grad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                       _lib.iptr(self._tuse(T_use, B)), _lib.dptr(loss),
-                                                       _lib.dptr(grad)))
-        return loss, grad
+        return self._grad_call("yfm_lambda_loss_grad_batch", kind, theta, space, T_use, 12)
 
     def lambda_loss_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int,
                                 space: int = 0, d_T_use: int | None = None, stream: int | None = None) -> None:
         """Device-pointer variant of :meth:`lambda_loss_grad` (raw addresses; d_grad: 12×B column-major);
         asynchronous on ``stream``."""
-        _lib.check(self.lib.yfm_lambda_loss_grad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
-                                                              ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                              ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
-                                                              ctypes.c_void_p(stream) if stream else None))
+        self._grad_call_device("yfm_lambda_loss_grad_batch_device", kind, d_theta, P, B, d_out, d_grad, space,
+                               d_T_use, stream)
 
     def lambda_loss_full_grad(self, kind: int, theta, space: int = 0, T_use=None):
         """(loss[B], grad[P, B]) of a λ model: get_loss as :meth:`loglik` returns it, bit for bit, and its derivative
@@ -234,44 +241,26 @@ class Engine:
         leading rows (A, B, ω; γ for NS) from the tangent of the score recursion, the last 12 the rows of
         :meth:`lambda_loss_grad`, bit for bit.  A candidate's gradient is NaN where its loss is −Inf, and where a
         tangent is not finite (:meth:`last_grad_unavailable`)."""
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        loss = np.empty(B, dtype=np.float64)
-        grad = np.empty((P, B), dtype=np.float64, order="F")
-        _lib.check(self.lib.yfm_lambda_loss_fullgrad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                           _lib.iptr(self._tuse(T_use, B)), _lib.dptr(loss),
-                                                           _lib.dptr(grad)))
-        return loss, grad
+        return self._grad_call("yfm_lambda_loss_fullgrad_batch", kind, theta, space, T_use, None)
 
     def lambda_loss_full_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int,
                                      space: int = 0, d_T_use: int | None = None, stream: int | None = None) -> None:
         """Device-pointer variant of :meth:`lambda_loss_full_grad` (raw addresses; d_grad: P×B column-major);
         asynchronous on ``stream``."""
-        _lib.check(self.lib.yfm_lambda_loss_fullgrad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P,
-                                                                  B, ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                                  ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
-                                                                  ctypes.c_void_p(stream) if stream else None))
+        self._grad_call_device("yfm_lambda_loss_fullgrad_batch_device", kind, d_theta, P, B, d_out, d_grad, space,
+                               d_T_use, stream)
 
     def neural_loss_grad(self, kind: int, theta, space: int = 0, T_use=None):
         """:meth:`lambda_loss_grad` for a neural kind (include/yfm.h yfm_neural_loss_grad_batch): (loss[B],
         grad[12, B]), the loss :meth:`loglik`'s bit for bit, the gradient NaN where it is −Inf."""
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        loss = np.empty(B, dtype=np.float64)
-        grad = np.empty((12, B), dtype=np.float64, order="F")
-        _lib.check(self.lib.yfm_neural_loss_grad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                       _lib.iptr(self._tuse(T_use, B)), _lib.dptr(loss),
-                                                       _lib.dptr(grad)))
-        return loss, grad
+        return self._grad_call("yfm_neural_loss_grad_batch", kind, theta, space, T_use, 12)
 
     def neural_loss_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int,
                                 space: int = 0, d_T_use: int | None = None, stream: int | None = None) -> None:
         """Device-pointer variant of :meth:`neural_loss_grad` (raw addresses; d_grad: 12×B column-major);
         asynchronous on ``stream``."""
-        _lib.check(self.lib.yfm_neural_loss_grad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
-                                                              ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                              ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
-                                                              ctypes.c_void_p(stream) if stream else None))
+        self._grad_call_device("yfm_neural_loss_grad_batch_device", kind, d_theta, P, B, d_out, d_grad, space,
+                               d_T_use, stream)
 
     def neural_loss_full_grad(self, kind: int, theta, space: int = 0, T_use=None):
         """:meth:`lambda_loss_full_grad` for a neural kind (include/yfm.h yfm_neural_loss_fullgrad_batch): (loss[B],
@@ -279,36 +268,27 @@ class Engine:
         adjoint sweep over the score recursion, the last 12 the rows of :meth:`neural_loss_grad`, bit for bit.  A
         candidate's gradient is NaN where its loss is −Inf, and where an adjoint is not finite
         (:meth:`last_grad_unavailable`)."""
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        loss = np.empty(B, dtype=np.float64)
-        grad = np.empty((P, B), dtype=np.float64, order="F")
-        _lib.check(self.lib.yfm_neural_loss_fullgrad_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                           _lib.iptr(self._tuse(T_use, B)), _lib.dptr(loss),
-                                                           _lib.dptr(grad)))
-        return loss, grad
+        return self._grad_call("yfm_neural_loss_fullgrad_batch", kind, theta, space, T_use, None)
 
     def neural_loss_full_grad_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_grad: int,
                                      space: int = 0, d_T_use: int | None = None, stream: int | None = None) -> None:
         """Device-pointer variant of :meth:`neural_loss_full_grad` (raw addresses; d_grad: P×B column-major);
         asynchronous on ``stream``."""
-        _lib.check(self.lib.yfm_neural_loss_fullgrad_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P,
-                                                                  B, ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                                  ctypes.c_void_p(d_out), ctypes.c_void_p(d_grad),
-                                                                  ctypes.c_void_p(stream) if stream else None))
+        self._grad_call_device("yfm_neural_loss_fullgrad_batch_device", kind, d_theta, P, B, d_out, d_grad, space,
+                               d_T_use, stream)
 
     def filter_states(self, kind: int, theta, space: int = 0, T_use=None):
         """Returns (loglik[B], beta[M, T-1, B], P[M, M, T-1, B]) — a_{t+1|t}, P_{t+1|t} after each filter! call."""
-        Th = np.asfortranarray(np.atleast_2d(np.asarray(theta, dtype=np.float64).T).T)
+        Th = self._batch(theta, kind)
         P, B = Th.shape
         M = state_dim(kind)
         T = self.T
         out = np.empty(B)
         beta = np.empty((M, max(T - 1, 0), B), order="F")
         Pm = np.empty((M, M, max(T - 1, 0), B), order="F")
-        tu = None if T_use is None else np.ascontiguousarray(np.broadcast_to(T_use, (B,)), dtype=np.int32)
-        _lib.check(self.lib.yfm_filter_states(self.ctx, kind, space, _lib.dptr(Th), P, B, _lib.iptr(tu),
-                                              _lib.dptr(beta), _lib.dptr(Pm), _lib.dptr(out)))
+        _lib.check(self.lib.yfm_filter_states(self.ctx, kind, space, _lib.dptr(Th), P, B,
+                                              _lib.iptr(self._tuse(T_use, B)), _lib.dptr(beta), _lib.dptr(Pm),
+                                              _lib.dptr(out)))
         return out, beta, Pm
 
     @staticmethod
@@ -325,28 +305,15 @@ class Engine:
         ``lag_one``, C_t = Cov(β_{t+1}, β_t | y_1..n), with n = T_use[b] (None: every column).  NaN beyond a window, and
         in all of a candidate whose loglik is −Inf or NaN, that was evaluated on the double-double path or that has an
         output that is not finite (:meth:`last_grad_unavailable` counts them)."""
-        self._smooth_kinds(kind, "smooth")
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        M, T = state_dim(kind), self.T
-        bs = np.empty((M, T, B), dtype=np.float64, order="F")
-        Vs = np.empty((M, M, T, B), dtype=np.float64, order="F")
-        Cs = np.empty((M, M, max(T - 1, 0), B), dtype=np.float64, order="F") if lag_one else None
-        _lib.check(self.lib.yfm_smooth_batch(self.ctx, kind, space, _lib.dptr(Th), P, B, _lib.iptr(self._tuse(T_use, B)),
-                                             _lib.dptr(bs), _lib.dptr(Vs), _lib.dptr(Cs) if lag_one else None))
-        return bs, Vs, Cs
+        return self._smooth_call("yfm_smooth_batch", self._smooth_kinds, "smooth", kind, theta, space, T_use, lag_one)
 
     def smooth_device(self, kind: int, d_theta: int, P: int, B: int, d_beta_s: int, d_V_s: int,
                       d_C_s: int | None = None, space: int = 0, d_T_use: int | None = None,
                       stream: int | None = None) -> None:
         """Device-pointer variant of :meth:`smooth` (raw addresses; d_beta_s M×T×B, d_V_s M×M×T×B, d_C_s M×M×(T−1)×B
         column-major or None); asynchronous on ``stream``."""
-        self._smooth_kinds(kind, "smooth_device")
-        _lib.check(self.lib.yfm_smooth_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
-                                                    ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                    ctypes.c_void_p(d_beta_s), ctypes.c_void_p(d_V_s),
-                                                    ctypes.c_void_p(d_C_s) if d_C_s else None,
-                                                    ctypes.c_void_p(stream) if stream else None))
+        self._smooth_call_device("yfm_smooth_batch_device", self._smooth_kinds, "smooth_device", kind, d_theta, P, B,
+                                 d_beta_s, d_V_s, d_C_s, space, d_T_use, stream)
 
     @staticmethod
     def _tvl_smooth_kinds(kind, what):
@@ -362,29 +329,16 @@ class Engine:
         n = T_use[b] (None: every column).  NaN beyond a window, and in all of a candidate whose loglik is −Inf or NaN,
         that has a data column with det(σ²I + P_tG_t) ≤ 0 or an output that is not finite
         (:meth:`last_grad_unavailable` counts them)."""
-        self._tvl_smooth_kinds(kind, "tvl_smooth")
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        M, T = state_dim(kind), self.T
-        bs = np.empty((M, T, B), dtype=np.float64, order="F")
-        Vs = np.empty((M, M, T, B), dtype=np.float64, order="F")
-        Cs = np.empty((M, M, max(T - 1, 0), B), dtype=np.float64, order="F") if lag_one else None
-        _lib.check(self.lib.yfm_tvl_smooth_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                 _lib.iptr(self._tuse(T_use, B)), _lib.dptr(bs), _lib.dptr(Vs),
-                                                 _lib.dptr(Cs) if lag_one else None))
-        return bs, Vs, Cs
+        return self._smooth_call("yfm_tvl_smooth_batch", self._tvl_smooth_kinds, "tvl_smooth", kind, theta, space,
+                                 T_use, lag_one)
 
     def tvl_smooth_device(self, kind: int, d_theta: int, P: int, B: int, d_beta_s: int, d_V_s: int,
                           d_C_s: int | None = None, space: int = 0, d_T_use: int | None = None,
                           stream: int | None = None) -> None:
         """Device-pointer variant of :meth:`tvl_smooth` (raw addresses; d_beta_s 4×T×B, d_V_s 4×4×T×B, d_C_s
         4×4×(T−1)×B column-major or None); asynchronous on ``stream``."""
-        self._tvl_smooth_kinds(kind, "tvl_smooth_device")
-        _lib.check(self.lib.yfm_tvl_smooth_batch_device(self.ctx, kind, space, ctypes.c_void_p(d_theta), P, B,
-                                                        ctypes.c_void_p(d_T_use) if d_T_use else None,
-                                                        ctypes.c_void_p(d_beta_s), ctypes.c_void_p(d_V_s),
-                                                        ctypes.c_void_p(d_C_s) if d_C_s else None,
-                                                        ctypes.c_void_p(stream) if stream else None))
+        self._smooth_call_device("yfm_tvl_smooth_batch_device", self._tvl_smooth_kinds, "tvl_smooth_device", kind,
+                                 d_theta, P, B, d_beta_s, d_V_s, d_C_s, space, d_T_use, stream)
 
     @staticmethod
     def _batch(theta, kind):

@@ -530,14 +530,17 @@ def estimate_steps_(model: AbstractKalmanModel, data, all_params, param_groups=N
         r = estimate_steps_batch(model, data, start[:, None], param_groups=param_groups,
                                  max_group_iters=max_group_iters, tol=tol, iterations=iterations,
                                  full_gradient=full_gradient)
-        if printing:
-            print(f"✓ Best overall LL = {r['ll'][0]} from start 1")
-        return r["init_c"][:, 0].copy(), float(r["ll"][0]), r["theta_c"][:, 0].copy(), 0
+        return _first_chain(r, printing)
     if param_groups is not None and any(g != "1" for g in param_groups):
         raise NotImplementedError("Kalman models estimate every parameter in group \"1\"")
     r = estimate_batch(model, data, start[:, None], max_group_iters=max_group_iters, tol=tol, iterations=iterations)
     if r["status"][0] == 1:
         raise EstimationError("compute_loss threw on the first group iteration (singular initialize_filter)")
+    return _first_chain(r, printing)
+
+
+def _first_chain(r, printing):
+    """What estimate_steps! returns for a one-chain result `r`: (init_p, ll, best_p, ir)."""
     if printing:
         print(f"✓ Best overall LL = {r['ll'][0]} from start 1")
     return r["init_c"][:, 0].copy(), float(r["ll"][0]), r["theta_c"][:, 0].copy(), 0
@@ -653,9 +656,16 @@ def estimate_neural_steps_(model: AbstractKalmanModel, data, all_params, param_g
     start = A[:, 0] if A.ndim == 2 else A
     r = estimate_neural_steps_batch(model, data, start[:, None], param_groups=param_groups,
                                     max_group_iters=max_group_iters, tol=tol, iterations=iterations)
-    if printing:
-        print(f"✓ Best overall LL = {r['ll'][0]} from start 1")
-    return r["init_c"][:, 0].copy(), float(r["ll"][0]), r["theta_c"][:, 0].copy(), 0
+    return _first_chain(r, printing)
+
+
+def _neg_loss_grad(model, data, Theta, T_use, method, guard):
+    """(−value[B], −gradient[rows, B]) of the engine's gradient call `method` at the unconstrained columns of Θ, the
+    reference's loss sign.  `guard`: None, or why the model's kind is not served (raised before the panel is set)."""
+    if guard:
+        raise NotImplementedError(guard)
+    val, g = getattr(_engine(model, data), method)(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
+    return -val, -g
 
 
 def compute_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
@@ -664,24 +674,19 @@ def compute_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None)
     reference's loss sign.  DNS with N ≤ 64 (:meth:`Engine.loglik_grad`), TVλ (:meth:`Engine.tvl_loglik_grad`) and
     the λ models (:meth:`Engine.lambda_loss_full_grad`: −get_loss and its full gradient); NaN gradient columns as
     there."""
-    eng = _engine(model, data)
-    if _p.is_lambda_kind(model.kind):
-        fn = eng.lambda_loss_full_grad
-    else:
-        fn = eng.tvl_loglik_grad if model.kind == _p.KIND_TVL else eng.loglik_grad
-    ll, g = fn(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
-    return -ll, -g
+    method = ("lambda_loss_full_grad" if _p.is_lambda_kind(model.kind)
+              else "tvl_loglik_grad" if model.kind == _p.KIND_TVL else "loglik_grad")
+    return _neg_loss_grad(model, data, Theta, T_use, method, None)
 
 
 def compute_lambda_loss_grad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
     """Batched compute_loss of a λ model with its gradient over every row of θ — what an L-BFGS group of
     estimate_steps! that holds leading parameters evaluates: (−loss[B], −∂loss/∂θ[P, B]) for every unconstrained θ_b
     (:meth:`Engine.lambda_loss_full_grad`).  NaN gradient columns where the loss is −Inf or a tangent is not finite."""
-    if not _p.is_lambda_kind(model.kind):
-        raise NotImplementedError("the full loss gradient is the λ models'; Kalman models use compute_loss_grad_batch, "
-                                  "neural models compute_neural_loss_grad_block")
-    loss, g = _engine(model, data).lambda_loss_full_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
-    return -loss, -g
+    guard = None if _p.is_lambda_kind(model.kind) else (
+        "the full loss gradient is the λ models'; Kalman models use compute_loss_grad_batch, "
+        "neural models compute_neural_loss_grad_block")
+    return _neg_loss_grad(model, data, Theta, T_use, "lambda_loss_full_grad", guard)
 
 
 def compute_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_use=None):
@@ -689,32 +694,27 @@ def compute_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_use=None)
     in estimate_steps! for the δ/Φ block (optimization.jl:442-479): (−loss[B], −∂loss/∂θ[12, B]) for every
     unconstrained θ_b, the rows being θ's last 12 (δ, then vec Φ column-major).  NaN gradient columns where the
     loss is −Inf."""
-    if _p.is_neural_kind(model.kind):
-        raise NotImplementedError("compute_loss_grad_block is " + _NEURAL_GAP)
-    if not _p.is_lambda_kind(model.kind):
-        raise NotImplementedError("the δ/Φ block gradient is the λ models'; Kalman models use compute_loss_grad_batch")
-    loss, g = _engine(model, data).lambda_loss_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
-    return -loss, -g
+    guard = ("compute_loss_grad_block is " + _NEURAL_GAP if _p.is_neural_kind(model.kind)
+             else None if _p.is_lambda_kind(model.kind)
+             else "the δ/Φ block gradient is the λ models'; Kalman models use compute_loss_grad_batch")
+    return _neg_loss_grad(model, data, Theta, T_use, "lambda_loss_grad", guard)
 
 
 def compute_neural_loss_grad_block(model: AbstractKalmanModel, data, Theta, T_use=None):
     """:func:`compute_loss_grad_block` for the neural kinds: (−loss[B], −∂loss/∂θ[12, B]) over θ's last 12 rows."""
-    if not _p.is_neural_kind(model.kind):
-        raise NotImplementedError("compute_neural_loss_grad_block is the neural models'; λ models use "
-                                  "compute_loss_grad_block")
-    loss, g = _engine(model, data).neural_loss_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
-    return -loss, -g
+    guard = None if _p.is_neural_kind(model.kind) else (
+        "compute_neural_loss_grad_block is the neural models'; λ models use compute_loss_grad_block")
+    return _neg_loss_grad(model, data, Theta, T_use, "neural_loss_grad", guard)
 
 
 def compute_neural_loss_fullgrad_batch(model: AbstractKalmanModel, data, Theta, T_use=None):
     """Batched compute_loss of a neural model with its gradient over every row of θ — what an L-BFGS over all
     parameters evaluates: (−loss[B], −∂loss/∂θ[P, B]) for every unconstrained θ_b
     (:meth:`Engine.neural_loss_full_grad`).  NaN gradient columns where the loss is −Inf or an adjoint is not finite."""
-    if not _p.is_neural_kind(model.kind):
-        raise NotImplementedError("compute_neural_loss_fullgrad_batch is the neural models'; λ models use "
-                                  "compute_lambda_loss_grad_batch, Kalman models compute_loss_grad_batch")
-    loss, g = _engine(model, data).neural_loss_full_grad(model.kind, Theta, space=_p.SPACE_UNCONSTRAINED, T_use=T_use)
-    return -loss, -g
+    guard = None if _p.is_neural_kind(model.kind) else (
+        "compute_neural_loss_fullgrad_batch is the neural models'; λ models use "
+        "compute_lambda_loss_grad_batch, Kalman models compute_loss_grad_batch")
+    return _neg_loss_grad(model, data, Theta, T_use, "neural_loss_full_grad", guard)
 
 
 def estimate_lbfgs_batch(model: AbstractKalmanModel, data, Theta0, space: int = 1, T_use=None, **opts) -> dict:

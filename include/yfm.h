@@ -453,6 +453,43 @@ int yfm_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const d
                           const int* T_use, int lags, double step, double* loglik_out, double* grad_out,
                           double* hess_out, double* opg_out);
 
+/* The same three calls for the TVλ model (P = 31): score series, OPG / HAC matrix and Hessian of the extended-Kalman-
+ * filter log-likelihood that yfm_tvl_loglik_grad_batch differentiates.  AN EXTENSION, as the DNS calls above are: the
+ * reference's estimate! returns no covariance.  The argument lists are those of the DNS namesakes.
+ *   Score series: S[d, k, b] = ∂ℓ_k/∂θ_d for 1 ≤ k ≤ nobs_b − 2 and exactly 0.0 elsewhere (column 0, the columns from
+ * nobs_b − 1 on, and every column when T_use[b] ≤ 2), ℓ_k the term get_loss adds after column k (at a NaN column the
+ * stale term, added again); scores_out is 31 × (T − 1) × B column-major, θ in the space passed.  Σ_k S[:, k, b] is
+ * yfm_tvl_loglik_grad_batch's gradient up to the order of the sum.  The series comes from the FP64 tangent recursion:
+ * it is the same bits under either yfm_set_precision setting and in whatever batch the candidate sits.
+ *   OPG / HAC matrix: J = Γ_0 + Σ_{ℓ=1}^{lags} (1 − ℓ/(lags+1))(Γ_ℓ + Γ_ℓ'), Γ_ℓ = Σ_k s_k s_{k−ℓ}' (Bartlett weights,
+ * lags = 0: the plain outer product; lags ≥ nobs − 2 is allowed).  opg_out is 31 × 31 × B, symmetric to the bit.
+ *   Hessian: H = ½(D + D'), D_i = (8(g(θ+h e_i) − g(θ−h e_i)) − (g(θ+2h e_i) − g(θ−2h e_i)))/(12h) over the realised
+ * steps, g the exact gradient: 4P = 124 perturbed candidates per θ through the TVλ loglik launch at the context's
+ * precision and the gradient kernel, the sequence of yfm_tvl_loglik_grad_batch.  step ≤ 0 asks for the default
+ * h = YFM_TVL_INFO_DEFAULT_STEP.  hess_out is 31 × 31 × B, symmetric to the bit.
+ *   Unavailable: the gradient's rule.  A candidate has NaN in all of S, J and H where its loglik is −Inf or NaN, where
+ * the tangent recursion's own FP64 value is not finite or meets a non-positive determinant, or where an entry of its
+ * gradient is not finite; and in all of H also where any of its 124 perturbed points has a NaN gradient.
+ * yfm_last_batch_grad_unavailable counts, after yfm_tvl_loglik_scores_batch(_device), what it counts after
+ * yfm_tvl_loglik_grad_batch and, after yfm_tvl_loglik_info_batch, the candidates with NaN in H (hess_out NULL: in J);
+ * the other yfm_last_batch_* counters then answer for the batch's own loglik launch.
+ *   loglik_out is bitwise yfm_loglik_batch's and grad_out bitwise yfm_tvl_loglik_grad_batch's.  Beyond the staging that
+ * yfm_tvl_loglik_grad_batch allocates for the same batch, no temporary exceeds 128 MiB: the scores, the perturbed
+ * points with the work records of their launches, H and J go chunk by chunk, and a candidate's outputs do not depend on
+ * how the batch is cut.
+ *   YFM_MODEL_TVL only, with every N the TVλ gradient accepts: every other kind returns YFM_EUNSUPPORTED (DNS has the
+ * calls above); lags < 0 and two NULL outputs return YFM_EINVAL.  yfm_loglik_scores_batch and yfm_loglik_info_batch
+ * keep refusing TVλ.  Additive: YFM_ABI_VERSION stays 5; a library that has the symbols has the feature. */
+#define YFM_TVL_INFO_DEFAULT_STEP 1e-5
+int yfm_tvl_loglik_scores_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                                const int* T_use, double* loglik_out, double* scores_out);
+int yfm_tvl_loglik_scores_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                       int B, const int* d_T_use, double* d_loglik_out, double* d_scores_out,
+                                       void* hip_stream);
+int yfm_tvl_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                              const int* T_use, int lags, double step, double* loglik_out, double* grad_out,
+                              double* hess_out, double* opg_out);
+
 /* The fixed-interval Kalman smoother of the fixed-loading models — β̂_{t|n} = E[β_t | y_1 … y_n], its covariance and the
  * lag-one covariance: level, slope and curvature paths, fitted curves, residuals that are not one-step forecasts, and
  * the moments Σ V_t, Σ C_t of an EM step.  AN EXTENSION: the reference has no counterpart (its predict, filter.jl:250-282,

@@ -715,6 +715,29 @@ int check_info(yfm_ctx* ctx, const char* what, int kind, int space, int P, int B
   return YFM_OK;
 }
 
+// The TVλ score / information entry points' model check: they run the TVλ tangent recursion, every N it takes.
+int check_tvl_info(yfm_ctx* ctx, const char* what, int kind, int space, int P, int B) {
+  if (state_dim(kind) >= 0 && kind != YFM_MODEL_TVL)
+    return set_error(YFM_EUNSUPPORTED, "%s is built for YFM_MODEL_TVL only (model_kind %d): the DNS score series, "
+                     "information matrix and Hessian are yfm_loglik_scores_batch and yfm_loglik_info_batch, and none "
+                     "exists for the other kinds", what, kind);
+  if (int r = check_batch(ctx, kind, space, P, B)) return r;
+  if (ctx->N > yfm::tvl_grad_max_n())
+    return set_error(YFM_EUNSUPPORTED, "N = %d maturities exceeds the %d of the tangent kernel that %s runs", ctx->N,
+                     yfm::tvl_grad_max_n(), what);
+  return YFM_OK;
+}
+
+// A score / information call family: its model check, its default Hessian step and the gradient call its messages
+// point to.  Its kernels follow the kind (score_launch, launch_grad, launch_opg by P).
+struct InfoFamily {
+  int (*check)(yfm_ctx*, const char*, int, int, int, int);
+  double default_step;
+  const char* grad_call;
+};
+const InfoFamily kDnsInfo{check_info, YFM_INFO_DEFAULT_STEP, "yfm_loglik_grad_batch"};
+const InfoFamily kTvlInfo{check_tvl_info, YFM_TVL_INFO_DEFAULT_STEP, "yfm_tvl_loglik_grad_batch"};
+
 // No temporary that the score / information entry points add is larger than this: bigger batches go chunk by chunk.
 // (The batch's own staging — θ, T_use, loglik, gradient and the work records of its loglik launch — is what
 // yfm_loglik_grad_batch allocates for the same batch.)
@@ -731,6 +754,18 @@ size_t fixedz_launch_bytes(int kind, int n) {
   return std::max({yfm::fixedz_dd_scratch_bytes(kind, n), yfm::fixedz_scratch_bytes(kind, n), sizeof(int) * (size_t)n});
 }
 
+// The work records enqueue() grows for a TVλ loglik launch of n candidates under the context's precision.
+size_t tvl_launch_bytes(const yfm_ctx* ctx, int n) {
+  return ctx->precision == YFM_PREC_CERTIFIED ? yfm::tvl_dd_scratch_bytes(n) : yfm::tvl_scratch_bytes(n);
+}
+
+// The score kernel of q's kind for candidates b0 … b0 + nb − 1 of the loglik launch q (`count`: DNS counts the
+// deferred into the launch's bank; the TVλ kernel always counts its own unavailable candidates there).
+hipError_t score_launch(const yfm::LaunchArgs& a, const Launch& q, double* d_scores, int b0, int nb, bool count) {
+  return q.kind == YFM_MODEL_TVL ? yfm::launch_tvl_scores(a, q.out, d_scores, b0, nb)
+                                 : yfm::launch_dns_scores(a, q.out, d_scores, b0, nb, count);
+}
+
 // The scores of the candidates of the loglik launch q (the last one enqueued on the own workspace), chunk by chunk
 // through info_scores; `each(b0, nb, d_scores)` consumes a chunk before the next one overwrites it (same stream).
 // `out_per`: bytes per candidate of what `each` itself keeps per chunk.
@@ -743,7 +778,7 @@ int for_score_chunks(yfm_ctx* ctx, const Launch& q, bool count, size_t out_per, 
   const yfm::LaunchArgs a = tangent_args(ctx, q);
   for (int b0 = 0; b0 < q.B; b0 += chunk) {
     const int nb = std::min(chunk, q.B - b0);
-    const hipError_t e = yfm::launch_dns_scores(a, q.out, d_scores, b0, nb, count);
+    const hipError_t e = score_launch(a, q, d_scores, b0, nb, count);
     if (e != hipSuccess) {
       ctx->own.bank_dirty = true;
       return set_error(YFM_EHIP, "score kernel launch: %s", hipGetErrorString(e));
@@ -769,10 +804,11 @@ int fit_chunk(int start, F&& need) {
 
 // Candidates per Hessian chunk: the 4P perturbed θ and their gradients (P doubles per point each), and everything the
 // loglik launch of the chunk's 4P·nb points allocates, each within kInfoChunkBytes.
-int hessian_chunk(int kind, int P, int B) {
+int hessian_chunk(const yfm_ctx* ctx, int kind, int P, int B) {
   const size_t np = 4 * (size_t)P;
-  return fit_chunk(info_chunk(sizeof(double) * (size_t)P * np, B),
-                   [&](int n) { return fixedz_launch_bytes(kind, (int)(np * n)); });
+  return fit_chunk(info_chunk(sizeof(double) * (size_t)P * np, B), [&](int n) {
+    return kind == YFM_MODEL_TVL ? tvl_launch_bytes(ctx, (int)(np * n)) : fixedz_launch_bytes(kind, (int)(np * n));
+  });
 }
 
 // H of every candidate of the staged launch q, chunk by chunk: the perturbed points, their logliks and gradients (the
@@ -782,7 +818,7 @@ int hessian_chunks(yfm_ctx* ctx, const Launch& q, double h, const double* d_grad
                    double* hess_out) {
   yfm::Workspace& w = ctx->own;
   const size_t P = (size_t)q.P, np = 4 * P;  // points per candidate
-  const int chunk = hessian_chunk(q.kind, q.P, q.B);
+  const int chunk = hessian_chunk(ctx, q.kind, q.P, q.B);
   YFM_HIP_CHECK(w.info_pts.ensure(sizeof(double) * P * np * chunk));
   YFM_HIP_CHECK(w.info_pgrad.ensure(sizeof(double) * P * np * chunk));
   // logliks (np), realised steps (2P), windows (np ints) per candidate
@@ -805,6 +841,110 @@ int hessian_chunks(yfm_ctx* ctx, const Launch& q, double h, const double* d_grad
     YFM_HIP_CHECK(hipMemcpyAsync(hess_out + P * P * b0, d_H, sizeof(double) * P * P * nb, hipMemcpyDeviceToHost,
                                  q.stream));
   }
+  return YFM_OK;
+}
+
+// The score entry points of a family: the loglik launch, then the scores chunk by chunk to the host.
+int scores_batch(const InfoFamily& f, const char* what, yfm_ctx* ctx, int model_kind, int param_space,
+                 const double* theta, int P, int B, const int* T_use, double* loglik_out, double* scores_out) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = f.check(ctx, what, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!theta || !loglik_out || !scores_out))
+    return set_error(YFM_EINVAL, "null theta, loglik_out or scores_out");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  if (int r = launch(ctx, q)) return r;
+  if (B > 0) {
+    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    const size_t per = (size_t)P * (size_t)(ctx->T - 1);
+    const int rc = for_score_chunks(ctx, q, true, 0, [&](int b0, int nb, const double* d_scores) {
+      if (per > 0)
+        YFM_HIP_CHECK(hipMemcpyAsync(scores_out + per * b0, d_scores, sizeof(double) * per * nb, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+      return (int)YFM_OK;
+    });
+    if (rc != YFM_OK) return rc;
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+  return YFM_OK;
+}
+
+// Their device-pointer twin: both launches alone, asynchronous on the caller's stream.
+int scores_batch_device(const InfoFamily& f, const char* what, yfm_ctx* ctx, int model_kind, int param_space,
+                        const double* d_theta, int P, int B, const int* d_T_use, double* d_loglik_out,
+                        double* d_scores_out, void* hip_stream) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = f.check(ctx, what, model_kind, param_space, P, B)) return r;
+  if (B > 0 && (!d_theta || !d_loglik_out || !d_scores_out))
+    return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_scores_out");
+  const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
+                                 static_cast<hipStream_t>(hip_stream));
+  if (int r = launch(ctx, q)) return r;
+  if (B == 0) return YFM_OK;
+  const hipError_t e = score_launch(tangent_args(ctx, q), q, d_scores_out, 0, B, true);
+  if (e != hipSuccess) {
+    ctx->own.bank_dirty = true;
+    return set_error(YFM_EHIP, "score kernel launch: %s", hipGetErrorString(e));
+  }
+  return YFM_OK;
+}
+
+// The information entry points of a family: loglik and gradient, J from the score chunks, H from the Hessian chunks.
+int info_batch(const InfoFamily& f, const char* what, yfm_ctx* ctx, int model_kind, int param_space, const double* theta,
+               int P, int B, const int* T_use, int lags, double step, double* loglik_out, double* grad_out,
+               double* hess_out, double* opg_out) {
+  if (int r = check_ctx(ctx)) return r;
+  if (int r = f.check(ctx, what, model_kind, param_space, P, B)) return r;
+  if (lags < 0) return set_error(YFM_EINVAL, "lags = %d < 0 (0: the plain outer product of the scores)", lags);
+  if (!hess_out && !opg_out)
+    return set_error(YFM_EINVAL, "hess_out and opg_out are both null: %s is the call for the loglik and its gradient "
+                     "alone", f.grad_call);
+  if (!(step == step) || step > 1.79769313486231570815e308)
+    return set_error(YFM_EINVAL, "step is not a finite number (<= 0: the default)");
+  if (B > 0 && (!theta || !loglik_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loglik_out or grad_out");
+  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
+  Launch q;
+  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
+  yfm::Workspace& w = ctx->own;
+  const size_t PP = (size_t)P * P;
+  YFM_HIP_CHECK(w.grad.ensure(sizeof(double) * (size_t)P * (size_t)(B > 0 ? B : 1)));
+  YFM_HIP_CHECK(w.info_flags.ensure(sizeof(unsigned int) * (yfm::kFlagsPerBank + 1)));
+  double* const d_grad = static_cast<double*>(w.grad.p);
+  unsigned int* const d_saved = static_cast<unsigned int*>(w.info_flags.p);
+  unsigned int* const d_count = d_saved + yfm::kFlagsPerBank;  // the candidates with a NaN H (no Hessian: a NaN J)
+  YFM_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned int), ctx->stream));
+  // the batch's own loglik and gradient, bitwise the gradient call's
+  if (int r = launch_grad(ctx, q, d_grad)) return r;
+  if (B > 0) {
+    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
+    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, d_grad, sizeof(double) * (size_t)P * B, hipMemcpyDeviceToHost, ctx->stream));
+    if (opg_out) {  // before any other launch: the scores read this launch's deferral list
+      const int rc = for_score_chunks(ctx, q, false, sizeof(double) * PP, [&](int b0, int nb, const double* d_scores) {
+        YFM_HIP_CHECK(w.info_out.ensure(sizeof(double) * PP * nb));
+        double* const d_J = static_cast<double*>(w.info_out.p);
+        YFM_HIP_CHECK(yfm::launch_opg(P, d_scores, ctx->T, nb, q.T_use ? q.T_use + b0 : nullptr, lags,
+                                      d_grad + (size_t)P * b0, d_J, hess_out ? nullptr : d_count, ctx->stream));
+        YFM_HIP_CHECK(hipMemcpyAsync(opg_out + PP * b0, d_J, sizeof(double) * PP * nb, hipMemcpyDeviceToHost,
+                                     ctx->stream));
+        return (int)YFM_OK;
+      });
+      if (rc != YFM_OK) return rc;
+    }
+    if (hess_out) {
+      // the perturbed launches take over the counter banks: the batch's own counters are kept and put back into the
+      // bank of the last launch, so yfm_last_batch_flags, _deferred and _steady answer for the batch itself
+      YFM_HIP_CHECK(hipMemcpyAsync(d_saved, w.bank_ptr(w.bank), sizeof(unsigned int) * yfm::kFlagsPerBank,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+      if (int r = hessian_chunks(ctx, q, step > 0.0 ? step : f.default_step, d_grad, d_count, hess_out))
+        return r;
+      YFM_HIP_CHECK(hipMemcpyAsync(w.bank_ptr(w.bank), d_saved, sizeof(unsigned int) * yfm::kFlagsPerBank,
+                                   hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    YFM_HIP_CHECK(hipMemcpyAsync(w.bank_ptr(w.bank) + 5, d_count, sizeof(unsigned int), hipMemcpyDeviceToDevice,
+                                 ctx->stream));
+  }
+  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
   return YFM_OK;
 }
 
@@ -853,9 +993,7 @@ int smooth_chunk(int kind, int M, int T, int B) {
 int tvl_smooth_chunk(const yfm_ctx* ctx, int T, int B) {
   const size_t rec = sizeof(double) * 20 * (size_t)std::max(T - 1, 1);
   const size_t out = sizeof(double) * 16 * (size_t)T;
-  return fit_chunk(info_chunk(std::max(rec, out), B), [&](int n) {
-    return ctx->precision == YFM_PREC_CERTIFIED ? yfm::tvl_dd_scratch_bytes(n) : yfm::tvl_scratch_bytes(n);
-  });
+  return fit_chunk(info_chunk(std::max(rec, out), B), [&](int n) { return tvl_launch_bytes(ctx, n); });
 }
 
 // The smoother over the candidates of q (θ, T_use and the logliks q.out on the device), chunk by chunk on q.stream:
@@ -1221,102 +1359,41 @@ int yfm_last_batch_grad_unavailable(yfm_ctx* ctx, long long* n) {
 
 int yfm_loglik_scores_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                             const int* T_use, double* loglik_out, double* scores_out) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_info(ctx, "yfm_loglik_scores_batch", model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!theta || !loglik_out || !scores_out))
-    return set_error(YFM_EINVAL, "null theta, loglik_out or scores_out");
-  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
-  Launch q;
-  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  if (int r = launch(ctx, q)) return r;
-  if (B > 0) {
-    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
-    const size_t per = (size_t)P * (size_t)(ctx->T - 1);
-    const int rc = for_score_chunks(ctx, q, true, 0, [&](int b0, int nb, const double* d_scores) {
-      if (per > 0)
-        YFM_HIP_CHECK(hipMemcpyAsync(scores_out + per * b0, d_scores, sizeof(double) * per * nb, hipMemcpyDeviceToHost,
-                                     ctx->stream));
-      return (int)YFM_OK;
-    });
-    if (rc != YFM_OK) return rc;
-  }
-  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return YFM_OK;
+  return scores_batch(kDnsInfo, "yfm_loglik_scores_batch", ctx, model_kind, param_space, theta, P, B, T_use, loglik_out,
+                      scores_out);
 }
 
 int yfm_loglik_scores_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P, int B,
                                    const int* d_T_use, double* d_loglik_out, double* d_scores_out, void* hip_stream) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_info(ctx, "yfm_loglik_scores_batch_device", model_kind, param_space, P, B)) return r;
-  if (B > 0 && (!d_theta || !d_loglik_out || !d_scores_out))
-    return set_error(YFM_EINVAL, "null d_theta, d_loglik_out or d_scores_out");
-  const Launch q = loglik_launch(model_kind, param_space, d_theta, P, B, d_T_use, d_loglik_out,
-                                 static_cast<hipStream_t>(hip_stream));
-  if (int r = launch(ctx, q)) return r;
-  if (B == 0) return YFM_OK;
-  const hipError_t e = yfm::launch_dns_scores(tangent_args(ctx, q), q.out, d_scores_out, 0, B, true);
-  if (e != hipSuccess) {
-    ctx->own.bank_dirty = true;
-    return set_error(YFM_EHIP, "score kernel launch: %s", hipGetErrorString(e));
-  }
-  return YFM_OK;
+  return scores_batch_device(kDnsInfo, "yfm_loglik_scores_batch_device", ctx, model_kind, param_space, d_theta, P, B,
+                             d_T_use, d_loglik_out, d_scores_out, hip_stream);
 }
 
 int yfm_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
                           const int* T_use, int lags, double step, double* loglik_out, double* grad_out,
                           double* hess_out, double* opg_out) {
-  if (int r = check_ctx(ctx)) return r;
-  if (int r = check_info(ctx, "yfm_loglik_info_batch", model_kind, param_space, P, B)) return r;
-  if (lags < 0) return set_error(YFM_EINVAL, "lags = %d < 0 (0: the plain outer product of the scores)", lags);
-  if (!hess_out && !opg_out)
-    return set_error(YFM_EINVAL, "hess_out and opg_out are both null: yfm_loglik_grad_batch is the call for the "
-                     "loglik and its gradient alone");
-  if (!(step == step) || step > 1.79769313486231570815e308)
-    return set_error(YFM_EINVAL, "step is not a finite number (<= 0: the default)");
-  if (B > 0 && (!theta || !loglik_out || !grad_out)) return set_error(YFM_EINVAL, "null theta, loglik_out or grad_out");
-  if (int r = validate_tuse(T_use, B, ctx->T)) return r;
-  Launch q;
-  if (int r = stage_inputs(ctx, model_kind, param_space, theta, P, B, T_use, q)) return r;
-  yfm::Workspace& w = ctx->own;
-  const size_t PP = (size_t)P * P;
-  YFM_HIP_CHECK(w.grad.ensure(sizeof(double) * (size_t)P * (size_t)(B > 0 ? B : 1)));
-  YFM_HIP_CHECK(w.info_flags.ensure(sizeof(unsigned int) * (yfm::kFlagsPerBank + 1)));
-  double* const d_grad = static_cast<double*>(w.grad.p);
-  unsigned int* const d_saved = static_cast<unsigned int*>(w.info_flags.p);
-  unsigned int* const d_count = d_saved + yfm::kFlagsPerBank;  // the candidates with a NaN H (no Hessian: a NaN J)
-  YFM_HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(unsigned int), ctx->stream));
-  // the batch's own loglik and gradient, bitwise yfm_loglik_grad_batch's
-  if (int r = launch_grad(ctx, q, d_grad)) return r;
-  if (B > 0) {
-    YFM_HIP_CHECK(hipMemcpyAsync(loglik_out, q.out, sizeof(double) * B, hipMemcpyDeviceToHost, ctx->stream));
-    YFM_HIP_CHECK(hipMemcpyAsync(grad_out, d_grad, sizeof(double) * (size_t)P * B, hipMemcpyDeviceToHost, ctx->stream));
-    if (opg_out) {  // before any other launch: the scores read this launch's deferral list
-      const int rc = for_score_chunks(ctx, q, false, sizeof(double) * PP, [&](int b0, int nb, const double* d_scores) {
-        YFM_HIP_CHECK(w.info_out.ensure(sizeof(double) * PP * nb));
-        double* const d_J = static_cast<double*>(w.info_out.p);
-        YFM_HIP_CHECK(yfm::launch_opg(d_scores, ctx->T, nb, q.T_use ? q.T_use + b0 : nullptr, lags,
-                                      d_grad + (size_t)P * b0, d_J, hess_out ? nullptr : d_count, ctx->stream));
-        YFM_HIP_CHECK(hipMemcpyAsync(opg_out + PP * b0, d_J, sizeof(double) * PP * nb, hipMemcpyDeviceToHost,
-                                     ctx->stream));
-        return (int)YFM_OK;
-      });
-      if (rc != YFM_OK) return rc;
-    }
-    if (hess_out) {
-      // the perturbed launches take over the counter banks: the batch's own counters are kept and put back into the
-      // bank of the last launch, so yfm_last_batch_flags, _deferred and _steady answer for the batch itself
-      YFM_HIP_CHECK(hipMemcpyAsync(d_saved, w.bank_ptr(w.bank), sizeof(unsigned int) * yfm::kFlagsPerBank,
-                                   hipMemcpyDeviceToDevice, ctx->stream));
-      if (int r = hessian_chunks(ctx, q, step > 0.0 ? step : YFM_INFO_DEFAULT_STEP, d_grad, d_count, hess_out))
-        return r;
-      YFM_HIP_CHECK(hipMemcpyAsync(w.bank_ptr(w.bank), d_saved, sizeof(unsigned int) * yfm::kFlagsPerBank,
-                                   hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    YFM_HIP_CHECK(hipMemcpyAsync(w.bank_ptr(w.bank) + 5, d_count, sizeof(unsigned int), hipMemcpyDeviceToDevice,
-                                 ctx->stream));
-  }
-  YFM_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-  return YFM_OK;
+  return info_batch(kDnsInfo, "yfm_loglik_info_batch", ctx, model_kind, param_space, theta, P, B, T_use, lags, step,
+                    loglik_out, grad_out, hess_out, opg_out);
+}
+
+int yfm_tvl_loglik_scores_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                                const int* T_use, double* loglik_out, double* scores_out) {
+  return scores_batch(kTvlInfo, "yfm_tvl_loglik_scores_batch", ctx, model_kind, param_space, theta, P, B, T_use,
+                      loglik_out, scores_out);
+}
+
+int yfm_tvl_loglik_scores_batch_device(yfm_ctx* ctx, int model_kind, int param_space, const double* d_theta, int P,
+                                       int B, const int* d_T_use, double* d_loglik_out, double* d_scores_out,
+                                       void* hip_stream) {
+  return scores_batch_device(kTvlInfo, "yfm_tvl_loglik_scores_batch_device", ctx, model_kind, param_space, d_theta, P,
+                             B, d_T_use, d_loglik_out, d_scores_out, hip_stream);
+}
+
+int yfm_tvl_loglik_info_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,
+                              const int* T_use, int lags, double step, double* loglik_out, double* grad_out,
+                              double* hess_out, double* opg_out) {
+  return info_batch(kTvlInfo, "yfm_tvl_loglik_info_batch", ctx, model_kind, param_space, theta, P, B, T_use, lags, step,
+                    loglik_out, grad_out, hess_out, opg_out);
 }
 
 int yfm_smooth_batch(yfm_ctx* ctx, int model_kind, int param_space, const double* theta, int P, int B,

@@ -87,10 +87,11 @@ hipError_t launch_dns_grad(const LaunchArgs& a, const double* ll, double* grad_o
 // (P × (T − 1) × nb column-major, starting at candidate b0), exact zeros outside a window's accumulated columns, NaN
 // where ll[b] is not finite or b was deferred (`count`: the deferred counted into a.flags[5]).
 hipError_t launch_dns_scores(const LaunchArgs& a, const double* ll, double* scores, int b0, int nb, bool count);
-// J_b = Γ₀ + Σ_{ℓ ≤ lags} (1 − ℓ/(lags + 1))(Γ_ℓ + Γ_ℓ') from the scores of nb candidates (T_use, grad: theirs), 20 × 20 × nb;
-// NaN where the candidate's own gradient grad[:, b] is NaN; count (may be null): raised by the candidates with a NaN J
-hipError_t launch_opg(const double* scores, int T, int nb, const int* T_use, int lags, const double* grad, double* J,
-                      unsigned int* count, hipStream_t s);
+// J_b = Γ₀ + Σ_{ℓ ≤ lags} (1 − ℓ/(lags + 1))(Γ_ℓ + Γ_ℓ') from the scores of nb candidates (T_use, grad: theirs), P × P × nb
+// with P = 20 (DNS) or 31 (TVλ); NaN where the candidate's own gradient grad[:, b] is NaN; count (may be null): raised
+// by the candidates with a NaN J
+hipError_t launch_opg(int P, const double* scores, int T, int nb, const int* T_use, int lags, const double* grad,
+                      double* J, unsigned int* count, hipStream_t s);
 // the 4P points θ ± h e_i, θ ± 2h e_i of nb candidates (pts: P × 4P nb; pts_T_use: 4P nb, untouched when T_use is
 // null) and the realised steps (2P nb); then H = ½(D + D') from their gradients, NaN where one of them or the candidate's
 // own gradient grad[:, b] is not finite (such candidates raise *count)
@@ -118,6 +119,11 @@ hipError_t launch_tvl_smooth(const LaunchArgs& a, const double* ll, double* beta
 // ll[b] is not finite or the recursion's own value or tangents are not usable (those counted in a.flags[5]).
 int tvl_grad_max_n();
 hipError_t launch_tvl_grad(const LaunchArgs& a, const double* ll, double* grad_out);
+// TVλ score series (yfm_tvl_score.hip), enqueued like launch_tvl_grad after the loglik launch of all a.B candidates:
+// S[d, k, b] = ∂ℓ_k/∂θ_d of candidates b0 … b0 + nb − 1 into scores (31 × (T − 1) × nb column-major, starting at
+// candidate b0), exact zeros outside a window's accumulated columns, NaN in all of a candidate that launch_tvl_grad
+// gives a NaN gradient (those with a finite ll[b] counted in a.flags[5])
+hipError_t launch_tvl_scores(const LaunchArgs& a, const double* ll, double* scores, int b0, int nb);
 // TVλ EKF kernel (yfm_tvl.hip): lanes per filter for a batch, largest N, launcher.  `share`: launches of this
 // size the caller runs concurrently on the device (the estimation driver's chain groups; 1 otherwise)
 int tvl_lanes_for(int B, int N, int share = 1);

@@ -7,16 +7,17 @@
 // there — S[d, k, b] = ∂ℓ_k/∂θ_d, grad::score_value — instead of only summing it.  The columns outside a candidate's
 // accumulated range 1 … nobs − 2 are written as exact zeros by the same lanes, so the array needs no memset.
 //
-// opg_kernel: J_b = Γ₀ + Σ_ℓ w_ℓ (Γ_ℓ + Γ_ℓ'), Γ_ℓ = Σ_k s_k s_{k−ℓ}', one wave per candidate on
-// v_mfma_f64_16x16x4_f64.  P = 20 is padded to 32: the tiles (0,0), (0,1), (1,1) are accumulated and the upper triangle
+// opg_kernel (DNS, P = 20) and opg31_kernel (TVλ, P = 31; its scores come from yfm_tvl_score.hip), one body opg_body<P>:
+// J_b = Γ₀ + Σ_ℓ w_ℓ (Γ_ℓ + Γ_ℓ'), Γ_ℓ = Σ_k s_k s_{k−ℓ}', one wave per candidate on
+// v_mfma_f64_16x16x4_f64.  P is padded to 32: the tiles (0,0), (0,1), (1,1) are accumulated and the upper triangle
 // is mirrored on the way out.  Operand layout (yfm_fixedz_mfma.hpp): A[i][k] in lane 16k + i, B[k][j] in lane 16k + j,
 // D[(l >> 4) + 4q][l & 15] in element q of lane l.  A k-step is four time steps; the A fragment of tile r is S[16r +
 // (l & 15), 4kk + (l >> 4)], and the B fragment of tile c has the same form, so at lag 0 the fragments serve both sides.
 // At lag ℓ the shifted fragments S[·, 4kk + (l >> 4) − ℓ] are scaled by the Bartlett weight and enter once as B (Γ_ℓ)
-// and once as A (Γ_ℓ').  Rows ≥ 20 and columns outside 0 … n − 1 are masked to zero.
+// and once as A (Γ_ℓ').  Rows ≥ P and columns outside 0 … n − 1 are masked to zero.
 //
 // Hessian: fourth-order central differences of the exact gradient.  hessian_points_kernel writes the 4P perturbed θ of
-// every candidate and the realised steps; the loglik launch and launch_dns_grad evaluate them (yfm_capi.hip);
+// every candidate and the realised steps; the loglik launch and the kind's gradient kernel evaluate them (yfm_capi.hip);
 // hessian_assemble_kernel forms D and ½(D + D'), NaN where any perturbed gradient or the candidate's own is unavailable.
 #include <algorithm>
 
@@ -24,6 +25,7 @@
 #include "yfm_grad.hpp"
 #include "yfm_grad_map.hpp"
 #include "yfm_internal.hpp"
+#include "yfm_tvl_grad.hpp"
 
 namespace yfm {
 
@@ -154,11 +156,11 @@ __global__ void score_unavailable_kernel(const int* __restrict__ defer_list, con
 
 namespace {
 
-constexpr int kOpgP = grad::kNP;  // 20 rows, padded to two 16-row tiles
-constexpr int kOpgWaves = 4;      // candidates (waves) per block
+constexpr int kOpgWaves = 4;  // candidates (waves) per block
 
 // the fragment of row tile r at k-step kk, shifted back by `lag` columns: S[16r + (lane & 15), 4kk + (lane >> 4) − lag],
 // zero for a padding row and outside columns 0 … n − 1
+template <int kOpgP>
 __device__ __forceinline__ double opg_frag(const double* __restrict__ S, int n, int r, int kk, int lag, int lane) {
   const int row = 16 * r + (lane & 15);
   const int col = 4 * kk + (lane >> 4) - lag;
@@ -166,15 +168,15 @@ __device__ __forceinline__ double opg_frag(const double* __restrict__ S, int n, 
   return ok ? S[(size_t)col * kOpgP + row] : 0.0;
 }
 
-}  // namespace
-
-// scores: 20 × ncol × B; grad: 20 × B, the candidates' own gradients; J: 20 × 20 × B.  One wave per candidate.  A
-// candidate without a gradient (NaN there) gets NaN in all of J, whatever its window; `count` (may be null) is raised
-// by the candidates with a NaN J.
-__global__ __launch_bounds__(64 * kOpgWaves) void opg_kernel(const double* __restrict__ scores, int ncol, int T, int B,
-                                                             const int* __restrict__ T_use, int lags,
-                                                             const double* __restrict__ grad, double* __restrict__ J,
-                                                             unsigned int* __restrict__ count) {
+// The body of both OPG kernels, 16 < kOpgP ≤ 32 rows padded to two 16-row tiles.  scores: kOpgP × ncol × B; grad:
+// kOpgP × B, the candidates' own gradients; J: kOpgP × kOpgP × B.  One wave per candidate.  A candidate without a
+// gradient (NaN there) gets NaN in all of J, whatever its window; `count` (may be null) is raised by the candidates
+// with a NaN J.
+template <int kOpgP>
+__device__ __forceinline__ void opg_body(const double* __restrict__ scores, int ncol, int T, int B,
+                                         const int* __restrict__ T_use, int lags, const double* __restrict__ grad,
+                                         double* __restrict__ J, unsigned int* __restrict__ count) {
+  static_assert(kOpgP > 16 && kOpgP <= 32, "two row tiles");
   const int lane = threadIdx.x & 63;
   const int b = blockIdx.x * kOpgWaves + (threadIdx.x >> 6);
   if (b >= B) return;  // the whole wave
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(64 * kOpgWaves) void opg_kernel(const double* __res
   const int nk = (n + 3) / 4;
   yfm_score_double4 a00 = {0.0, 0.0, 0.0, 0.0}, a01 = a00, a11 = a00;
   for (int kk = 0; kk < nk; ++kk) {
-    const double f0 = opg_frag(S, n, 0, kk, 0, lane), f1 = opg_frag(S, n, 1, kk, 0, lane);
+    const double f0 = opg_frag<kOpgP>(S, n, 0, kk, 0, lane), f1 = opg_frag<kOpgP>(S, n, 1, kk, 0, lane);
     a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, f0, a00, 0, 0, 0);
     a01 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, f1, a01, 0, 0, 0);
     a11 = __builtin_amdgcn_mfma_f64_16x16x4f64(f1, f1, a11, 0, 0, 0);
@@ -194,8 +196,8 @@ __global__ __launch_bounds__(64 * kOpgWaves) void opg_kernel(const double* __res
   for (int lag = 1; lag <= lmax; ++lag) {
     const double w = 1.0 - (double)lag / ((double)lags + 1.0);
     for (int kk = lag / 4; kk < nk; ++kk) {
-      const double f0 = opg_frag(S, n, 0, kk, 0, lane), f1 = opg_frag(S, n, 1, kk, 0, lane);
-      const double g0 = w * opg_frag(S, n, 0, kk, lag, lane), g1 = w * opg_frag(S, n, 1, kk, lag, lane);
+      const double f0 = opg_frag<kOpgP>(S, n, 0, kk, 0, lane), f1 = opg_frag<kOpgP>(S, n, 1, kk, 0, lane);
+      const double g0 = w * opg_frag<kOpgP>(S, n, 0, kk, lag, lane), g1 = w * opg_frag<kOpgP>(S, n, 1, kk, lag, lane);
       a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, g0, a00, 0, 0, 0);  // w Γ_ℓ
       a00 = __builtin_amdgcn_mfma_f64_16x16x4f64(g0, f0, a00, 0, 0, 0);  // w Γ_ℓ'
       a01 = __builtin_amdgcn_mfma_f64_16x16x4f64(f0, g1, a01, 0, 0, 0);
@@ -220,15 +222,33 @@ __global__ __launch_bounds__(64 * kOpgWaves) void opg_kernel(const double* __res
       Jb[(size_t)cj * kOpgP + ri] = a00[q];
       Jb[(size_t)ri * kOpgP + cj] = a00[q];
     }
-    if (cj < kOpgP - 16) {  // tile (0,1): rows 0 … 15, columns 16 … 19
+    if (cj < kOpgP - 16) {  // tile (0,1): rows 0 … 15, columns 16 … kOpgP − 1
       Jb[(size_t)(16 + cj) * kOpgP + ri] = a01[q];
       Jb[(size_t)ri * kOpgP + 16 + cj] = a01[q];
     }
-    if (ri <= cj && cj < kOpgP - 16) {  // tile (1,1): rows and columns 16 … 19
+    if (ri <= cj && cj < kOpgP - 16) {  // tile (1,1): rows and columns 16 … kOpgP − 1
       Jb[(size_t)(16 + cj) * kOpgP + 16 + ri] = a11[q];
       Jb[(size_t)(16 + ri) * kOpgP + 16 + cj] = a11[q];
     }
   }
+}
+
+}  // namespace
+
+// DNS: 20 rows (rows 20 … 31 of the second tile are padding)
+__global__ __launch_bounds__(64 * kOpgWaves) void opg_kernel(const double* __restrict__ scores, int ncol, int T, int B,
+                                                             const int* __restrict__ T_use, int lags,
+                                                             const double* __restrict__ grad, double* __restrict__ J,
+                                                             unsigned int* __restrict__ count) {
+  opg_body<grad::kNP>(scores, ncol, T, B, T_use, lags, grad, J, count);
+}
+
+// TVλ: 31 rows (row 31 is padding); tile (1,1) holds 15 live rows
+__global__ __launch_bounds__(64 * kOpgWaves) void opg31_kernel(const double* __restrict__ scores, int ncol, int T, int B,
+                                                               const int* __restrict__ T_use, int lags,
+                                                               const double* __restrict__ grad, double* __restrict__ J,
+                                                               unsigned int* __restrict__ count) {
+  opg_body<tvlgrad::kNP>(scores, ncol, T, B, T_use, lags, grad, J, count);
 }
 
 // The perturbed points of candidates 0 … B − 1: point 4(P b + i) + s is θ_b moved along e_i by +h, −h, +2h, −2h
@@ -308,10 +328,11 @@ hipError_t launch_dns_scores(const LaunchArgs& a, const double* ll, double* scor
   return hipGetLastError();
 }
 
-hipError_t launch_opg(const double* scores, int T, int nb, const int* T_use, int lags, const double* grad, double* J,
-                      unsigned int* count, hipStream_t s) {
+hipError_t launch_opg(int P, const double* scores, int T, int nb, const int* T_use, int lags, const double* grad,
+                      double* J, unsigned int* count, hipStream_t s) {
   if (nb <= 0) return hipSuccess;
-  hipLaunchKernelGGL(opg_kernel, dim3((nb + kOpgWaves - 1) / kOpgWaves), dim3(64 * kOpgWaves), 0, s, scores, T - 1, T,
+  if (P != grad::kNP && P != tvlgrad::kNP) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(P == grad::kNP ? opg_kernel : opg31_kernel, dim3((nb + kOpgWaves - 1) / kOpgWaves), dim3(64 * kOpgWaves), 0, s, scores, T - 1, T,
                      nb, T_use, lags, grad, J, count);
   return hipGetLastError();
 }

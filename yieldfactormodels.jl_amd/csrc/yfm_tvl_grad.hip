@@ -20,47 +20,11 @@
 // precision); a candidate whose loglik is −Inf or NaN gets NaN gradients here.  A candidate whose loglik is finite
 // but whose FP64 recursion here is not usable (its own value not finite, a negative determinant, a non-finite
 // tangent) gets NaN gradients too and is counted in flags[5] (yfm_last_batch_grad_unavailable).
-#include <type_traits>
-
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
-#include "yfm_tvl_grad.hpp"
+#include "yfm_tvl_grad_map.hpp"
 
 namespace yfm {
-
-namespace {
-
-constexpr int kTvlGradBlock = 256;
-
-// the seed kinds of slot S when a candidate has L lanes (tvlgrad::slot_direction: which directions it holds)
-template <int L, int S>
-constexpr int tvl_slot_mask() {
-  namespace g = tvlgrad;
-  if (L >= 32) return g::kSeedAll;
-  if (S >= g::slots_before_phi(L)) return g::kSeedF;
-  constexpr int lo = S * L, hi = S * L + L - 1;
-  return (lo <= 0 ? g::kSeedS : 0) | ((lo < g::kOffD && hi >= g::kOffU) ? g::kSeedQ : 0) |
-         ((lo < g::kOffF && hi >= g::kOffD) ? g::kSeedD : 0);
-}
-// f(integral_constant<int, S>) for S = 0 … ND − 1
-template <int ND, int S = 0, class F>
-__device__ __forceinline__ void tvl_for_slots(F&& f) {
-  f(std::integral_constant<int, S>{});
-  if constexpr (S + 1 < ND) tvl_for_slots<ND, S + 1>(f);
-}
-
-// This lane's index in its group, formed afresh (the wave's lane count through an operand the compiler cannot fold):
-// the step loop and the epilogue ask for it again, so the index is not carried in a register across the loop,
-// where it was the one value that went to scratch.
-template <int L>
-__device__ __forceinline__ int fresh_group_lane() {
-  static_assert(64 % L == 0 && kTvlGradBlock % 64 == 0, "a group lies inside one wave");
-  unsigned z = 0u;
-  asm volatile("" : "+v"(z));
-  return (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, z)) & (unsigned)(L - 1));
-}
-
-}  // namespace
 
 // L lanes per candidate, ND directions per lane.  Y: the caller's raw N×T panel (column-major); prep: the prepared
 // panel, read for its per-column NaN flags only (offset np + 2, stride ldp).  Dynamic LDS: N × (m, 1/m), then per

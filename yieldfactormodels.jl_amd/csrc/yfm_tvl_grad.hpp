@@ -854,5 +854,13 @@ YFM_GHD double grad_value(const Model& m, const Tangent& t, int N, int nobs) {
   return -0.5 * gfma((double)nterms, dconst, t.acc);
 }
 
+// ∂ℓ_k/∂θ_c[d] of the step just taken, ℓ_k the term get_loss adds after column k: −½(dconst + last), with
+// grad_value's dconst and the step's own (at a NaN column: the stale) tangent term; 0 for a step that is not
+// accumulated (column 0).  Summed over a window's steps these are grad_value, up to the order of the sum.
+YFM_GHD double score_value(const Model& m, const Tangent& t, int N, bool acc) {
+  const double dconst = (seed_fs(t) * (double)(N - kM)) * m.rsig2;
+  return acc ? -0.5 * (dconst + t.last) : 0.0;
+}
+
 }  // namespace tvlgrad
 }  // namespace yfm

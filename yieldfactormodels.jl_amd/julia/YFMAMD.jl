@@ -139,6 +139,43 @@ function tvl_smooth(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = C
     βs, V, C
 end
 
+"TVλ loglik and its score series — an extension, the reference's estimate! returns no covariance: (ll[B],
+S[31, T-1, B]) with S[d, k, b] = ∂ℓ_k/∂Θ[d, b] in `space`, ℓ_k the term get_loss adds after column k (0-based slot k + 1
+here): exact zeros outside a window's accumulated columns, sum(S, dims = 2) the gradient of tvl_loglik_grad_batch up to
+the order of the sum.  NaN in all of a candidate without a gradient (yfm.h; counted by
+yfm_last_batch_grad_unavailable).  TVλ only."
+function tvl_loglik_scores(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,
+                           T_use::Union{Nothing,Vector{Cint}} = nothing)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    ll, S = Vector{Float64}(undef, B), Array{Float64}(undef, P, max(size(data, 2) - 1, 0), B)
+    GC.@preserve Θ ll S T_use check(@ccall LIB.yfm_tvl_loglik_scores_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, ll::Ptr{Cdouble},
+        S::Ptr{Cdouble})::Cint)
+    ll, S
+end
+
+"TVλ information matrices — an extension: (ll[B], grad[31, B], H[31, 31, B], J[31, 31, B]) with ll and grad those of
+tvl_loglik_grad_batch bit for bit, H = ∂²ll/∂Θ∂Θ' by fourth-order central differences of the exact gradient (step ≤ 0: the
+library's default) and J = Γ₀ + Σ_ℓ (1 − ℓ/(lags+1))(Γ_ℓ + Γ_ℓ') of the score series.  hessian = false or opg = false skips
+that half (returned as nothing; not both).  NaN matrices for a candidate without a gradient, a NaN H where one of its
+124 perturbed points has none (yfm.h; yfm_last_batch_grad_unavailable counts the NaN H).  TVλ only."
+function tvl_loglik_info(model, data::Matrix{Float64}, Θ::Matrix{Float64}; space = UNCONSTRAINED,
+                         T_use::Union{Nothing,Vector{Cint}} = nothing, lags::Integer = 0, step::Real = 0.0,
+                         hessian::Bool = true, opg::Bool = true)
+    c = ensure_panel!(model, data)
+    P, B = size(Θ)
+    ll, grad = Vector{Float64}(undef, B), Matrix{Float64}(undef, P, B)
+    H = hessian ? Array{Float64}(undef, P, P, B) : nothing
+    J = opg ? Array{Float64}(undef, P, P, B) : nothing
+    GC.@preserve Θ ll grad H J T_use check(@ccall LIB.yfm_tvl_loglik_info_batch(c.ptr::Ptr{Cvoid}, kind(model)::Cint,
+        space::Cint, Θ::Ptr{Cdouble}, Cint(P)::Cint, Cint(B)::Cint, tuse_ptr(T_use)::Ptr{Cint}, Cint(lags)::Cint,
+        Float64(step)::Cdouble, ll::Ptr{Cdouble}, grad::Ptr{Cdouble},
+        (hessian ? pointer(H) : Ptr{Cdouble}(C_NULL))::Ptr{Cdouble},
+        (opg ? pointer(J) : Ptr{Cdouble}(C_NULL))::Ptr{Cdouble})::Cint)
+    ll, grad, H, J
+end
+
 "TVλ loglik and its gradient: (ll[B], grad[31, B]), grad[:, b] = ∂(+loglik)/∂Θ[:, b] in `space` — estimate!'s
 ForwardDiff gradient (optimization.jl:367, :10-23) of the EKF of filter.jl:12-80.  ll is bitwise loglik_batch's under the
 context's precision; the gradient is the FP64 tangent recursion.  NaN gradient columns where ll is -Inf / NaN or the

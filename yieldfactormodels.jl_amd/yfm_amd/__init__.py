@@ -21,6 +21,7 @@ from .driver import load_initial_parameters_, run, run_neural_estimation_
 from . import lbfgs
 from . import inference
 from .inference import covariance, standard_errors_, standard_errors_batch
+from .inference import tvl_standard_errors_, tvl_standard_errors_batch
 from . import smoothing
 from .smoothing import em_moments, smooth_, smooth_batch, smoothed_yields
 from .smoothing import tvl_smooth_, tvl_smooth_batch, tvl_smoothed_yields
@@ -38,6 +39,7 @@ __all__ = [
     "compute_neural_loss_grad_block", "estimate_neural_steps_", "estimate_neural_steps_batch", "run_neural_estimation_",
     "compute_neural_loss_fullgrad_batch", "estimate_neural_lbfgs_batch", "estimate_neural_",
     "inference", "covariance", "standard_errors_batch", "standard_errors_",
+    "tvl_standard_errors_batch", "tvl_standard_errors_",
     "smoothing", "smooth_batch", "smooth_", "smoothed_yields", "em_moments",
     "tvl_smooth_batch", "tvl_smooth_", "tvl_smoothed_yields",
 ]

@@ -48,16 +48,18 @@ _DEVICE = [_V, ctypes.c_int, ctypes.c_int, _V, ctypes.c_int, ctypes.c_int, _V]
 _BATCH = {
     "yfm_loglik_batch": 1,
     "yfm_loglik_grad_batch": 2, "yfm_tvl_loglik_grad_batch": 2, "yfm_loglik_scores_batch": 2,
+    "yfm_tvl_loglik_scores_batch": 2,
     "yfm_lambda_loss_grad_batch": 2, "yfm_lambda_loss_fullgrad_batch": 2,
     "yfm_neural_loss_grad_batch": 2, "yfm_neural_loss_fullgrad_batch": 2,
     "yfm_smooth_batch": 3, "yfm_tvl_smooth_batch": 3,
 }
+_INFO = [ctypes.c_int, ctypes.c_double, _D, _D, _D, _D]  # lags, step, loglik, grad, hess, opg
 _HOST_ONLY = {
     "yfm_filter_states": [_D, _D, _D],
     "yfm_predict": [ctypes.c_int, _D, _D, _D, _D, _D],
     "yfm_forecast": [ctypes.c_int, _D],
     "yfm_loss_array": [ctypes.c_int, _D],
-    "yfm_loglik_info_batch": [ctypes.c_int, ctypes.c_double, _D, _D, _D, _D],
+    "yfm_loglik_info_batch": _INFO, "yfm_tvl_loglik_info_batch": _INFO,
     "yfm_estimate": [ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_double, _D, _D, _D, _D, _I, _LL],
 }
 for _name, _n in _BATCH.items():
@@ -70,6 +72,8 @@ ABI_VERSION = 5
 
 # the default Hessian step (include/yfm.h: YFM_INFO_DEFAULT_STEP)
 INFO_DEFAULT_STEP = 1e-4
+# the TVλ calls' (include/yfm.h: YFM_TVL_INFO_DEFAULT_STEP)
+TVL_INFO_DEFAULT_STEP = 1e-5
 
 # precision modes (include/yfm.h: enum yfm_precision)
 PREC_CERTIFIED, PREC_FP64 = 0, 1

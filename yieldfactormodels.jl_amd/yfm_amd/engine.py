@@ -162,13 +162,7 @@ class Engine:
         term get_loss adds after column k — exact zeros outside a window's accumulated columns 1 … T_use − 2, NaN for
         a candidate without a gradient (include/yfm.h yfm_loglik_scores_batch; DNS with N ≤ 64)."""
         self._dns_only(kind, "loglik_scores")
-        Th = self._batch(theta, kind)
-        P, B = Th.shape
-        ll = np.empty(B, dtype=np.float64)
-        S = np.empty((P, max(self.T - 1, 0), B), dtype=np.float64, order="F")
-        _lib.check(self.lib.yfm_loglik_scores_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                    _lib.iptr(self._tuse(T_use, B)), _lib.dptr(ll), _lib.dptr(S)))
-        return ll, S
+        return self._scores_call("yfm_loglik_scores_batch", kind, theta, space, T_use)
 
     def loglik_scores_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_scores: int, space: int = 0,
                              d_T_use: int | None = None, stream: int | None = None) -> None:
@@ -186,8 +180,45 @@ class Engine:
         half (its entry is None).  NaN matrices for a candidate without a gradient, and a NaN Hessian where one of
         its perturbed points has none (include/yfm.h yfm_loglik_info_batch; DNS with N ≤ 64)."""
         self._dns_only(kind, "loglik_info")
+        return self._info_call("yfm_loglik_info_batch", "loglik_info", "loglik_grad", kind, theta, space, T_use, lags,
+                               step, hessian, opg)
+
+    def tvl_loglik_scores(self, kind: int, theta, space: int = 0, T_use=None):
+        """(ll[B], S[31, T−1, B]) of the TVλ model: :meth:`loglik_scores` for the extended Kalman filter
+        (include/yfm.h yfm_tvl_loglik_scores_batch) — NaN in all of a candidate that :meth:`tvl_loglik_grad` gives a
+        NaN gradient."""
+        self._tvl_only(kind, "tvl_loglik_scores")
+        return self._scores_call("yfm_tvl_loglik_scores_batch", kind, theta, space, T_use)
+
+    def tvl_loglik_scores_device(self, kind: int, d_theta: int, P: int, B: int, d_out: int, d_scores: int,
+                                 space: int = 0, d_T_use: int | None = None, stream: int | None = None) -> None:
+        """Device-pointer variant of :meth:`tvl_loglik_scores` (raw addresses; d_scores: 31×(T−1)×B column-major);
+        asynchronous on ``stream``."""
+        self._tvl_only(kind, "tvl_loglik_scores_device")
+        self._grad_call_device("yfm_tvl_loglik_scores_batch_device", kind, d_theta, P, B, d_out, d_scores, space,
+                               d_T_use, stream)
+
+    def tvl_loglik_info(self, kind: int, theta, space: int = 0, T_use=None, lags: int = 0, step: float | None = None,
+                        hessian: bool = True, opg: bool = True) -> dict:
+        """:meth:`loglik_info` for the TVλ model (include/yfm.h yfm_tvl_loglik_info_batch): ll[B] and grad[31, B]
+        those of :meth:`tvl_loglik_grad`, bit for bit, hess[31, 31, B] from the 124 perturbed gradients per candidate
+        and opg[31, 31, B] from the score series."""
+        self._tvl_only(kind, "tvl_loglik_info")
+        return self._info_call("yfm_tvl_loglik_info_batch", "tvl_loglik_info", "tvl_loglik_grad", kind, theta, space,
+                               T_use, lags, step, hessian, opg)
+
+    def _scores_call(self, fn: str, kind, theta, space, T_use):
+        Th = self._batch(theta, kind)
+        P, B = Th.shape
+        ll = np.empty(B, dtype=np.float64)
+        S = np.empty((P, max(self.T - 1, 0), B), dtype=np.float64, order="F")
+        _lib.check(getattr(self.lib, fn)(self.ctx, kind, space, _lib.dptr(Th), P, B, _lib.iptr(self._tuse(T_use, B)),
+                                         _lib.dptr(ll), _lib.dptr(S)))
+        return ll, S
+
+    def _info_call(self, fn: str, what: str, grad: str, kind, theta, space, T_use, lags, step, hessian, opg) -> dict:
         if not (hessian or opg):
-            raise ValueError("loglik_info: hessian and opg are both off (loglik_grad gives the loglik and gradient)")
+            raise ValueError(f"{what}: hessian and opg are both off ({grad} gives the loglik and gradient)")
         if lags < 0:
             raise ValueError(f"lags = {lags} < 0")
         Th = self._batch(theta, kind)
@@ -196,10 +227,10 @@ class Engine:
         grad = np.empty((P, B), dtype=np.float64, order="F")
         H = np.empty((P, P, B), dtype=np.float64, order="F") if hessian else None
         J = np.empty((P, P, B), dtype=np.float64, order="F") if opg else None
-        _lib.check(self.lib.yfm_loglik_info_batch(self.ctx, kind, space, _lib.dptr(Th), P, B,
-                                                  _lib.iptr(self._tuse(T_use, B)), int(lags),
-                                                  0.0 if step is None else float(step), _lib.dptr(ll), _lib.dptr(grad),
-                                                  _lib.dptr(H) if hessian else None, _lib.dptr(J) if opg else None))
+        _lib.check(getattr(self.lib, fn)(self.ctx, kind, space, _lib.dptr(Th), P, B, _lib.iptr(self._tuse(T_use, B)),
+                                         int(lags), 0.0 if step is None else float(step), _lib.dptr(ll),
+                                         _lib.dptr(grad), _lib.dptr(H) if hessian else None,
+                                         _lib.dptr(J) if opg else None))
         return dict(ll=ll, grad=grad, hess=H, opg=J)
 
     @staticmethod
@@ -207,6 +238,13 @@ class Engine:
         if kind != KIND_DNS:
             raise NotImplementedError(f"{what} is built for the DNS model (kind {KIND_DNS}) only, not kind {kind}: the "
                                       "other kinds have no score series, information matrix or Hessian")
+
+    @staticmethod
+    def _tvl_only(kind, what):
+        if kind != KIND_TVL:
+            gap = ("the DNS model has loglik_scores and loglik_info" if kind == KIND_DNS
+                   else "only DNS and TVλ have score series, information matrices and Hessians")
+            raise NotImplementedError(f"{what} is built for the TVλ model (kind {KIND_TVL}) only, not kind {kind}: {gap}")
 
     def tvl_loglik_grad(self, kind: int, theta, space: int = 0, T_use=None):
         """(ll[B], grad[31, B]) of the TVλ model: the logliks of :meth:`loglik`, bit for bit under the context's

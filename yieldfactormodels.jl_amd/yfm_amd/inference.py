@@ -1,8 +1,9 @@
-"""Standard errors of a maximum-likelihood estimate of the DNS model.
+"""Standard errors of a maximum-likelihood estimate of the DNS and TVλ models.
 
 An extension: the reference's ``estimate!`` (optimization.jl) returns the optimum and its loss and no covariance.
 The device gives the Hessian H of the log-likelihood and the OPG / HAC matrix J of its score series
-(:meth:`yfm_amd.engine.Engine.loglik_info`, include/yfm.h yfm_loglik_info_batch); this module turns them into
+(:meth:`yfm_amd.engine.Engine.loglik_info` and ``tvl_loglik_info``, include/yfm.h yfm_loglik_info_batch and
+yfm_tvl_loglik_info_batch); this module turns them into
 covariance matrices and standard errors with NumPy, in the unconstrained space estimation runs in and, by the delta
 method, in the constrained space of ``set_params!``.
 """
@@ -107,6 +108,25 @@ def _se(cov):
         return np.sqrt(np.einsum("iib->ib", cov))
 
 
+def _standard_errors(info, what, kind, refusal, model, data, theta_c, T_use, cov, lags, step) -> dict:
+    from . import models as _m
+    if cov not in COV_KINDS:
+        raise ValueError(f"cov must be one of {COV_KINDS}, got {cov!r}")
+    if model.kind != kind:
+        raise NotImplementedError(f"{what} {refusal(model.kind)}")
+    Th = np.asarray(theta_c, dtype=np.float64)
+    if Th.ndim == 1:
+        Th = Th[:, None]
+    X = np.asfortranarray(_p.untransform_params(model.kind, Th))
+    eng = _m._engine(model, data)
+    r = getattr(eng, info)(model.kind, X, space=_p.SPACE_UNCONSTRAINED, T_use=T_use, lags=lags, step=step,
+                           hessian=cov != "opg", opg=cov != "hessian")
+    cov_u, pd = covariance(r["hess"], r["opg"], cov)
+    cov_c = delta_method(cov_u, transform_jacobian(model.kind, X))
+    return dict(cov_u=cov_u, se_u=_se(cov_u), cov_c=cov_c, se_c=_se(cov_c), ll=r["ll"], grad=r["grad"], pd=pd,
+                unavailable=eng.last_grad_unavailable())
+
+
 def standard_errors_batch(model, data, theta_c, T_use=None, cov: str = "sandwich", lags: int = 0, step=None) -> dict:
     """Standard errors of the DNS estimates θ_c (P×B constrained, as ``estimate_`` returns them; column b on the window
     ``data[:, :T_use[b]]``).  θ_c is untransformed and the log-likelihood's Hessian and OPG matrix (``lags`` Bartlett
@@ -114,28 +134,38 @@ def standard_errors_batch(model, data, theta_c, T_use=None, cov: str = "sandwich
     method with the diagonal Jacobian of ``transform_params``, ll and grad (of +loglik, at θ_u), pd (False where the
     matrix was not positive definite: NaN covariances, no exception) and ``unavailable``, the candidates the device
     gave no matrices for.  ``cov``: "hessian", "opg" or "sandwich"."""
-    from . import models as _m
-    if cov not in COV_KINDS:
-        raise ValueError(f"cov must be one of {COV_KINDS}, got {cov!r}")
-    if model.kind != _p.KIND_DNS:
-        raise NotImplementedError(f"standard errors are built for the DNS model only (model kind {model.kind}): the "
-                                  "other kinds have no score series, information matrix or Hessian")
-    Th = np.asarray(theta_c, dtype=np.float64)
-    if Th.ndim == 1:
-        Th = Th[:, None]
-    X = np.asfortranarray(_p.untransform_params(model.kind, Th))
-    eng = _m._engine(model, data)
-    r = eng.loglik_info(model.kind, X, space=_p.SPACE_UNCONSTRAINED, T_use=T_use, lags=lags, step=step,
-                        hessian=cov != "opg", opg=cov != "hessian")
-    cov_u, pd = covariance(r["hess"], r["opg"], cov)
-    cov_c = delta_method(cov_u, transform_jacobian(model.kind, X))
-    return dict(cov_u=cov_u, se_u=_se(cov_u), cov_c=cov_c, se_c=_se(cov_c), ll=r["ll"], grad=r["grad"], pd=pd,
-                unavailable=eng.last_grad_unavailable())
+    def refusal(kind):
+        if kind == _p.KIND_TVL:
+            return (f"are built for the DNS model only (model kind {kind}): the TVλ model's are "
+                    "tvl_standard_errors_batch")
+        return (f"are built for the DNS model only (model kind {kind}): the "
+                "other kinds have no score series, information matrix or Hessian")
+    return _standard_errors("loglik_info", "standard errors", _p.KIND_DNS, refusal, model, data, theta_c, T_use, cov,
+                            lags, step)
+
+
+def tvl_standard_errors_batch(model, data, theta_c, T_use=None, cov: str = "sandwich", lags: int = 0,
+                              step=None) -> dict:
+    """:func:`standard_errors_batch` for the TVλ model (31×B constrained estimates): the same dict, from
+    :meth:`yfm_amd.engine.Engine.tvl_loglik_info` and the TVλ transform's Jacobian."""
+    def refusal(kind):
+        return (f"are built for the TVλ model only (model kind {kind}): the DNS model's are standard_errors_batch, and "
+                "the other kinds have no score series, information matrix or Hessian")
+    return _standard_errors("tvl_loglik_info", "TVλ standard errors", _p.KIND_TVL, refusal, model, data, theta_c, T_use,
+                            cov, lags, step)
 
 
 def standard_errors_(model, data, params, **opts) -> dict:
     """:func:`standard_errors_batch` for one constrained parameter vector: the same dict without the batch axis."""
     r = standard_errors_batch(model, data, np.asarray(params, dtype=np.float64).reshape(-1, 1), **opts)
+    out = {k: (v[..., 0] if isinstance(v, np.ndarray) else v) for k, v in r.items()}
+    out["pd"] = bool(r["pd"][0])
+    return out
+
+
+def tvl_standard_errors_(model, data, params, **opts) -> dict:
+    """:func:`tvl_standard_errors_batch` for one constrained parameter vector: the same dict without the batch axis."""
+    r = tvl_standard_errors_batch(model, data, np.asarray(params, dtype=np.float64).reshape(-1, 1), **opts)
     out = {k: (v[..., 0] if isinstance(v, np.ndarray) else v) for k, v in r.items()}
     out["pd"] = bool(r["pd"][0])
     return out

@@ -1,0 +1,27 @@
+"""CPU test of the LDS layouts of the two TVλ loglik kernels (csrc/yfm_tvl_layout.hpp: TvlSmem, TvlDdSmem), which
+the kernels carve their shared memory from and whose bytes() their launchers pass.  tests/tvl_layout_host_check.cpp, a
+stand-alone program built with -fsanitize=address,undefined, holds both structs to the pointer chains and the two
+byte-count formulas they replace: equal totals, equal offsets, 16-byte alignment of the double2 / dd regions wherever
+the former chain had it, disjoint regions.
+
+Cases: N ∈ {1, 3, 4, 7, 30, 33, 360, 2047}, the columns per chunk chunk_columns gives for each N, L ∈ {1 … 64} (FP64)
+and {4 … 64} (dd); and the dd launcher's 160 KiB refusal at the first N where it triggers (N = 2,758 at L = 4: beyond
+the N ≤ 2,048 the chunk rule admits, which the program also asserts).
+"""
+from __future__ import annotations
+
+import subprocess
+
+from conftest import ROOT
+
+
+def test_layout_structs_match_the_former_chains(tmp_path):
+    exe = tmp_path / "tvl_layout_host_check"
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
+                    "-fno-sanitize-recover=all", str(ROOT / "tests" / "tvl_layout_host_check.cpp"), "-o", str(exe)],
+                   check=True)
+    out = subprocess.run([str(exe)], capture_output=True, text=True)
+    print(out.stdout, out.stderr)
+    assert out.returncode == 0
+    assert "96 layouts checked, 0 failures" in out.stdout
+    assert "dd L=4: LDS refusal first at N=2758" in out.stdout

@@ -53,6 +53,7 @@ inline unsigned atomicAdd(unsigned* p, unsigned v) {
   return o;
 }
 int __builtin_amdgcn_mov_dpp(int, int, int, int, bool);
+int __builtin_amdgcn_ds_bpermute(int, int);
 int __double2loint(double);
 int __double2hiint(double);
 double __hiloint2double(int, int);

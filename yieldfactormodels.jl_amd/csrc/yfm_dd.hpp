@@ -17,6 +17,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "yfm_device.hpp"  // kLog2Pi
+
 // Floating-point contraction must stay off in every translation unit that includes this
 // header (a fused a·b + c inside TwoSum / TwoProd would break the error-free
 // transformations); the pragma below covers the rest of the including file.
@@ -451,6 +453,35 @@ __device__ __forceinline__ void group_sum12(const dd_acc (&in)[12], dd (&out)[12
     out[k] = b0 ? dd{rh, rl} : dd{g6h[k], g6l[k]};
     out[6 + k] = b0 ? dd{g6h[k], g6l[k]} : dd{rh, rl};
   }
+}
+
+// The epilogue of the capacitance-form dd filters (M states), by lane 0 of a live group: get_loss's value from the dd
+// sums of the accumulated terms (nobs columns: nobs − 2 terms), NaN (flags[0]) where initialize_filter threw, −Inf (flags[1]) on a DomainError or a value that is
+// not finite
+__device__ __forceinline__ void dd_finish_loglik(bool init_ok, int nobs, int N, int M, dd sig2, const dd_acc& sum_ld,
+                                                 const dd_acc& sum_q, bool neg, unsigned int* __restrict__ flags,
+                                                 double* __restrict__ out, int b) {
+  double ll;
+  if (!init_ok) {
+    ll = __builtin_nan("");  // the reference throws from initialize_filter
+    atomicAdd(&flags[0], 1u);
+  } else {
+    const int nterms = max(nobs - 2, 0);
+    if (nterms == 0) {
+      ll = 0.0;
+    } else {
+      // per term: (N − M)·log σ² + N·log 2π (+ log|det B̃_t| + q_t, summed above)
+      const dd lsig = dd_log(sig2);
+      dd tot = dd_mul_d(dd_add_d(dd_mul_d(lsig, (double)(N - M)), (double)N * kLog2Pi), (double)nterms);
+      tot = dd_add(tot, dd_add(sum_ld.value(), sum_q.value()));
+      ll = -0.5 * dd_to_double(tot);
+    }
+    if (neg || !isfinite(ll)) {  // DomainError / non-finite → -Inf (filter.jl:197-204)
+      ll = -__builtin_inf();
+      atomicAdd(&flags[1], 1u);
+    }
+  }
+  out[b] = ll;
 }
 
 }  // namespace yfm

@@ -495,6 +495,42 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// x of lane `src` of this wave (ds_bpermute: the LDS crossbar, no LDS memory and no wave barrier)
+__device__ __forceinline__ double lane_read_f64(int src, double x) {
+  const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
+  const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
+  return __hiloint2double(hi, lo);
+}
+
+// ---- raw-panel staging: chunk c holds the columns c·TC … c·TC + TC − 1 of the caller's N×T column-major matrix
+// (CHY = TC·N doubles, PRE per thread of a BLOCK; zeros past the panel) with each column's NaN flag from the prepared
+// panel (offset np + 2, stride ldp); chunk c in LDS, chunk c + 1 in registers.  Called from the kernels' lambdas.
+template <int PRE, int BLOCK>
+__device__ __forceinline__ void raw_chunk_load(const double* __restrict__ Y, const double* __restrict__ prep, int ldp,
+                                               int np, int T, int N, int TC, int CHY, int c, int tid,
+                                               double (&pre)[PRE], double& pre_nan) {
+  const size_t base = (size_t)c * CHY;
+  const size_t lim = (size_t)T * N;
+#pragma unroll
+  for (int r = 0; r < PRE; ++r) {
+    const int e = r * BLOCK + tid;
+    const size_t g = base + e;
+    pre[r] = (e < CHY && g < lim) ? Y[g] : 0.0;
+  }
+  const int tc = c * TC + tid;
+  pre_nan = (tid < TC && tc < T) ? prep[(size_t)tc * ldp + np + 2] : 0.0;
+}
+template <int PRE, int BLOCK>
+__device__ __forceinline__ void raw_chunk_store(double* s_y, double* s_nan, int TC, int CHY, int tid,
+                                                const double (&pre)[PRE], const double& pre_nan) {
+#pragma unroll
+  for (int r = 0; r < PRE; ++r) {
+    const int e = r * BLOCK + tid;
+    if (e < CHY) s_y[e] = pre[r];
+  }
+  if (tid < TC) s_nan[tid] = pre_nan;
+}
+
 // Sum over the aligned group of L lanes (DPP / permlane butterflies, no LDS); every lane of
 // the group receives the total.
 template <int L>

@@ -335,25 +335,9 @@ __global__ __launch_bounds__(kFdBlock) void fixedz_dd_loglik_kernel(
   double pre[kFdPre];
   double pre_nan = 0.0;
   auto load_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int q = 0; q < kFdPre; ++q) {
-      const int e = q * kFdBlock + tid;
-      const size_t gi = base + e;
-      pre[q] = (e < CHY && gi < lim) ? Y[gi] : 0.0;
-    }
-    const int tc = c * TC + tid;
-    pre_nan = (tid < TC && tc < T) ? prep[(size_t)tc * ldp + np + 2] : 0.0;
+    raw_chunk_load<kFdPre, kFdBlock>(Y, prep, ldp, np, T, N, TC, CHY, c, tid, pre, pre_nan);
   };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int q = 0; q < kFdPre; ++q) {
-      const int e = q * kFdBlock + tid;
-      if (e < CHY) s_y[e] = pre[q];
-    }
-    if (tid < TC) s_nan[tid] = pre_nan;
-  };
+  auto store_chunk = [&]() { raw_chunk_store<kFdPre, kFdBlock>(s_y, s_nan, TC, CHY, tid, pre, pre_nan); };
   if (nsteps > 0) {
     load_chunk(0);
     store_chunk();
@@ -471,27 +455,7 @@ __global__ __launch_bounds__(kFdBlock) void fixedz_dd_loglik_kernel(
 
   if (live && j == 0) {
   atomicAdd(&flags[3], 1u);  // n_deferred (yfm_last_batch_deferred)
-  double ll;
-  if (!init_ok) {
-    ll = __builtin_nan("");  // the reference throws from initialize_filter
-    atomicAdd(&flags[0], 1u);
-  } else {
-    const int nterms = max(nobs - 2, 0);
-    if (nterms == 0) {
-      ll = 0.0;
-    } else {
-      // per term: (N − M)·log σ² + N·log 2π (+ log|det B̃_t| + q_t, summed above)
-      const dd lsig = dd_log(sig2);
-      dd tot = dd_mul_d(dd_add_d(dd_mul_d(lsig, (double)(N - M)), (double)N * kLog2Pi), (double)nterms);
-      tot = dd_add(tot, dd_add(sum_ld.value(), sum_q.value()));
-      ll = -0.5 * dd_to_double(tot);
-    }
-    if (neg || !isfinite(ll)) {  // DomainError / non-finite → -Inf (filter.jl:197-204)
-      ll = -__builtin_inf();
-      atomicAdd(&flags[1], 1u);
-    }
-  }
-  out[b] = ll;
+  dd_finish_loglik(init_ok, nobs, N, M, sig2, sum_ld, sum_q, neg, flags, out, b);
   }
   __syncthreads();  // LDS (panel chunks, per-group parameters) reused by the next slot group
   }
@@ -505,15 +469,11 @@ hipError_t launch_fd_l(const LaunchArgs& a, double* rec, int TC) {
   const int grid = std::min((a.B + GPB - 1) / GPB, 256);
   const size_t shmem = sizeof(double) * ((size_t)TC + (size_t)TC * a.N + (size_t)GPB * FdRec<M>::Par);
   if (shmem > 64 * 1024) return hipErrorInvalidValue;
-  if (a.rec_beta) {
-    hipLaunchKernelGGL((fixedz_dd_loglik_kernel<L, M, LEAD, true>), dim3(grid), dim3(kFdBlock), shmem, a.stream, rec,
-                       a.defer_list, a.defer_count, a.theta, a.P, a.space, a.raw, a.panel, a.ldp, a.np, a.T, a.N, TC, a.mats,
-                       a.T_use, a.out, a.flags, a.rec_beta, a.rec_P, a.horizon, a.rec_len);
-  } else {
-    hipLaunchKernelGGL((fixedz_dd_loglik_kernel<L, M, LEAD, false>), dim3(grid), dim3(kFdBlock), shmem, a.stream, rec,
-                       a.defer_list, a.defer_count, a.theta, a.P, a.space, a.raw, a.panel, a.ldp, a.np, a.T, a.N, TC, a.mats,
-                       a.T_use, a.out, a.flags, nullptr, nullptr, 0, 0);
-  }
+  const bool rc = a.rec_beta != nullptr;
+  auto* k = rc ? &fixedz_dd_loglik_kernel<L, M, LEAD, true> : &fixedz_dd_loglik_kernel<L, M, LEAD, false>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kFdBlock), shmem, a.stream, rec, a.defer_list, a.defer_count, a.theta, a.P,
+                     a.space, a.raw, a.panel, a.ldp, a.np, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags, a.rec_beta,
+                     rc ? a.rec_P : nullptr, rc ? a.horizon : 0, rc ? a.rec_len : 0);
   return hipGetLastError();
 }
 
@@ -523,8 +483,7 @@ hipError_t launch_fd_m(const LaunchArgs& a, double* rec) {
   int L = 4;
   while (L * MPL < a.N && L < 64) L <<= 1;
   if (L * MPL < a.N) return hipErrorInvalidValue;
-  int TC = (kFdPre * kFdBlock) / a.N;
-  if (TC > 32) TC = 32;
+  const int TC = chunk_columns(kFdPre * kFdBlock, a.N);
   if (TC < 1) return hipErrorInvalidValue;
   switch (L) {
     case 4: return launch_fd_l<4, M, LEAD>(a, rec, TC);

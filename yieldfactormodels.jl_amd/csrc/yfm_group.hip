@@ -177,28 +177,18 @@ hipError_t launch_group_l(const LaunchArgs& a, int TC) {
   constexpr int GPB = kGBlock / L;
   const int grid = (a.B + GPB - 1) / GPB;
   const size_t shmem = sizeof(double) * (size_t)TC * a.ldp;
-  if (a.rec_beta) {
-    hipLaunchKernelGGL((fixedz_group_kernel<L, M, LEAD, true>), dim3(grid), dim3(kGBlock), shmem, a.stream, a.theta,
-                       a.P, a.B, a.space, a.panel, a.ldp, a.np, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags,
-                       a.rec_beta, a.rec_P, a.horizon, a.rec_len, a.defer_list, a.defer_count, a.flags_next);
-  } else {
-    hipLaunchKernelGGL((fixedz_group_kernel<L, M, LEAD, false>), dim3(grid), dim3(kGBlock), shmem, a.stream, a.theta,
-                       a.P, a.B, a.space, a.panel, a.ldp, a.np, a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags,
-                       nullptr, nullptr, 0, 0, a.defer_list, a.defer_count, a.flags_next);
-  }
+  const bool rec = a.rec_beta != nullptr;
+  auto* k = rec ? &fixedz_group_kernel<L, M, LEAD, true> : &fixedz_group_kernel<L, M, LEAD, false>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kGBlock), shmem, a.stream, a.theta, a.P, a.B, a.space, a.panel, a.ldp, a.np,
+                     a.T, a.N, TC, a.mats, a.T_use, a.out, a.flags, a.rec_beta, rec ? a.rec_P : nullptr,
+                     rec ? a.horizon : 0, rec ? a.rec_len : 0, a.defer_list, a.defer_count, a.flags_next);
   return hipGetLastError();
 }
 
 template <int M, int LEAD>
 hipError_t launch_group_m(const LaunchArgs& a, int L, int TC) {
-  switch (L) {
-    case 4: return launch_group_l<4, M, LEAD>(a, TC);
-    case 8: return launch_group_l<8, M, LEAD>(a, TC);
-    case 16: return launch_group_l<16, M, LEAD>(a, TC);
-    case 32: return launch_group_l<32, M, LEAD>(a, TC);
-    case 64: return launch_group_l<64, M, LEAD>(a, TC);
-  }
-  return hipErrorInvalidValue;
+  return with_lanes_of<4, 8, 16, 32, 64>(
+      L, [&](auto ln) { return launch_group_l<decltype(ln)::value, M, LEAD>(a, TC); });
 }
 
 }  // namespace
@@ -216,8 +206,7 @@ hipError_t launch_fixedz_group(int kind, const LaunchArgs& a) {
   if (!a.defer_list || !a.defer_count) return hipErrorInvalidValue;
   const int L = group_lanes_for(kind, a.N);
   if (L < 0) return hipErrorInvalidValue;
-  int TC = (kGPre * kGBlock) / a.ldp;  // columns per chunk: the prefetch registers hold ≤ kGPre·256
-  if (TC > 32) TC = 32;
+  const int TC = chunk_columns(kGPre * kGBlock, a.ldp);
   if (TC < 1) return hipErrorInvalidValue;
   if (kind == 0) return launch_group_m<3, 1>(a, L, TC);
   if (kind == 2) return launch_group_m<5, 2>(a, L, TC);

@@ -1,6 +1,7 @@
 // yfm_internal.hpp — launch interface between the C ABI (yfm_capi.hip) and the kernels.
 #pragma once
 #include "yfm_flags.hpp"
+#include "yfm_tvl_layout.hpp"  // chunk_columns, kTvlGaps, kTvlPowGaps
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -37,6 +38,18 @@ struct DevBuf {
     return e;
   }
 };
+
+// A lane count as a type, and f(Lanes<L>) for the L among Ls that `lanes` names (any other count is refused)
+template <int LN>
+struct Lanes {
+  static constexpr int value = LN;
+};
+template <int... Ls, class F>
+hipError_t with_lanes_of(int lanes, F&& f) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((lanes == Ls && ((e = f(Lanes<Ls>{})), true)) || ...);
+  return e;
+}
 
 struct LaunchArgs {
   const double* theta;  // P×B device
@@ -135,8 +148,6 @@ size_t tvl_scratch_bytes(int B);
 // Power mode (the certified kernel, when the jumps are too many or inexact): every maturity is an exact integer
 // multiple k_i·Δ of one step Δ (integer-month grids), so e^{−λm_i} = b^{k_i} with b = e^{−λΔ} — one dd exp per
 // step and integer powers of b for the lane starts and the Kp ≤ kTvlPowGaps distinct jump exponents e_q.
-constexpr int kTvlGaps = 8;
-constexpr int kTvlPowGaps = 16;
 struct TvlGaps {
   int K = 0;
   bool exact = false;         // every jump is the exact difference of its two maturities

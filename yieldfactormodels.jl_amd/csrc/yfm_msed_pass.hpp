@@ -138,12 +138,7 @@ struct Variant {
   static constexpr int L = LN;
   static constexpr bool STATIC = ST, HASB = HB, SCALED = SC;
 };
-template <int LN>
-struct Lanes {
-  static constexpr int value = LN;
-};
-
-// f(Lanes<L>) for the lane counts the tree is built for
+// f(Lanes<L>) for the tree's lane counts (a switch: through with_lanes_of nns_*_kernel's assembly moves)
 template <class F>
 hipError_t with_lanes(int lanes, F&& f) {
   switch (lanes) {

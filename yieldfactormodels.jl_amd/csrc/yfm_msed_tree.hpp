@@ -9,6 +9,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "yfm_tvl_layout.hpp"  // chunk_columns
+
 namespace yfm {
 namespace msedtree {
 
@@ -64,11 +66,7 @@ constexpr int log_classes_per_lane() {
 }
 
 // columns per panel chunk: the prefetch registers hold ≤ kMsedPre·256 yields (0: N is out of range)
-inline int chunk_columns(int N) {
-  if (N < 1) return 0;
-  const int TC = (kMsedPre * kMsedBlock) / N;
-  return TC > 32 ? 32 : TC;
-}
+inline int chunk_columns(int N) { return yfm::chunk_columns(kMsedPre * kMsedBlock, N); }
 
 }  // namespace msedtree
 }  // namespace yfm

@@ -26,11 +26,18 @@
 //
 // Panel: the caller's raw N×T column-major matrix (columns staged into LDS TC at a
 // time, prefetched into registers one chunk ahead) plus the per-column NaN flags of
-// the prepared panel (yfm_kernels.hip: prep_panel_kernel, offset np+2, stride ldp).
+// the prepared panel (yfm_kernels.hip: prep_panel_kernel, offset np+2, stride ldp):
+// raw_chunk_load / raw_chunk_store of yfm_device.hpp.
+// Elsewhere (DESIGN.md §3.2c maps the pieces and says what stays inline): a maturity's loadings,
+// innovation and 14 sums and the Gram matrix in yfm_tvl_step.hpp (shared with the tangent
+// kernels); the LDS layout in yfm_tvl_layout.hpp (the launcher passes TvlSmem's bytes()).
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
+#include "yfm_tvl_step.hpp"
 
 namespace yfm {
+
+using namespace tvlstep;  // the statistics S2 … VV of a step, accum_stats, tvl_gram
 
 namespace {
 
@@ -38,13 +45,6 @@ constexpr int kTvlBlock = 256;
 constexpr int kTvlPre = 8;  // panel doubles prefetched per thread per chunk (≤ 2 waves/SIMD of VGPRs)
 
 }  // namespace
-
-// Sufficient statistics of one EKF step, indices into the accumulator array.
-// Σ Z_c (c = 2..4), the Gram entries, u = Z'v and v'v, with the innovation
-// v = y − Z[:,1:3]β[1:3] formed per maturity as the reference does (filter.jl:33-34): the
-// uncentered reconstruction v'v = y'y − 2β'Z'y + β'Gβ loses ‖Z‖‖β‖/‖v‖ digits when the
-// loadings are nearly collinear (measured: 1.8e-8 on a random N = 33, T = 3 case).
-enum : int { S2 = 0, S3, S4, G22, G23, G24, G33, G34, G44, U1, U2, U3, U4, VV, NSTAT };
 
 // Per-candidate record written by tvl_init_kernel (layout kRec* in yfm_internal.hpp): the
 // decoded parameters and the initial state, so the filter kernel never holds the 10×10
@@ -79,13 +79,6 @@ __global__ __launch_bounds__(256) void tvl_init_kernel(const double* __restrict_
   r[kRecOk] = ok ? 1.0 : 0.0;
   r[46] = 0.0;
   r[47] = 0.0;
-}
-
-// x of lane `src` of this wave (ds_bpermute: the LDS crossbar, no LDS memory and no wave barrier)
-__device__ __forceinline__ double lane_read_f64(int src, double x) {
-  const int lo = __builtin_amdgcn_ds_bpermute(src << 2, __double2loint(x));
-  const int hi = __builtin_amdgcn_ds_bpermute(src << 2, __double2hiint(x));
-  return __hiloint2double(hi, lo);
 }
 
 // Lane-distributed 4×4 update (L ≥ 4): the four roles qr = lane & 3 of each quad hold column qr of P,
@@ -171,6 +164,54 @@ struct TvlQuad {
   }
 };
 
+// the epilogue, by lane 0 of a live group: get_loss's value from the accumulated terms (nobs columns: nobs − 2 terms),
+// NaN (flags[0]) where initialize_filter threw, −Inf (flags[1]) on a DomainError or a value that is not finite
+__device__ __forceinline__ void tvl_finish(bool init_ok, int nobs, int N, double sigma2, const LogDetAcc& ld,
+                                           double sumq, bool neg, unsigned int* __restrict__ flags,
+                                           double* __restrict__ out, int b) {
+  double ll;
+  if (!init_ok) {
+    ll = __builtin_nan("");  // the reference throws from initialize_filter
+    atomicAdd(&flags[0], 1u);
+  } else {
+    const int nterms = max(nobs - 2, 0);
+    if (nterms == 0) {
+      ll = 0.0;
+    } else {
+      const double per_term = (double)(N - 4) * log(sigma2) + (double)N * kLog2Pi;
+      ll = -0.5 * ((double)nterms * per_term + ld.log_value() + sumq);
+    }
+    if (neg || !isfinite(ll)) {  // DomainError / non-finite → -Inf (filter.jl:197-204)
+      ll = -__builtin_inf();
+      atomicAdd(&flags[1], 1u);
+    }
+  }
+  out[b] = ll;
+}
+
+// RECORD: β_{t+1|t} and P_{t+1|t} of step t into slot t − (my_steps − rec_len) of candidate b (the last rec_len
+// steps are kept); every lane of a quad takes part in gathering P, the lane with `write` stores
+template <bool DIST>
+__device__ __forceinline__ void tvl_record(int t, int my_steps, int rec_len, bool write, int b, const double (&beta)[4],
+                                           const double (&Pc)[4], const double (&Pm)[4][4],
+                                           double* __restrict__ rec_beta, double* __restrict__ rec_P) {
+  constexpr int M = 4;
+  double Pfull[M][M];
+  if constexpr (DIST) quad_gather_rows<M>(Pc, Pfull);  // every lane of the quad takes part
+  const int slot = t - max(0, my_steps - rec_len);  // the last rec_len steps
+  if (write && slot >= 0) {
+    const size_t o = (size_t)b * (size_t)rec_len + slot;
+#pragma unroll
+    for (int i = 0; i < M; ++i) rec_beta[o * M + i] = beta[i];
+    if (rec_P) {
+#pragma unroll
+      for (int k = 0; k < M; ++k)
+#pragma unroll
+        for (int i = 0; i < M; ++i) rec_P[o * M * M + k * M + i] = DIST ? Pfull[i][k] : Pm[i][k];
+    }
+  }
+}
+
 template <int L, bool RECORD>
 __global__ __launch_bounds__(kTvlBlock, 2) void tvl_loglik_kernel(
     const double* __restrict__ rec, int B, const double* __restrict__ Y,
@@ -181,12 +222,13 @@ __global__ __launch_bounds__(kTvlBlock, 2) void tvl_loglik_kernel(
   constexpr int M = 4;
   constexpr int GPB = kTvlBlock / L;  // filters per block
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  double2* s_mr = reinterpret_cast<double2*>(smem);  // (m_i, 1/m_i)
-  double* s_nan = smem + 2 * N;                       // TC NaN flags of the staged chunk
-  double* s_y = s_nan + TC;                           // TC columns of N yields (column-major, stride N)
-  double* s_w = s_y + TC * N;                         // per group: e^{-λ d_k}, k < K (≤ kTvlGaps)
-  double* s_xch = s_w + GPB * kTvlGaps;               // per group: 4×4 exchange block (L ≥ 4)
-  int* s_gi = reinterpret_cast<int*>(s_xch + (L >= 4 ? GPB * 16 : 0));  // gap index of the jump i → i + L
+  const TvlSmem lay{N, TC, GPB, L};  // the regions and what they hold: yfm_tvl_layout.hpp
+  double2* s_mr = reinterpret_cast<double2*>(smem);
+  double* s_nan = smem + lay.mr();
+  double* s_y = s_nan + lay.nan();
+  double* s_w = s_y + lay.y();
+  double* s_xch = s_w + lay.w();
+  int* s_gi = reinterpret_cast<int*>(s_xch + lay.xch());
   __shared__ double s_gd[kTvlGaps];
   __shared__ int s_nobs_max;
 
@@ -281,25 +323,9 @@ __global__ __launch_bounds__(kTvlBlock, 2) void tvl_loglik_kernel(
   double pre[kTvlPre];
   double pre_nan = 0.0;
   auto load_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int r = 0; r < kTvlPre; ++r) {
-      const int e = r * kTvlBlock + tid;
-      const size_t g = base + e;
-      pre[r] = (e < CHY && g < lim) ? Y[g] : 0.0;
-    }
-    const int tc = c * TC + tid;
-    pre_nan = (tid < TC && tc < T) ? prep[(size_t)tc * ldp + np + 2] : 0.0;
+    raw_chunk_load<kTvlPre, kTvlBlock>(Y, prep, ldp, np, T, N, TC, CHY, c, tid, pre, pre_nan);
   };
-  auto store_chunk = [&]() {
-#pragma unroll
-    for (int r = 0; r < kTvlPre; ++r) {
-      const int e = r * kTvlBlock + tid;
-      if (e < CHY) s_y[e] = pre[r];
-    }
-    if (tid < TC) s_nan[tid] = pre_nan;
-  };
+  auto store_chunk = [&]() { raw_chunk_store<kTvlPre, kTvlBlock>(s_y, s_nan, TC, CHY, tid, pre, pre_nan); };
   if (nsteps > 0) {
     load_chunk(0);
     store_chunk();
@@ -361,28 +387,8 @@ __global__ __launch_bounds__(kTvlBlock, 2) void tvl_loglik_kernel(
       for (int k = 0; k < NSTAT; ++k) s[k] = 0.0;
       // one maturity: z = e^{-λm}, loadings, Jacobian column, statistics
       auto accum = [&](double2 mr, double z, double y) {
-        const double m = mr.x;
-        const double it = rl * mr.y;             // 1/τ
-        const double z2 = (1.0 - z) * it;        // (1 − z)/τ
-        const double z3 = z2 - z;
-        // Jacobian column as written (filter.jl:43-46): ((β2+β3)(z/λ − z/(λ²m)) + β3·m·z)·(λ − 0.01)
-        //   = z·(k1 − k1/(λm) + c2·m),  k1 = c1/λ
-        const double z4 = z * fma(c2, m, fma(-k1, it, k1));
-        s[S2] += z2;
-        s[S3] += z3;
-        s[S4] += z4;
-        s[G22] = fma(z2, z2, s[G22]);
-        s[G23] = fma(z2, z3, s[G23]);
-        s[G24] = fma(z2, z4, s[G24]);
-        s[G33] = fma(z3, z3, s[G33]);
-        s[G34] = fma(z3, z4, s[G34]);
-        s[G44] = fma(z4, z4, s[G44]);
-        const double v = y - fma(beta[2], z3, fma(beta[1], z2, beta[0]));  // y − Z[:,1:3]β[1:3]
-        s[U1] += v;
-        s[U2] = fma(z2, v, s[U2]);
-        s[U3] = fma(z3, v, s[U3]);
-        s[U4] = fma(z4, v, s[U4]);
-        s[VV] = fma(v, v, s[VV]);
+        Row r;
+        accum_stats(rl, k1, c2, beta, mr.x, mr.y, z, y, s, r);
       };
       if (K > 0) {
         // few distinct jumps d_k = m_{i+L} − m_i: z_{i+L} = z_i · e^{-λ d_k}, one exp per lane
@@ -400,9 +406,7 @@ __global__ __launch_bounds__(kTvlBlock, 2) void tvl_loglik_kernel(
         } else {
           double* w = s_w + grp * kTvlGaps;
           for (int q = j; q < K; q += L) w[q] = exp(-(lam * s_gd[q]));
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+          wave_lds_sync();
 #pragma unroll 2
           for (int i = j; i < N; i += L) {
             const double2 mr = s_mr[i];
@@ -422,16 +426,7 @@ __global__ __launch_bounds__(kTvlBlock, 2) void tvl_loglik_kernel(
       for (int k = 0; k < NSTAT; ++k) s[k] = group_sum<L>(s[k]);
 
       double G[M][M];
-      G[0][0] = (double)N;
-      G[0][1] = G[1][0] = s[S2];
-      G[0][2] = G[2][0] = s[S3];
-      G[0][3] = G[3][0] = s[S4];
-      G[1][1] = s[G22];
-      G[1][2] = G[2][1] = s[G23];
-      G[1][3] = G[3][1] = s[G24];
-      G[2][2] = s[G33];
-      G[2][3] = G[3][2] = s[G34];
-      G[3][3] = s[G44];
+      tvl_gram(s, N, G);
       const double u[M] = {s[U1], s[U2], s[U3], s[U4]};
       const double vv = s[VV];
 
@@ -550,20 +545,7 @@ __global__ __launch_bounds__(kTvlBlock, 2) void tvl_loglik_kernel(
       }
     }
     if constexpr (RECORD) {
-      double Pfull[M][M];
-      if constexpr (DIST) quad_gather_rows<M>(Pc, Pfull);  // every lane of the quad takes part
-      const int slot = t - max(0, my_steps - rec_len);  // the last rec_len steps
-      if (live && act && j == 0 && slot >= 0) {
-        const size_t o = (size_t)b * (size_t)rec_len + slot;
-#pragma unroll
-        for (int i = 0; i < M; ++i) rec_beta[o * M + i] = beta[i];
-        if (rec_P) {
-#pragma unroll
-          for (int k = 0; k < M; ++k)
-#pragma unroll
-            for (int i = 0; i < M; ++i) rec_P[o * M * M + k * M + i] = DIST ? Pfull[i][k] : Pm[i][k];
-        }
-      }
+      tvl_record<DIST>(t, my_steps, rec_len, live && act && j == 0, b, beta, Pc, Pm, rec_beta, rec_P);
     }
     if (tt == TC - 1) {  // chunk done: its buffer takes the prefetched chunk, prefetch the one after
       __syncthreads();
@@ -575,24 +557,7 @@ __global__ __launch_bounds__(kTvlBlock, 2) void tvl_loglik_kernel(
   }
 
   if (!live || j != 0) return;
-  double ll;
-  if (!init_ok) {
-    ll = __builtin_nan("");  // the reference throws from initialize_filter
-    atomicAdd(&flags[0], 1u);
-  } else {
-    const int nterms = max(nobs - 2, 0);
-    if (nterms == 0) {
-      ll = 0.0;
-    } else {
-      const double per_term = (double)(N - M) * log(sigma2) + (double)N * kLog2Pi;
-      ll = -0.5 * ((double)nterms * per_term + ld.log_value() + sumq);
-    }
-    if (neg || !isfinite(ll)) {  // DomainError / non-finite → -Inf (filter.jl:197-204)
-      ll = -__builtin_inf();
-      atomicAdd(&flags[1], 1u);
-    }
-  }
-  out[b] = ll;
+  tvl_finish(init_ok, nobs, N, sigma2, ld, sumq, neg, flags, out, b);
 }
 
 namespace {
@@ -601,19 +566,14 @@ template <int L>
 hipError_t launch_tvl_l(const LaunchArgs& a, const TvlGaps& g, int TC) {
   constexpr int GPB = kTvlBlock / L;
   const int grid = (a.B + GPB - 1) / GPB;
-  const size_t shmem = sizeof(double) * (size_t)(2 * a.N + TC + TC * a.N + GPB * kTvlGaps + (L >= 4 ? GPB * 16 : 0)) +
-                       sizeof(int) * a.N;
+  const size_t shmem = TvlSmem{a.N, TC, GPB, L}.bytes();
   hipLaunchKernelGGL(tvl_init_kernel, dim3((a.B + 255) / 256), dim3(256), 0, a.stream, a.theta, a.P, a.B, a.space,
                      a.scratch, a.flags_next);
-  if (a.rec_beta) {
-    hipLaunchKernelGGL((tvl_loglik_kernel<L, true>), dim3(grid), dim3(kTvlBlock), shmem, a.stream, a.scratch, a.B,
-                       a.raw, a.panel, a.ldp, a.np, a.T, a.N, TC, a.mats, g.K, g.d, g.idx, a.T_use, a.out, a.flags, a.rec_beta,
-                       a.rec_P, a.horizon, a.rec_len);
-  } else {
-    hipLaunchKernelGGL((tvl_loglik_kernel<L, false>), dim3(grid), dim3(kTvlBlock), shmem, a.stream, a.scratch, a.B,
-                       a.raw, a.panel, a.ldp, a.np, a.T, a.N, TC, a.mats, g.K, g.d, g.idx, a.T_use, a.out, a.flags, nullptr,
-                       nullptr, 0, 0);
-  }
+  const bool rec = a.rec_beta != nullptr;
+  auto* k = rec ? &tvl_loglik_kernel<L, true> : &tvl_loglik_kernel<L, false>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kTvlBlock), shmem, a.stream, a.scratch, a.B, a.raw, a.panel, a.ldp, a.np, a.T,
+                     a.N, TC, a.mats, g.K, g.d, g.idx, a.T_use, a.out, a.flags, a.rec_beta, rec ? a.rec_P : nullptr,
+                     rec ? a.horizon : 0, rec ? a.rec_len : 0);
   return hipGetLastError();
 }
 
@@ -650,20 +610,10 @@ int tvl_lanes_for(int B, int N, int share) {
 }
 
 hipError_t launch_tvl(const LaunchArgs& a, const TvlGaps& g, int lanes) {
-  // columns per chunk: the prefetch registers hold ≤ kTvlPre·256 yields
-  int TC = (kTvlPre * kTvlBlock) / a.N;
-  if (TC > 32) TC = 32;
+  const int TC = chunk_columns(kTvlPre * kTvlBlock, a.N);
   if (TC < 1) return hipErrorInvalidValue;
-  switch (lanes) {
-    case 1: return launch_tvl_l<1>(a, g, TC);
-    case 2: return launch_tvl_l<2>(a, g, TC);
-    case 4: return launch_tvl_l<4>(a, g, TC);
-    case 8: return launch_tvl_l<8>(a, g, TC);
-    case 16: return launch_tvl_l<16>(a, g, TC);
-    case 32: return launch_tvl_l<32>(a, g, TC);
-    case 64: return launch_tvl_l<64>(a, g, TC);
-  }
-  return hipErrorInvalidValue;
+  return with_lanes_of<1, 2, 4, 8, 16, 32, 64>(lanes,
+                                               [&](auto ln) { return launch_tvl_l<decltype(ln)::value>(a, g, TC); });
 }
 
 }  // namespace yfm

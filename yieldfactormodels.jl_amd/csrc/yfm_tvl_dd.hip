@@ -23,6 +23,9 @@
 // tvl_dd_init_kernel (one thread per candidate) and hand over a per-candidate record.
 // exp(−λ m_i) walks the maturities of a lane with the dd jump factors e^{−λ d_k}
 // (relative drift ≤ (N/L)·2^-104).
+// Shared with yfm_tvl.hip: the raw-panel staging of yfm_device.hpp (the column sums and max|y| are
+// staged beside it here); the LDS layout is TvlDdSmem of yfm_tvl_layout.hpp, the epilogue
+// dd_finish_loglik of yfm_dd.hpp.  DESIGN.md §3.2c lists what stays inline in the kernel body.
 #include "yfm_dd.hpp"
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
@@ -38,15 +41,9 @@ namespace {
 constexpr int kDdBlock = 256;
 constexpr int kDdPre = 8;  // panel doubles prefetched per thread per chunk
 constexpr int M4 = 4;
-// per-group jump factors e^{−λ d_k} in LDS: 17 dd (272 B) apart, so the 16 groups of a wave
-// reading their own table hit disjoint banks (a power-of-two stride is a 4-way conflict)
-constexpr int kDdJumps = kTvlPowGaps > kTvlGaps ? kTvlPowGaps : kTvlGaps;
-constexpr int kDdWStride = kDdJumps + 1;
-// per-group 4×4 dd exchange blocks 17 dd (272 B) apart: at 16 dd (256 B = 64 banks) the 16 groups of a wave
-// exchanging the same entry all hit the same banks — a 16-way conflict on every transpose
-constexpr int kXchStride = 4 * 4 + 1;
 
-// per-candidate record written by tvl_dd_init_kernel (doubles)
+// per-candidate record written by tvl_dd_init_kernel (doubles); its first kDPar (σ², δ, Φ, Q: yfm_tvl_layout.hpp) are
+// the read-only part staged in LDS per group
 constexpr int kDSig = 0;     // σ² (dd)
 constexpr int kDDelta = 2;   // δ (4 doubles, exact θ entries)
 constexpr int kDPhi = 6;     // Φ row-major (16 dd)
@@ -55,58 +52,8 @@ constexpr int kDBeta = 58;   // β₀ (4 dd)
 constexpr int kDP = 66;      // P₀ upper triangle (10 dd)
 constexpr int kDOk = 86;
 constexpr int kDRecLen = 88;
-constexpr int kDPar = 58;    // σ², δ, Φ, Q: the read-only part staged in LDS per group
 
 __device__ __forceinline__ int utri(int i, int k) { return i * M4 - i * (i - 1) / 2 + (k - i); }  // i ≤ k < 4
-
-// β ← δ + Φ b;  P ← Φ X Φ'·s + Q  (X symmetric, upper triangle; s = σ² after an update, 1 for
-// the prediction-only step)
-__device__ __forceinline__ void dd_propagate(const double* par, const dd (&b)[M4], const dd (&X)[10], bool scale,
-                                             dd (&beta)[M4], dd (&P)[10]) {
-  const dd* Phi = reinterpret_cast<const dd*>(par + kDPhi);
-  const dd* Q = reinterpret_cast<const dd*>(par + kDQ);
-  const dd sig2 = *reinterpret_cast<const dd*>(par + kDSig);
-  dd A[M4][M4];
-#pragma unroll
-  for (int i = 0; i < M4; ++i) {
-    dd s = dd_make(par[kDDelta + i]);
-#pragma unroll
-    for (int j = 0; j < M4; ++j) s = dd_add(s, dd_mul(Phi[i * M4 + j], b[j]));
-    beta[i] = s;
-#pragma unroll
-    for (int j = 0; j < M4; ++j) {
-      dd_acc a;
-#pragma unroll
-      for (int l = 0; l < M4; ++l) a.add_prod(Phi[i * M4 + l], X[l <= j ? utri(l, j) : utri(j, l)]);
-      A[i][j] = a.value();
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < M4; ++i)
-#pragma unroll
-    for (int k = i; k < M4; ++k) {
-      dd_acc a;
-#pragma unroll
-      for (int l = 0; l < M4; ++l) a.add_prod(A[i][l], Phi[k * M4 + l]);
-      dd s = a.value();
-      if (scale) s = dd_mul(s, sig2);
-      P[utri(i, k)] = dd_add(s, Q[utri(i, k)]);
-    }
-}
-
-// x of the lane at byte address `addr` (= lane · 4) of this wave (ds_bpermute: the LDS crossbar, no LDS memory)
-__device__ __forceinline__ double lane_read(int addr, double x) {
-  const int lo = __builtin_amdgcn_ds_bpermute(addr, __double2loint(x));
-  const int hi = __builtin_amdgcn_ds_bpermute(addr, __double2hiint(x));
-  return __hiloint2double(hi, lo);
-}
-
-// LDS writes of this wave visible to its own later reads (the quads of a filter are in one wave)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // the dd held by lane S of this lane's 16-lane row (DPP row_newbcast)
 template <int S>
@@ -127,8 +74,10 @@ __device__ __forceinline__ void gather_sym(const dd (&col)[M4], dd (&X)[M4][M4])
   bcast_row<3>(col, X[3]);
 }
 
-// dd_propagate distributed over the quad (role qr = lane & 3; lanes of a group with the same role
-// compute the same values): β_qr then a broadcast; column qr of A = ΦX from column qr of X (the entry role i of the
+// β ← δ + Φ b;  P ← Φ X Φ'·s + Q  (X symmetric; s = σ² after an update, 1 for the prediction-only step), distributed
+// over the quad (role qr = lane & 3; lanes of a group with the same role compute the same values).  dd_propagate
+// is the one-lane form this replaced (in git history: rows of A = ΦX, then the upper triangle of AΦ'·s + Q, every
+// entry a dd_acc sum over l = 0 … 3).  β_qr then a broadcast; column qr of A = ΦX from column qr of X (the entry role i of the
 // row form would form, in the same operation order), one gather; then column qr of the new P.  Every upper entry
 // (i ≤ k) is formed by role k exactly as dd_propagate forms it, and the entry below the diagonal is taken from the
 // role that owns it as an upper entry, so P stays bitwise symmetric and bitwise dd_propagate's.  xc: column qr of
@@ -174,10 +123,10 @@ __device__ __forceinline__ void dd_propagate_q(const double* par, int qr, int qg
       pc = dd_add(s, Q[qg <= qr ? utri(qg, qr) : utri(qr, qg)]);
     }
     xch[qr * M4 + qg] = pc;
-    wave_sync();
+    wave_lds_sync();
 #pragma unroll
     for (int k = 0; k < M4; ++k) Pc[k] = xch[k <= qr ? qr * M4 + k : k * M4 + qr];
-    wave_sync();  // the block is rewritten by the next exchange
+    wave_lds_sync();  // the block is rewritten by the next exchange
     return;
   }
   dd At[M4][M4];  // At[l][i] = A[i][l]
@@ -205,13 +154,34 @@ __device__ __forceinline__ void dd_propagate_q(const double* par, int qr, int qg
   // role qr's value of entry (k, qr) is its own for k ≤ qr and role k's upper entry (qr, k) below
 #pragma unroll
   for (int k = 0; k < M4; ++k) xch[qr * M4 + k] = pc[k];
-  wave_sync();
+  wave_lds_sync();
 #pragma unroll
   for (int k = 0; k < M4; ++k) {
     const dd o = xch[k * M4 + qr];
     Pc[k] = k <= qr ? pc[k] : o;
   }
-  wave_sync();  // the block is rewritten by the next exchange
+  wave_lds_sync();  // the block is rewritten by the next exchange
+}
+
+// RECORD: β_{t+1|t} and P_{t+1|t} of step t, rounded to FP64, into slot t − (my_steps − rec_len) of candidate b (the
+// last rec_len steps are kept); every lane of a quad takes part in gathering P, the lane with `write` stores
+__device__ __forceinline__ void tvl_dd_record(int t, int my_steps, int rec_len, bool act, int j, int b, const dd (&beta)[M4],
+                                              const dd (&Pc)[M4], double* __restrict__ rec_beta,
+                                              double* __restrict__ rec_P) {
+  const int slot = t - max(0, my_steps - rec_len);
+  dd Pf[M4][M4];
+  gather_sym(Pc, Pf);  // every lane of the quad takes part in the exchange
+  if (act && j == 0 && slot >= 0) {
+    const size_t o = (size_t)b * (size_t)rec_len + slot;
+#pragma unroll
+    for (int i = 0; i < M4; ++i) rec_beta[o * M4 + i] = dd_to_double(beta[i]);
+    if (rec_P) {
+#pragma unroll
+      for (int c = 0; c < M4; ++c)
+#pragma unroll
+        for (int i = 0; i < M4; ++i) rec_P[o * M4 * M4 + c * M4 + i] = dd_to_double(Pf[i][c]);
+    }
+  }
 }
 
 }  // namespace
@@ -350,17 +320,17 @@ __global__ __launch_bounds__(kDdBlock, 1) void tvl_dd_loglik_kernel(
     int rec_len) {
   constexpr int GPB = kDdBlock / L;
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  constexpr int kSumDd = 2;                            // dd column sums per staged column
-  double* s_m = smem;                                  // m_i
-  dd* s_rm = reinterpret_cast<dd*>(smem + N);          // 1/m_i (dd)
-  double* s_nan = smem + 3 * N;                        // TC NaN flags of the staged chunk
-  dd* s_sum = reinterpret_cast<dd*>(s_nan + TC);       // per staged column: Σy, Σy² (dd)
-  double* s_ymax = s_nan + (1 + 2 * kSumDd) * TC;      // per staged column: max_i |y_i|
-  double* s_y = s_ymax + TC;                           // TC columns of N yields
-  double* s_par = s_y + TC * N;                        // per group: σ², δ, Φ, Q (kDPar doubles)
-  dd* s_w = reinterpret_cast<dd*>(s_par + GPB * kDPar);  // per group: e^{-λ d_k}, k < K
-  dd* s_xch = s_w + GPB * kDdWStride;                  // per group: 4×4 dd exchange block
-  int* s_gi = reinterpret_cast<int*>(s_xch + GPB * kXchStride);
+  const TvlDdSmem lay{N, TC, GPB, L};  // the regions and what they hold: yfm_tvl_layout.hpp
+  double* s_m = smem;
+  dd* s_rm = reinterpret_cast<dd*>(smem + N);
+  double* s_nan = smem + lay.mats();
+  dd* s_sum = reinterpret_cast<dd*>(s_nan + TC);
+  double* s_ymax = s_nan + lay.cols();
+  double* s_y = s_ymax + lay.ymax();
+  double* s_par = s_y + lay.y();
+  dd* s_w = reinterpret_cast<dd*>(s_par + lay.par());
+  dd* s_xch = s_w + lay.w();
+  int* s_gi = reinterpret_cast<int*>(s_xch + lay.xch());
   // jump k: the maturity difference d_k, or (power mode, pstep = Δ > 0) its exponent e_k: e^{−λd_k} = (e^{−λΔ})^{e_k}
   __shared__ double s_gd[kDdJumps];
   __shared__ int s_gsrc[kDdJumps];  // a lane whose first maturity equals jump k exactly, or −1
@@ -435,29 +405,16 @@ __global__ __launch_bounds__(kDdBlock, 1) void tvl_dd_loglik_kernel(
   double pre[kDdPre];
   double pre_nan = 0.0, pre_sum[2 * kSumDd] = {}, pre_ymax = 0.0;
   auto load_chunk = [&](int c) {
-    const size_t base = (size_t)c * CHY;
-    const size_t lim = (size_t)T * N;
-#pragma unroll
-    for (int q = 0; q < kDdPre; ++q) {
-      const int e = q * kDdBlock + tid;
-      const size_t g = base + e;
-      pre[q] = (e < CHY && g < lim) ? Y[g] : 0.0;
-    }
+    raw_chunk_load<kDdPre, kDdBlock>(Y, prep, ldp, np, T, N, TC, CHY, c, tid, pre, pre_nan);
     const int tc = c * TC + tid;
     const bool own = tid < TC && tc < T;
-    pre_nan = own ? prep[(size_t)tc * ldp + np + 2] : 0.0;
 #pragma unroll
     for (int q = 0; q < 4; ++q) pre_sum[q] = own ? colsum[(size_t)tc * 4 + q] : 0.0;
     pre_ymax = own ? colsum[(size_t)T * 4 + tc] : 0.0;
   };
   auto store_chunk = [&]() {
-#pragma unroll
-    for (int q = 0; q < kDdPre; ++q) {
-      const int e = q * kDdBlock + tid;
-      if (e < CHY) s_y[e] = pre[q];
-    }
+    raw_chunk_store<kDdPre, kDdBlock>(s_y, s_nan, TC, CHY, tid, pre, pre_nan);
     if (tid < TC) {
-      s_nan[tid] = pre_nan;
       s_sum[kSumDd * tid] = {pre_sum[0], pre_sum[1]};
       s_sum[kSumDd * tid + 1] = {pre_sum[2], pre_sum[3]};
       s_ymax[tid] = pre_ymax;
@@ -608,11 +565,7 @@ __global__ __launch_bounds__(kDdBlock, 1) void tvl_dd_loglik_kernel(
               if (s_gsrc[q] < 0) w[q] = dd_exp(neg_rate(lam, s_gd[q]));
           }
         }
-        if (!jump1) {
-          __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          __builtin_amdgcn_wave_barrier();
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
+        if (!jump1) wave_lds_sync();
         // the LDS operands of maturity i + L are read while maturity i is accumulated (at one wave per SIMD a
         // read at the top of the iteration it feeds stalls the wave for the LDS latency); the last read is a
         // harmless repeat of maturity N − 1.  LONG (≥ 32 maturities per lane: config 3's 90 at L = 4): the one-jump
@@ -627,8 +580,8 @@ __global__ __launch_bounds__(kDdBlock, 1) void tvl_dd_loglik_kernel(
           // one jump (uniform grids): the factor is loop-invariant
           dd wn;
           if (jump1) {
-            const int src = ((tid & 63) - j + s_gsrc[0]) << 2;  // the source lane of this group (groups are wave-aligned)
-            wn = {lane_read(src, z.hi), lane_read(src, z.lo)};
+            const int src = (tid & 63) - j + s_gsrc[0];  // the source lane of this group (groups are wave-aligned)
+            wn = {lane_read_f64(src, z.hi), lane_read_f64(src, z.lo)};
           } else {
             wn = w[0];
           }
@@ -780,10 +733,10 @@ __global__ __launch_bounds__(kDdBlock, 1) void tvl_dd_loglik_kernel(
       dd ws[M4];
 #pragma unroll
       for (int k = 0; k < M4; ++k) xch[qr * M4 + k] = x[k][0];
-      wave_sync();
+      wave_lds_sync();
 #pragma unroll
       for (int k = 0; k < M4; ++k) ws[k] = dd_ldexp(dd_add(x[k][0], xch[k * M4 + qr]), -1);
-      wave_sync();
+      wave_lds_sync();
       // K v = W u: component qr, then all four
       dd kv[M4];
       {
@@ -819,20 +772,7 @@ __global__ __launch_bounds__(kDdBlock, 1) void tvl_dd_loglik_kernel(
       }
     }
     if constexpr (RECORD) {
-      const int slot = t - max(0, my_steps - rec_len);
-      dd Pf[M4][M4];
-      gather_sym(Pc, Pf);  // every lane of the quad takes part in the exchange
-      if (act && j == 0 && slot >= 0) {
-        const size_t o = (size_t)b * (size_t)rec_len + slot;
-#pragma unroll
-        for (int i = 0; i < M4; ++i) rec_beta[o * M4 + i] = dd_to_double(beta[i]);
-        if (rec_P) {
-#pragma unroll
-          for (int c = 0; c < M4; ++c)
-#pragma unroll
-            for (int i = 0; i < M4; ++i) rec_P[o * M4 * M4 + c * M4 + i] = dd_to_double(Pf[i][c]);
-        }
-      }
+      tvl_dd_record(t, my_steps, rec_len, act, j, b, beta, Pc, rec_beta, rec_P);
     }
     if (tt == TC - 1) {
       __syncthreads();
@@ -844,27 +784,7 @@ __global__ __launch_bounds__(kDdBlock, 1) void tvl_dd_loglik_kernel(
   }
 
   if (!live || j != 0) return;
-  double ll;
-  if (!init_ok) {
-    ll = __builtin_nan("");
-    atomicAdd(&flags[0], 1u);
-  } else {
-    const int nterms = max(nobs - 2, 0);
-    if (nterms == 0) {
-      ll = 0.0;
-    } else {
-      // per term: (N − 4)·log σ² + N·log 2π (+ log|det B̃_t| + q_t, summed above)
-      const dd lsig = dd_log(sig2);
-      dd tot = dd_mul_d(dd_add_d(dd_mul_d(lsig, (double)(N - M4)), (double)N * kLog2Pi), (double)nterms);
-      tot = dd_add(tot, dd_add(sum_ld.value(), sum_q.value()));
-      ll = -0.5 * dd_to_double(tot);
-    }
-    if (neg || !isfinite(ll)) {
-      ll = -__builtin_inf();
-      atomicAdd(&flags[1], 1u);
-    }
-  }
-  out[b] = ll;
+  dd_finish_loglik(init_ok, nobs, N, M4, sig2, sum_ld, sum_q, neg, flags, out, b);
 }
 
 namespace {
@@ -873,12 +793,7 @@ template <int L>
 hipError_t launch_tvl_dd_l(const LaunchArgs& a, const double* rec_dd, const double* colsum, const TvlGaps& g, int TC) {
   constexpr int GPB = kDdBlock / L;
   const int grid = (a.B + GPB - 1) / GPB;
-  constexpr int kSumDd = 2;
-  // the kernel's LDS layout: m, 1/m, per staged column NaN flag, dd sums, max|y| and N yields, per group the
-  // parameters, jump factors and exchange block, and the jump index per maturity
-  const size_t shmem = sizeof(double) * (size_t)(3 * a.N + (2 + 2 * kSumDd) * TC + TC * a.N + GPB * kDPar +
-                                                 2 * GPB * kDdWStride + 2 * GPB * kXchStride) +
-                       sizeof(int) * a.N;
+  const size_t shmem = TvlDdSmem{a.N, TC, GPB, L}.bytes();
   if (shmem > 160 * 1024) return hipErrorInvalidValue;  // gfx950: 160 KiB of LDS per workgroup
   auto* k = a.rec_beta ? &tvl_dd_loglik_kernel<L, true> : &tvl_dd_loglik_kernel<L, false>;
   if constexpr (L <= 8) {
@@ -960,10 +875,9 @@ hipError_t launch_tvl_dd(const LaunchArgs& a, const double* rec_dd, const double
   // per maturity
   TvlGaps g = g_in;
   if (!g.exact) g.K = 0;
-  int TC = (kDdPre * kDdBlock) / a.N;
-  if (TC > 32) TC = 32;
+  const int TC = chunk_columns(kDdPre * kDdBlock, a.N);
   if (TC < 1) return hipErrorInvalidValue;
-  switch (lanes) {
+  switch (lanes) {  // not with_lanes_of: the order the kernels are emitted in is kept
     case 4: return launch_tvl_dd_l<4>(a, rec_dd, colsum, g, TC);
     case 8: return launch_tvl_dd_l<8>(a, rec_dd, colsum, g, TC);
     case 16: return launch_tvl_dd_l<16>(a, rec_dd, colsum, g, TC);

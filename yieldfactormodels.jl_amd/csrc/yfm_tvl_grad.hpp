@@ -33,12 +33,14 @@
 // Every fused multiply-add is an explicit fma; contraction is off.
 #pragma once
 #include "yfm_grad.hpp"  // gfma, gauss_solve, YFM_GHD
+#include "yfm_tvl_step.hpp"  // the statistics of a step, shared with tvl_loglik_kernel
 
 namespace yfm {
 namespace tvlgrad {
 
 using grad::gauss_solve;
 using grad::gfma;
+using namespace tvlstep;  // S2 … VV, NSTAT, Row, accum_stats, tvl_gram
 
 constexpr int kM = 4;
 constexpr int kNP = 31;  // σ², U (10, by column), δ (4), Φ (16, row-major)
@@ -297,9 +299,7 @@ YFM_GHD void init_state(const Model& m, const double* Linv, State& s, Tangent (&
 }
 
 // ---- the O(N) part of a data step: statistics and their state derivatives ------------------------------
-// statistics of one EKF step (the order of yfm_tvl.hip)
-enum : int { S2 = 0, S3, S4, G22, G23, G24, G33, G34, G44, U1, U2, U3, U4, VV, NSTAT };
-// the statistics that move with β₂ and β₃ beyond what other statistics already give: through Z₄
+// the statistics of one EKF step are tvlstep's (yfm_tvl_step.hpp); those that move with β₂ and β₃ beyond what other statistics already give: through Z₄
 enum : int { JS4 = 0, JG24, JG34, JG44, JU4, NJ };
 
 struct Moments {
@@ -343,27 +343,9 @@ YFM_GHD void step_consts(const double (&beta)[4], double minm, StepConst& k) {
 
 // one maturity m (rm = 1/m) with z = e^{−λm} and yield y
 YFM_GHD void accum(const StepConst& k, const double (&beta)[4], double m, double rm, double z, double y, Moments& mo) {
-  const double it = k.rl * rm;       // 1/τ
-  const double z2 = (1.0 - z) * it;  // (1 − z)/τ
-  const double z3 = z2 - z;
-  // Jacobian column as written (filter.jl:43-46): ((β2+β3)(z/λ − z/(λ²m)) + β3·m·z)·(λ − 0.01)
-  const double z4 = z * gfma(k.c2, m, gfma(-k.k1, it, k.k1));
-  const double v = y - gfma(beta[2], z3, gfma(beta[1], z2, beta[0]));  // y − Z[:,1:3]β[1:3]
-  double* s = mo.s;
-  s[S2] += z2;
-  s[S3] += z3;
-  s[S4] += z4;
-  s[G22] = gfma(z2, z2, s[G22]);
-  s[G23] = gfma(z2, z3, s[G23]);
-  s[G24] = gfma(z2, z4, s[G24]);
-  s[G33] = gfma(z3, z3, s[G33]);
-  s[G34] = gfma(z3, z4, s[G34]);
-  s[G44] = gfma(z4, z4, s[G44]);
-  s[U1] += v;
-  s[U2] = gfma(z2, v, s[U2]);
-  s[U3] = gfma(z3, v, s[U3]);
-  s[U4] = gfma(z4, v, s[U4]);
-  s[VV] = gfma(v, v, s[VV]);
+  Row r;
+  accum_stats(k.rl, k.k1, k.c2, beta, m, rm, z, y, mo.s, r);
+  const double it = r.it, z2 = r.z2, z3 = r.z3, z4 = r.z4, v = r.v;
   // derivatives with respect to β₄ (∂λ/∂β₄ = dl) …
   const double mzd = (m * z) * k.dl;
   const double e2 = (z - z2) * k.el;  // ∂Z₂/∂β₄
@@ -414,16 +396,7 @@ struct Step {
 
 YFM_GHD void primal_update(const Model& m, const State& s, const Moments& mo, int N, Step& u) {
   const double* st = mo.s;
-  u.G[0][0] = (double)N;
-  u.G[0][1] = u.G[1][0] = st[S2];
-  u.G[0][2] = u.G[2][0] = st[S3];
-  u.G[0][3] = u.G[3][0] = st[S4];
-  u.G[1][1] = st[G22];
-  u.G[1][2] = u.G[2][1] = st[G23];
-  u.G[1][3] = u.G[3][1] = st[G24];
-  u.G[2][2] = st[G33];
-  u.G[2][3] = u.G[3][2] = st[G34];
-  u.G[3][3] = st[G44];
+  tvl_gram(mo.s, N, u.G);
   u.u[0] = st[U1];
   u.u[1] = st[U2];
   u.u[2] = st[U3];

@@ -110,8 +110,3 @@ def assert_candidate(model, name, n, b, beta_s, V_s, C_s):
         missed = {what: e for what, e in errs.items() if not e[0] <= SR.REL}
         assert not missed, (name, n, b, missed)
     return errs
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))

@@ -1,0 +1,142 @@
+"""The shared checkers can fail: tests/grad_rule.py and the bit comparison of tests/gpu_scenarios.py on synthetic arrays
+(no fixture, no compiler, no GPU)."""
+from __future__ import annotations
+
+import numpy as np
+import pytest
+
+from gpu_scenarios import assert_same_bits, same_bits
+from grad_rule import REL, assert_candidate_rule, assert_gradient_rule, chain_factor
+from yfm_amd import KIND_DNS, KIND_TVL
+from yfm_amd.params import n_params, transform_params
+
+P, B = 4, 100
+
+
+def case():
+    """‖g_fd‖∞ = 4 for every candidate, row 2 exactly zero, everything compared; g = g_fd passes."""
+    g_fd = np.tile(np.array([4.0, 1.0, 0.0, -2.0])[:, None], (1, B))
+    return {"g_fd": g_fd, "e_fd": np.full(B, 1e-12), "compared": np.ones(B, dtype=bool),
+            "T_use": np.full(B, 10), "loglik_truth": np.full(B, -3.0), "ref_err": np.full(B, 1.0)}
+
+
+def test_rule_holds_at_the_bound_and_fails_one_ulp_above():
+    c = case()
+    bound = REL * 4.0 + c["e_fd"][7]
+    g = c["g_fd"].copy()
+    c["g_fd"][1, 7], g[1, 7] = bound, 0.0  # |g − g_fd| is the bound to the bit
+    assert_gradient_rule(g, c)
+    c["g_fd"][1, 7] = np.nextafter(bound, np.inf)
+    assert abs(g[1, 7] - c["g_fd"][1, 7]) > bound
+    with pytest.raises(AssertionError):
+        assert_gradient_rule(g, c)
+
+
+def test_rule_needs_three_quarters_compared():
+    c = case()
+    c["compared"][75:] = False
+    assert_gradient_rule(c["g_fd"].copy(), c)
+    c["compared"][74] = False
+    with pytest.raises(AssertionError):
+        assert_gradient_rule(c["g_fd"].copy(), c)
+
+
+def test_rule_wants_exact_zeros():
+    c = case()
+    g = c["g_fd"].copy()
+    g[2, 3] = 1e-300  # far inside the bound, but g_fd is 0.0 there
+    with pytest.raises(AssertionError):
+        assert_gradient_rule(g, c)
+    c["compared"][3] = False
+    assert_gradient_rule(g, c)
+
+
+def test_rule_checks_the_selection_it_is_given():
+    c = case()
+    g = c["g_fd"].copy()
+    g[0, 5] += 1.0
+    c["compared"][5] = False  # not compared: not checked …
+    assert_gradient_rule(g, c)
+    with pytest.raises(AssertionError):  # … unless the selection says so
+        assert_gradient_rule(g, c, sel=np.ones(B, dtype=bool))
+    c["compared"][5] = True
+    with pytest.raises(AssertionError):
+        assert_gradient_rule(g, c)
+    assert_gradient_rule(g, c, sel=np.arange(B) != 5)
+    hard = np.arange(B) == 5
+    assert_gradient_rule(g, c, second_clause=hard)  # err = 1 ≤ ref_err = 1
+    c["ref_err"][5] = 0.5
+    with pytest.raises(AssertionError):
+        assert_gradient_rule(g, c, second_clause=hard)
+
+
+def test_rule_extras_are_asserted_only_where_passed():
+    c = case()
+    c["T_use"][9], c["compared"][9] = 2, False
+    g = c["g_fd"].copy()
+    assert_gradient_rule(g, c)
+    with pytest.raises(AssertionError):
+        assert_gradient_rule(g, c, short_windows_zero=True)
+    ll = c["loglik_truth"] * (1 + 2e-9)
+    assert_gradient_rule(g, c, primal=ll, primal_asserted=False)
+    assert_gradient_rule(g, c, primal=c["loglik_truth"] * (1 + 5e-10))
+    with pytest.raises(AssertionError):
+        assert_gradient_rule(g, c, primal=ll)
+    ll = c["loglik_truth"].copy()
+    ll[9] = 0.0
+    assert_gradient_rule(g, c, primal=ll, primal_mask=c["compared"])
+
+
+def test_candidate_rule_wants_the_fixtures_nan_pattern():
+    g_fd = np.array([[4.0, np.nan], [1.0, np.nan]])
+    e_fd = np.array([1e-12, np.nan])
+    loss = np.array([2.0, -np.inf])
+    g = np.array([[4.0, np.nan], [1.0, np.nan], [9.0, np.nan]])  # a row past the fixture's leading ones
+    assert assert_candidate_rule(g, g_fd, e_fd, loss) == 0.0
+    bad = g.copy()
+    bad[:, 1] = 0.5  # a finite gradient where the fixture has NaN
+    with pytest.raises(AssertionError):
+        assert_candidate_rule(bad, g_fd, e_fd, loss)
+    bad = g.copy()
+    bad[2, 0] = np.nan  # NaN where the fixture is finite
+    with pytest.raises(AssertionError):
+        assert_candidate_rule(bad, g_fd, e_fd, loss)
+    with pytest.raises(AssertionError):
+        assert_candidate_rule(g, g_fd, e_fd, np.array([2.0, 2.0]))
+    bad = g.copy()
+    bad[1, 0] += 1e-8
+    with pytest.raises(AssertionError):
+        assert_candidate_rule(bad, g_fd, e_fd, loss)
+
+
+@pytest.mark.parametrize("kind", [KIND_DNS, KIND_TVL])
+def test_chain_factor_is_the_transforms_derivative(kind):
+    """The index tables against central differences of transform_params at a random θ: its Jacobian is diagonal and
+    the diagonal is chain_factor."""
+    n = n_params(kind)
+    th = np.random.default_rng(kind).normal(scale=0.5, size=n)
+    h = 1e-5
+    J = np.empty((n, n))
+    for i in range(n):
+        up, dn = th.copy(), th.copy()
+        up[i] += h
+        dn[i] -= h
+        J[:, i] = (transform_params(kind, up) - transform_params(kind, dn)) / (up[i] - dn[i])
+    f = chain_factor(kind, transform_params(kind, th))
+    assert np.all(np.abs(J - np.diag(f)) <= 1e-6 * np.abs(f).max())
+    assert np.all(np.abs(np.diag(J) - f) <= 1e-6 * np.abs(f))
+
+
+def test_bit_comparison():
+    nan1 = np.array([0x7FF8000000000000], dtype=np.uint64).view(np.float64)
+    nan2 = np.array([0x7FF8000000000001], dtype=np.uint64).view(np.float64)
+    assert np.isnan(nan1).all() and np.isnan(nan2).all()
+    assert same_bits(nan1, nan1.copy()) and not same_bits(nan1, nan2)
+    assert same_bits([0.0, 1.5], [0.0, 1.5]) and not same_bits([0.0], [-0.0])
+    assert not same_bits(np.zeros(2), np.zeros((2, 1)))
+    for a, b in ((nan1, nan2), ([0.0], [-0.0])):
+        assert_same_bits(a, b, nan_payloads=False)
+        with pytest.raises(AssertionError):
+            assert_same_bits(a, b)
+    with pytest.raises(AssertionError):
+        assert_same_bits([1.0], [2.0], nan_payloads=False)

@@ -27,7 +27,7 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT
+from host_check_io import build_host_check
 
 MARGIN = 4.0
 GEOMEAN = 1.25
@@ -36,11 +36,7 @@ FLOOR = 2.0 ** -52
 
 @pytest.fixture(scope="module")
 def lines(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("fixedz_mean") / "fixedz_mean_host_check"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    f"-I{ROOT / 'tools' / 'host_fixedz' / 'stub'}", f"-I{ROOT / 'yieldfactormodels.jl_amd' / 'csrc'}",
-                    str(ROOT / "tests" / "fixedz_mean_host_check.cpp"), "-o", str(exe), "-lquadmath"], check=True)
+    exe = build_host_check(tmp_path_factory, "fixedz_mean_host_check", sanitize=True)
     out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
     rows = [ln.split() for ln in out.splitlines() if ln.startswith("case ")]
     return [(int(r[1]), float(r[2]), r[3], float(r[4]), float(r[5]), float(r[6])) for r in rows]

@@ -22,6 +22,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from gpu_scenarios import assert_batch_independent
+from grad_rule import assert_gradient_rule
 from test_gpu_parity import assert_parity
 from yfm_amd import KIND_DNS
 
@@ -30,31 +32,10 @@ import make_grad_long as ML  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-REL = 1e-9
-
 
 @pytest.fixture(scope="module")
 def cases():
     return ML.load_cases()
-
-
-def rule(name, c, g, sel, second_clause=None):
-    """The rule over the candidates of `sel` (a mask); the maxima are printed before anything is asserted."""
-    gn = np.abs(c["g_fd"]).max(axis=0)
-    err = np.abs(g - c["g_fd"]).max(axis=0)
-    bound = REL * gn + c["e_fd"]
-    nz = sel & (gn > 0)
-    print(f"case {name}: compared {int(c['compared'].sum())}/{sel.size}, checked {int(sel.sum())}, max err/bound "
-          f"{np.max(err[nz] / bound[nz]):.3e}, max err/|g| {np.max(err[nz] / gn[nz]):.3e}")
-    ok = err <= bound
-    if second_clause is not None:
-        for b in np.flatnonzero(second_clause & sel):
-            print(f"case {name}: hard candidate {b}: err/|g| {err[b] / gn[b]:.3e}, err/bound {err[b] / bound[b]:.3e}, "
-                  f"plain FP64 reference's err/|g| {c['ref_err'][b] / gn[b]:.3e}")
-        ok = ok | (second_clause & (err <= c["ref_err"]))
-    assert np.all(ok[sel]), (np.flatnonzero(sel & ~ok), (err / gn)[sel & ~ok])
-    zero = (c["g_fd"] == 0.0) & sel[None, :]
-    assert np.all(g[zero] == 0.0)
 
 
 @pytest.mark.parametrize("name", ["L", "L-windows", "L-n64"])
@@ -62,8 +43,7 @@ def test_gradient_matches_truth_differences(engine, cases, name):
     c = cases[name]
     engine.set_panel(c["Y"], c["maturities"])
     ll, g = engine.loglik_grad(KIND_DNS, c["Theta"], space=0, T_use=c["T_use"])
-    assert c["compared"].mean() >= 0.75
-    rule(name, c, g, c["compared"])
+    assert_gradient_rule(g, c, label=f"case {name}")
     assert_parity(ll, c["loglik_oracle"], c["loglik_truth"])
     assert engine.last_grad_unavailable() == 0
 
@@ -76,7 +56,7 @@ def test_hard_candidates(engine, cases):
     assert c["compared"].mean() >= 0.75 and np.isfinite(c["ref_err"][c["hard"]]).all()
     engine.set_panel(c["Y"], c["maturities"])
     ll, g = engine.loglik_grad(KIND_DNS, c["Theta"], space=0, T_use=c["T_use"])
-    rule("L-hard", c, g, c["compared"], second_clause=c["hard"])
+    assert_gradient_rule(g, c, label="case L-hard", second_clause=c["hard"])
     assert_parity(ll, c["loglik_oracle"], c["loglik_truth"])
     assert engine.last_grad_unavailable() == 0
 
@@ -95,7 +75,7 @@ def test_band_below_the_deferral_threshold(engine, cases):
     assert engine.last_grad_unavailable() == int((~have).sum()) == engine.last_deferred()
     np.testing.assert_array_equal(ll, engine.loglik(KIND_DNS, c["Theta"], space=0, T_use=c["T_use"]))
     assert np.all(c["compared"][k1 <= 5e5])
-    rule("L-band", c, g, c["compared"] & have)
+    assert_gradient_rule(g, c, label="case L-band", sel=c["compared"] & have)
     assert_parity(ll, c["loglik_oracle"], c["loglik_truth"])
 
 
@@ -104,11 +84,5 @@ def test_outputs_do_not_depend_on_the_batch(engine, cases):
     c = cases["L"]
     engine.set_panel(c["Y"], c["maturities"])
     Th = c["Theta"]
-    ll, g = engine.loglik_grad(KIND_DNS, Th)
-    l1, g1 = engine.loglik_grad(KIND_DNS, Th[:, 47])
-    llr, gr = engine.loglik_grad(KIND_DNS, np.asfortranarray(Th[:, ::-1]))
+    ll, g = assert_batch_independent(lambda X: engine.loglik_grad(KIND_DNS, X), Th, [47])
     assert np.isfinite(g[:, 47]).all()
-    np.testing.assert_array_equal(l1[0], ll[47])
-    np.testing.assert_array_equal(g1[:, 0], g[:, 47])
-    np.testing.assert_array_equal(llr[::-1], ll)
-    np.testing.assert_array_equal(gr[:, ::-1], g)

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import msed_reference as R
+from gpu_scenarios import assert_device_entry_matches
 from yfm_amd import _lib
 from yfm_amd import models as M
 from yfm_amd import params as P
@@ -282,24 +283,13 @@ def test_batch_independence(engine, lanes_env, kind, N):
 
 
 def test_device_entry_point(engine):
-    import torch
     N, T = 30, 40
     mats, Y = mats_for(N), panel_for(N, T)
     engine.set_panel(Y, mats)
     for kind in KINDS:
         Th = theta_for(kind, 0)[:, :70]
         tu = (np.arange(70) % 40 + 1).astype(np.int32)
-        host = engine.loglik(kind, Th, space=0, T_use=tu).copy()
-        d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
-        d_tu = torch.from_numpy(tu).cuda()
-        d_out = torch.empty(70, dtype=torch.float64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            engine.loglik_device(kind, d_th.data_ptr(), Th.shape[0], 70, d_out.data_ptr(), space=0,
-                                 d_T_use=d_tu.data_ptr(), stream=s.cuda_stream)
-        s.synchronize()
-        np.testing.assert_array_equal(d_out.cpu().numpy(), host)
-        torch.cuda.synchronize()
+        assert_device_entry_matches(engine.loglik, engine.loglik_device, kind, Th, tu, space=0)
 
 
 @pytest.mark.parametrize("kind", [4, 5, 6, 8])

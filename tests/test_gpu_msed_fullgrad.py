@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from gpu_scenarios import assert_device_entry_matches, same_bits
+from grad_rule import REL, assert_candidate_rule as check_gradient
 from yfm_amd import _lib
 from yfm_amd import models as M
 from yfm_amd import params as P
@@ -27,7 +29,6 @@ import make_msed_fullgrad as MF  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 KINDS = MF.KINDS
-REL = 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -42,23 +43,6 @@ def lanes_env():
     os.environ.pop("YFM_MSED_LANES", None)
     if old is not None:
         os.environ["YFM_MSED_LANES"] = old
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def check_gradient(g, g_fd, e_fd, loss, label=""):
-    for b in range(g.shape[1]):
-        if np.isnan(g_fd[:, b]).any():
-            assert np.isneginf(loss[b]) and np.isnan(g[:, b]).all(), (label, b, loss[b], g[:, b])
-            continue
-        assert np.isfinite(loss[b]) and np.isfinite(g[:, b]).all(), (label, b, loss[b], g[:, b])
-        err = np.max(np.abs(g[:, b] - g_fd[:, b]))
-        bound = REL * np.max(np.abs(g_fd[:, b])) + e_fd[b]
-        print(f"{label} b={b}: max|g - g_fd| = {err:.3e}, bound {bound:.3e}")
-        assert err <= bound, (label, b, err, bound)
 
 
 @pytest.mark.parametrize("lanes", ["4", "16"])
@@ -161,26 +145,13 @@ def test_window_without_a_compared_column(engine, cases):
 
 def test_device_entry_point(engine, cases):
     """The _device entry on a side stream equals the synchronous one bit for bit (windows of every length)."""
-    import torch
     for kind in KINDS:
         name = f"k{kind}_n30t8"
         engine.set_panel(cases[f"{name}_Y"], cases[f"{name}_maturities"])
         Th = S.theta_batch(kind, 70, scale=0.1, seed=500 + kind, bad_frac=0.0)
-        Pn = Th.shape[0]
         tu = (np.arange(70) % 8 + 1).astype(np.int32)
-        loss, g = engine.lambda_loss_full_grad(kind, Th, space=0, T_use=tu)
-        d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
-        d_tu = torch.from_numpy(tu).cuda()
-        d_out = torch.empty(70, dtype=torch.float64, device="cuda")
-        d_g = torch.empty((70, Pn), dtype=torch.float64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            engine.lambda_loss_full_grad_device(kind, d_th.data_ptr(), Pn, 70, d_out.data_ptr(), d_g.data_ptr(),
-                                                space=0, d_T_use=d_tu.data_ptr(), stream=s.cuda_stream)
-        s.synchronize()
-        assert same_bits(d_out.cpu().numpy(), loss)
-        assert same_bits(d_g.cpu().numpy().T, g)
-        torch.cuda.synchronize()
+        assert_device_entry_matches(engine.lambda_loss_full_grad, engine.lambda_loss_full_grad_device, kind, Th, tu,
+                                    space=0)
 
 
 def test_model_layer_and_unsupported_kinds(engine, cases):

@@ -16,7 +16,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
-from test_gpu_msed_fullgrad import check_gradient, lanes_env, same_bits  # noqa: F401  (lanes_env is a fixture)
+from gpu_scenarios import same_bits
+from grad_rule import assert_candidate_rule as check_gradient
+from test_gpu_msed_fullgrad import lanes_env  # noqa: F401  (lanes_env is a fixture)
 
 sys.path.insert(0, str(GOLDEN / "msed_fullgrad"))
 import make_msed_fullgrad_long as ML  # noqa: E402

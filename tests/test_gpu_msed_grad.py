@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from gpu_scenarios import assert_device_entry_matches
+from grad_rule import REL, assert_candidate_rule as check_gradient
 from yfm_amd import _lib
 from yfm_amd import models as M
 from yfm_amd import params as P
@@ -26,24 +28,11 @@ pytestmark = pytest.mark.gpu
 
 KINDS = MG.KINDS
 CODE = {3: "NS", 4: "SD-NS", 5: "RWSD-NS", 6: "SSD-NS", 8: "SRWSD-NS"}
-REL = 1e-9
 
 
 @pytest.fixture(scope="module")
 def cases():
     return MG.load_cases()
-
-
-def check_gradient(g, g_fd, e_fd, loss, label=""):
-    for b in range(g.shape[1]):
-        if np.isnan(g_fd[:, b]).any():
-            assert np.isneginf(loss[b]) and np.isnan(g[:, b]).all(), (label, b, loss[b], g[:, b])
-            continue
-        assert np.isfinite(loss[b]) and np.isfinite(g[:, b]).all(), (label, b, loss[b], g[:, b])
-        err = np.max(np.abs(g[:, b] - g_fd[:, b]))
-        bound = REL * np.max(np.abs(g_fd[:, b])) + e_fd[b]
-        print(f"{label} b={b}: max|g - g_fd| = {err:.3e}, bound {bound:.3e}")
-        assert err <= bound, (label, b, err, bound)
 
 
 @pytest.mark.parametrize("space", [0, 1])
@@ -137,7 +126,6 @@ def test_neg_inf_candidate_has_no_gradient(engine, cases):
 
 
 def test_device_entry_point(engine):
-    import torch
     N, T = 30, 40
     mats = mats_for(N)
     Y = S.simulate_panel(P.KIND_SD_NS, T, maturities=mats, seed=7)
@@ -145,19 +133,7 @@ def test_device_entry_point(engine):
     for kind in KINDS:
         Th = S.theta_batch(kind, 70, scale=0.1, seed=500 + kind, bad_frac=0.0)
         tu = (np.arange(70) % 40 + 1).astype(np.int32)
-        loss, g = engine.lambda_loss_grad(kind, Th, space=0, T_use=tu)
-        d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
-        d_tu = torch.from_numpy(tu).cuda()
-        d_out = torch.empty(70, dtype=torch.float64, device="cuda")
-        d_g = torch.empty((70, 12), dtype=torch.float64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            engine.lambda_loss_grad_device(kind, d_th.data_ptr(), Th.shape[0], 70, d_out.data_ptr(), d_g.data_ptr(),
-                                           space=0, d_T_use=d_tu.data_ptr(), stream=s.cuda_stream)
-        s.synchronize()
-        np.testing.assert_array_equal(d_out.cpu().numpy(), loss)
-        np.testing.assert_array_equal(d_g.cpu().numpy().T, g)
-        torch.cuda.synchronize()
+        assert_device_entry_matches(engine.lambda_loss_grad, engine.lambda_loss_grad_device, kind, Th, tu, space=0)
 
 
 def test_model_layer_and_unsupported_kinds(engine, cases):

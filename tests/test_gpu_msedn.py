@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from gpu_scenarios import assert_device_entry_matches
 
 import msedn_reference as R
 from oracle import optim_nm as NM
@@ -315,23 +316,12 @@ def test_nm_block_equals_sequential_nelder_mead(engine):
 
 
 def test_device_entry_point(engine):
-    import torch
     N, T = 30, 40
     engine.set_panel(panel_for(N, T), mats_for(N))
     for kind in (R.KIND_NNS, R.sd_kind(2, False, True)):
         Th = theta_for(kind, 0)[:, :70]
         tu = (np.arange(70) % 40 + 1).astype(np.int32)
-        host = engine.loglik(kind, Th, space=0, T_use=tu).copy()
-        d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
-        d_tu = torch.from_numpy(tu).cuda()
-        d_out = torch.empty(70, dtype=torch.float64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            engine.loglik_device(kind, d_th.data_ptr(), Th.shape[0], 70, d_out.data_ptr(), space=0,
-                                 d_T_use=d_tu.data_ptr(), stream=s.cuda_stream)
-        s.synchronize()
-        np.testing.assert_array_equal(d_out.cpu().numpy(), host)
-        torch.cuda.synchronize()
+        assert_device_entry_matches(engine.loglik, engine.loglik_device, kind, Th, tu, space=0)
 
 
 def test_unsupported_requests(engine, lanes_env):

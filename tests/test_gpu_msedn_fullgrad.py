@@ -16,6 +16,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from gpu_scenarios import assert_device_entry_matches, same_bits
+from grad_rule import REL, assert_candidate_rule as check_leading
 from yfm_amd import _lib
 from yfm_amd import models as M
 from yfm_amd import params as P
@@ -31,7 +33,6 @@ import make_msedn_grad as MG  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 KINDS = MF.kinds()
-REL = 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -50,26 +51,8 @@ def env():
             os.environ[k] = old[k]
 
 
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
 def kind_of(name: str) -> int:
     return int(name[1:name.index("_")])
-
-
-def check_leading(g, g_fd, e_fd, loss, label=""):
-    nl = g_fd.shape[0]
-    for b in range(g.shape[1]):
-        if np.isnan(g_fd[:, b]).any():
-            assert np.isneginf(loss[b]) and np.isnan(g[:, b]).all(), (label, b, loss[b], g[:, b])
-            continue
-        assert np.isfinite(loss[b]) and np.isfinite(g[:, b]).all(), (label, b, loss[b], g[:, b])
-        err = np.max(np.abs(g[:nl, b] - g_fd[:, b]))
-        bound = REL * np.max(np.abs(g_fd[:, b])) + e_fd[b]
-        print(f"{label} b={b}: max|g - g_fd| = {err:.3e}, bound {bound:.3e}")
-        assert err <= bound, (label, b, err, bound)
 
 
 @pytest.mark.parametrize("lanes", ["4", "16"])
@@ -182,26 +165,13 @@ def test_window_without_a_compared_column(engine, cases):
 
 def test_device_entry_point(engine):
     """The _device entry on a side stream equals the synchronous one bit for bit (windows of every length)."""
-    import torch
     N, T = 33, 8
     engine.set_panel(MN.panel_for(N, T), MN.mats_for(N))
     for kind in KINDS:
         Th = np.asfortranarray(MN.theta_for(kind, 0)[:, :70])
-        Pn = Th.shape[0]
         tu = (np.arange(70) % 8 + 1).astype(np.int32)
-        loss, g = engine.neural_loss_full_grad(kind, Th, space=0, T_use=tu)
-        d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
-        d_tu = torch.from_numpy(tu).cuda()
-        d_out = torch.empty(70, dtype=torch.float64, device="cuda")
-        d_g = torch.empty((70, Pn), dtype=torch.float64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            engine.neural_loss_full_grad_device(kind, d_th.data_ptr(), Pn, 70, d_out.data_ptr(), d_g.data_ptr(),
-                                                space=0, d_T_use=d_tu.data_ptr(), stream=s.cuda_stream)
-        s.synchronize()
-        assert same_bits(d_out.cpu().numpy(), loss)
-        assert same_bits(d_g.cpu().numpy().T, g)
-        torch.cuda.synchronize()
+        assert_device_entry_matches(engine.neural_loss_full_grad, engine.neural_loss_full_grad_device, kind, Th, tu,
+                                    space=0)
 
 
 def test_model_layer_and_unsupported_kinds(engine, cases):

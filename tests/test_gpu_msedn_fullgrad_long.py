@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from gpu_scenarios import same_bits
 
 sys.path.insert(0, str(GOLDEN / "msedn_fullgrad"))
 import make_msedn_fullgrad_long as ML  # noqa: E402
@@ -33,11 +34,6 @@ def lanes_env():
     os.environ.pop("YFM_MSED_LANES", None)
     if old is not None:
         os.environ["YFM_MSED_LANES"] = old
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
 def kind_of(name: str) -> int:

@@ -14,6 +14,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN
+from gpu_scenarios import assert_device_entry_matches
+from grad_rule import assert_candidate_rule as check_gradient
 from yfm_amd import _lib
 from yfm_amd import models as M
 from yfm_amd import params as P
@@ -27,7 +29,6 @@ import make_msedn_grad as MG  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 KINDS = MG.kinds()
-REL = 1e-9
 
 
 @pytest.fixture(scope="module")
@@ -37,23 +38,6 @@ def cases():
 
 def kind_of(name: str) -> int:
     return int(name[1:name.index("_")])
-
-
-def check_gradient(g, g_fd, e_fd, loss, label=""):
-    """The rule per candidate (column).  Returns the worst error relative to ‖g_fd‖∞."""
-    worst = 0.0
-    for b in range(g.shape[1]):
-        if np.isnan(g_fd[:, b]).any():
-            assert np.isneginf(loss[b]) and np.isnan(g[:, b]).all(), (label, b, loss[b], g[:, b])
-            continue
-        assert np.isfinite(loss[b]) and np.isfinite(g[:, b]).all(), (label, b, loss[b], g[:, b])
-        err = np.max(np.abs(g[:, b] - g_fd[:, b]))
-        scale = np.max(np.abs(g_fd[:, b]))
-        bound = REL * scale + e_fd[b]
-        print(f"{label} b={b}: max|g - g_fd| = {err:.3e}, bound {bound:.3e}, relative {err / scale:.3e}")
-        assert err <= bound, (label, b, err, bound)
-        worst = max(worst, err / scale)
-    return worst
 
 
 @pytest.mark.parametrize("space", [0, 1])
@@ -117,26 +101,13 @@ def test_batch_independence(engine, lanes_env, kind, N):
 
 def test_device_entry_point(engine):
     """The device-pointer call on a stream of its own writes the host-pointer call's bits."""
-    import torch
     N, T = 30, 40
     mats, Y = MN.mats_for(N), MN.panel_for(N, T)
     engine.set_panel(Y, mats)
     for kind in KINDS:
         Th = np.asfortranarray(MN.theta_for(kind, 0)[:, :70])
         tu = (np.arange(70) % 40 + 1).astype(np.int32)
-        loss, g = engine.neural_loss_grad(kind, Th, space=0, T_use=tu)
-        d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
-        d_tu = torch.from_numpy(tu).cuda()
-        d_out = torch.empty(70, dtype=torch.float64, device="cuda")
-        d_g = torch.empty((70, 12), dtype=torch.float64, device="cuda")
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            engine.neural_loss_grad_device(kind, d_th.data_ptr(), Th.shape[0], 70, d_out.data_ptr(), d_g.data_ptr(),
-                                           space=0, d_T_use=d_tu.data_ptr(), stream=s.cuda_stream)
-        s.synchronize()
-        np.testing.assert_array_equal(d_out.cpu().numpy(), loss)
-        np.testing.assert_array_equal(d_g.cpu().numpy().T, g)
-        torch.cuda.synchronize()
+        assert_device_entry_matches(engine.neural_loss_grad, engine.neural_loss_grad_device, kind, Th, tu, space=0)
 
 
 def test_model_layer_and_refusals(engine, cases):

@@ -18,9 +18,9 @@ import sys
 
 import numpy as np
 import pytest
-import torch
 
 from conftest import GOLDEN
+from gpu_scenarios import assert_device_entry_matches
 from yfm_amd import KIND_DNS, KIND_GNS, KIND_TVL, _lib
 from yfm_amd import synthetic as S
 from yfm_amd.params import KIND_NNS, KIND_SD_NS, n_params, transform_params
@@ -152,21 +152,7 @@ def test_a_deferred_candidate_has_nan_scores_and_is_counted(engine):
 def test_device_entry_point_on_a_side_stream(engine, small):
     Y, m, Th, tu = small
     engine.set_panel(Y, m)
-    P, B = Th.shape
-    T = Y.shape[1]
-    ll, Sc = engine.loglik_scores(KIND_DNS, Th, T_use=tu)
-    d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
-    d_tu = torch.from_numpy(tu).cuda()
-    d_ll = torch.empty(B, dtype=torch.float64, device="cuda")
-    d_s = torch.full((B, T - 1, P), 7.0, dtype=torch.float64, device="cuda")  # the P×(T−1)×B array, column-major
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        engine.loglik_scores_device(KIND_DNS, d_th.data_ptr(), P, B, d_ll.data_ptr(), d_s.data_ptr(),
-                                    d_T_use=d_tu.data_ptr(), stream=s.cuda_stream)
-    s.synchronize()
-    np.testing.assert_array_equal(d_ll.cpu().numpy(), ll)
-    np.testing.assert_array_equal(d_s.cpu().numpy().transpose(2, 1, 0), Sc)
+    assert_device_entry_matches(engine.loglik_scores, engine.loglik_scores_device, KIND_DNS, Th, tu)
 
 
 def test_other_kinds_are_refused(engine, small):

@@ -12,15 +12,11 @@ import pytest
 
 import smooth_fixture as SF
 import smoother_reference as SR
+from gpu_scenarios import same_bits
 from yfm_amd import KIND_DNS, KIND_NNS, KIND_SD_NS, KIND_TVL, _lib, n_params
 from yfm_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
 def n30(engine):

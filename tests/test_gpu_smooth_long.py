@@ -21,7 +21,7 @@ import pytest
 
 import smooth_long_fixture as LF
 import smoother_reference as SR
-from smooth_long_fixture import same_bits
+from gpu_scenarios import same_bits
 
 pytestmark = pytest.mark.gpu
 

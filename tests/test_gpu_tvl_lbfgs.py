@@ -24,6 +24,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+from grad_rule import SPACE_ROWS
 from yfm_amd import KIND_TVL, create_model, estimate_, estimate_lbfgs_batch
 from yfm_amd import synthetic as S
 from yfm_amd.params import transform_params
@@ -32,7 +33,7 @@ pytestmark = pytest.mark.gpu
 
 LL_THETA0, LL_OPT = 368.0633, 398.5098
 OPTS = dict(g_tol=1e-4, f_abstol=0.0)
-POS, R11 = [0, 1, 3, 6, 10], [15, 20, 25, 30]
+POS, R11 = (list(rows) for rows in SPACE_ROWS[KIND_TVL][:2])
 
 
 @pytest.fixture(scope="module")

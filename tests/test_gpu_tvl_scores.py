@@ -21,9 +21,9 @@ import sys
 
 import numpy as np
 import pytest
-import torch
 
 from conftest import GOLDEN
+from gpu_scenarios import assert_device_entry_matches
 from yfm_amd import KIND_DNS, KIND_GNS, KIND_TVL, _lib
 from yfm_amd import synthetic as S
 from yfm_amd.params import KIND_NNS, KIND_SD_NS, n_params, transform_params
@@ -149,25 +149,9 @@ def test_unavailable_candidates_are_nan_in_all_of_s(engine, small):
 def test_device_entry_point_on_a_side_stream_leaves_the_guards_alone(engine, small):
     Y, m, Th = small
     engine.set_panel(Y, m)
-    P, B = Th.shape
     T = Y.shape[1]
     tu = np.array([T, 1, 2, 3, 7, T, T - 1, 4, T], dtype=np.int32)
-    ll, Sc = engine.tvl_loglik_scores(KIND_TVL, Th, T_use=tu)
-    d_th = torch.from_numpy(np.ascontiguousarray(Th.T)).cuda()
-    d_tu = torch.from_numpy(tu).cuda()
-    d_ll = torch.empty(B, dtype=torch.float64, device="cuda")
-    n, guard = B * (T - 1) * P, 64
-    d_buf = torch.full((n + 2 * guard,), 7.0, dtype=torch.float64, device="cuda")
-    s = torch.cuda.Stream()
-    s.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(s):
-        engine.tvl_loglik_scores_device(KIND_TVL, d_th.data_ptr(), P, B, d_ll.data_ptr(),
-                                        d_buf.data_ptr() + 8 * guard, d_T_use=d_tu.data_ptr(), stream=s.cuda_stream)
-    s.synchronize()
-    buf = d_buf.cpu().numpy()
-    assert np.all(buf[:guard] == 7.0) and np.all(buf[guard + n:] == 7.0)
-    np.testing.assert_array_equal(d_ll.cpu().numpy(), ll)
-    np.testing.assert_array_equal(buf[guard:guard + n].reshape(B, T - 1, P).transpose(2, 1, 0), Sc)
+    assert_device_entry_matches(engine.tvl_loglik_scores, engine.tvl_loglik_scores_device, KIND_TVL, Th, tu, guard=64)
 
 
 def test_other_kinds_are_refused_by_the_c_entry_points(engine, small):

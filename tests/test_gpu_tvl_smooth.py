@@ -14,17 +14,13 @@ import pytest
 import tvl_smooth_fixture as TF
 import tvl_smoother_reference as TR
 from conftest import GOLDEN
+from gpu_scenarios import same_bits
 from yfm_amd import KIND_DNS, KIND_NNS, KIND_SD_NS, KIND_TVL, _lib, n_params
 from yfm_amd import synthetic as S
 
 pytestmark = pytest.mark.gpu
 
 MODES = (_lib.PREC_CERTIFIED, _lib.PREC_FP64)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
 
 
 @pytest.fixture

@@ -19,7 +19,7 @@ import pytest
 
 import smooth_long_fixture as LF
 import tvl_smoother_reference as TR
-from smooth_long_fixture import same_bits
+from gpu_scenarios import same_bits
 from test_gpu_tvl_smooth import MODES
 from yfm_amd import KIND_TVL
 

@@ -8,70 +8,30 @@ The estimation-length cases of grad_long_cases.npz (T up to 600, make_grad_long.
 """
 from __future__ import annotations
 
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from grad_rule import REL, assert_gradient_rule, chain_factor
+from host_check_io import build_host_check, run_grad_host as run_host
 
 sys.path.insert(0, str(GOLDEN / "grad"))
 import make_grad as MG  # noqa: E402
 import make_grad_long as ML  # noqa: E402
 
-REL = 1e-9
-
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("grad") / "grad_host_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    str(ROOT / "tests" / "grad_host_check.cpp"), "-o", str(exe)], check=True)
-    return exe
-
-
-def hexf(v) -> str:
-    return "nan" if v != v else float(v).hex()
-
-
-def run_host(exe, tmp_path, Y, m, Th, tu, space=0):
-    N, T = Y.shape
-    B = Th.shape[1]
-    words = [str(N), str(T), str(B), str(space)]
-    words += [hexf(v) for v in m]
-    words += [hexf(v) for v in np.asarray(Y).reshape(-1, order="F")]
-    for b in range(B):
-        words.append(str(int(tu[b])))
-        words += [hexf(v) for v in Th[:, b]]
-    path = tmp_path / "case.txt"
-    path.write_text(" ".join(words))
-    out = subprocess.run([str(exe), str(path)], check=True, capture_output=True, text=True).stdout.split("\n")
-    rows = np.array([[float.fromhex(v) if "0x" in v else float(v) for v in line.split()] for line in out[:B]])
-    return rows[:, 0], rows[:, 1:].T
-
-
-def check_case(c, ll, g):
-    cmp_ = c["compared"]
-    assert cmp_.mean() >= 0.75
-    gn = np.abs(c["g_fd"]).max(axis=0)
-    err = np.abs(g - c["g_fd"]).max(axis=0)
-    bound = REL * gn + c["e_fd"]
-    print("max err / bound over the compared:", np.max(err[cmp_] / np.maximum(bound[cmp_], 1e-300)),
-          "max err / |g|:", np.max(err[cmp_] / np.maximum(gn[cmp_], 1e-300)))
-    assert np.all(err[cmp_] <= bound[cmp_]), (err[cmp_] / gn[cmp_]).max()
-    zero = c["g_fd"] == 0.0
-    assert np.all(g[zero & cmp_[None, :]] == 0.0)
-    fin = np.isfinite(c["loglik_truth"])
-    den = np.maximum(np.abs(c["loglik_truth"][fin]), 1e-300)
-    assert np.all(np.abs(ll[fin] - c["loglik_truth"][fin]) / den <= REL)
+    return build_host_check(tmp_path_factory, "grad_host_check")
 
 
 @pytest.mark.parametrize("name", ["B", "E"])
 def test_host_gradient_matches_truth_differences(harness, tmp_path, name):
     c = MG.load_cases()[name]
     ll, g = run_host(harness, tmp_path, c["Y"], c["maturities"], c["Theta"], c["T_use"])
-    check_case(c, ll, g)
+    assert_gradient_rule(g, c, label=f"case {name}", primal=ll)
 
 
 def check_long_case(name, c, ll, g):
@@ -79,28 +39,14 @@ def check_long_case(name, c, ll, g):
     candidate of L-hard (the dense FP64 oracle's own loglik is more than 1e-9 from the truth) may instead be as close
     to the truth as the plain FP64 reference gradient, err ≤ ref_err; the host build has no deferral, so the L-band
     candidates with a stored κ₁(Z'Z) ≥ 5e5 are left to the GPU test."""
-    cmp_ = c["compared"]
-    assert cmp_.mean() >= 0.75
-    sel = cmp_ & (c["kappa1"] < 5e5) if name == "L-band" else cmp_
-    gn = np.abs(c["g_fd"]).max(axis=0)
-    err = np.abs(g - c["g_fd"]).max(axis=0)
-    bound = REL * gn + c["e_fd"]
-    print(f"case {name}: checked {int(sel.sum())}/{sel.size}, max err / bound {np.max(err[sel] / bound[sel]):.3e}, "
-          f"max err / |g| {np.max(err[sel] / gn[sel]):.3e}")
-    ok = err <= bound
+    sel = c["compared"] & (c["kappa1"] < 5e5) if name == "L-band" else c["compared"]
+    hard = None
     if name == "L-hard":
         assert c["hard"].tolist() == [True, True, True, True, False, False]
-        for b in np.flatnonzero(c["hard"]):
-            print(f"hard candidate {b}: err / |g| {err[b] / gn[b]:.3e}, err / bound {err[b] / bound[b]:.3e}, "
-                  f"plain FP64 reference's err / |g| {c['ref_err'][b] / gn[b]:.3e}")
-        ok = ok | (c["hard"] & (err <= c["ref_err"]))
-    assert np.all(ok[sel]), (np.flatnonzero(sel & ~ok), (err / gn)[sel & ~ok])
-    assert np.all(g[(c["g_fd"] == 0.0) & sel[None, :]] == 0.0)
+        hard = c["hard"]
     # the recursion's own FP64 value: held to the bar where the dense FP64 oracle is inside it too
-    fin = np.isfinite(c["loglik_truth"]) & sel & ~c["hard"]
-    rel = np.abs(ll[fin] - c["loglik_truth"][fin]) / np.maximum(np.abs(c["loglik_truth"][fin]), 1e-300)
-    print(f"FP64 primal: max |ll − truth| / |truth| over the candidates that are not hard {rel.max():.3e}")
-    assert np.all(rel <= REL)
+    assert_gradient_rule(g, c, label=f"case {name}", sel=sel, second_clause=hard, primal=ll,
+                         primal_mask=sel & ~c["hard"])
 
 
 @pytest.mark.parametrize("name", ML.CASE_NAMES)
@@ -119,9 +65,5 @@ def test_host_chain_rule(harness, tmp_path):
     Tc = np.stack([transform_params(KIND_DNS, Th[:, b]) for b in range(Th.shape[1])], axis=1)
     _, g0 = run_host(harness, tmp_path, c["Y"], c["maturities"], Th, c["T_use"], 0)
     _, g1 = run_host(harness, tmp_path, c["Y"], c["maturities"], Tc, c["T_use"], 1)
-    f = np.ones_like(Tc)
-    for i in (1, 2, 4, 7):
-        f[i] = Tc[i]
-    for i in (11, 15, 19):
-        f[i] = (1.0 - Tc[i] ** 2) / 2.0
+    f = chain_factor(KIND_DNS, Tc)
     assert np.all(np.abs(g0 - g1 * f).max(axis=0) <= REL * np.abs(g0).max(axis=0))

@@ -62,6 +62,14 @@ def _kernel_metadata(tmp_path):
     return meta
 
 
+def only(meta, fragment):
+    """The metadata of the one kernel whose symbol holds `fragment`."""
+    hits = [(n, m) for n, m in meta.items() if fragment in n]
+    assert len(hits) == 1, sorted(meta)
+    print(*hits[0])
+    return hits[0][1]
+
+
 @pytest.mark.skipif(not LIB.exists() or not READELF.exists(), reason="in-tree library or llvm-readelf missing")
 def test_hot_kernels_within_register_budget(tmp_path):
     meta = _kernel_metadata(tmp_path)

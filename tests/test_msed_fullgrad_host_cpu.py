@@ -7,73 +7,29 @@ a −Inf loss comes with P NaNs, exactly where the fixture has them.  The N = 30
 (make_msed_fullgrad_long.py) run through the same program."""
 from __future__ import annotations
 
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from grad_rule import assert_candidate_rule as check_gradient
+from gpu_scenarios import same_bits
+from host_check_io import build_host_check, run_fullgrad_host as run_host
 
 sys.path.insert(0, str(GOLDEN / "msed_fullgrad"))
 import make_msed_fullgrad as MF  # noqa: E402
 import make_msed_fullgrad_long as MFL  # noqa: E402
 
-REL = 1e-9
-
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("msed_fullgrad") / "msed_fullgrad_host_check"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    str(ROOT / "tests" / "msed_fullgrad_host_check.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_host_check(tmp_path_factory, "msed_fullgrad_host_check", sanitize=True)
 
 
 @pytest.fixture(scope="module")
 def cases():
     return MF.load_cases()
-
-
-def hexf(v) -> str:
-    return "nan" if v != v else float(v).hex()
-
-
-def run_host(exe, tmp_path, kind, Y, m, Th, tu, space):
-    """(loss[B], get_loss[B], unavailable[B], grad[P, B], get_loss_grad's [12, B]) from the host build."""
-    N, T = Y.shape
-    P, B = Th.shape
-    words = [str(kind), str(N), str(T), str(B), str(space)]
-    words += [hexf(v) for v in m]
-    words += [hexf(v) for v in np.asarray(Y).reshape(-1, order="F")]
-    for b in range(B):
-        words.append(str(int(tu[b])))
-        words += [hexf(v) for v in Th[:, b]]
-    path = tmp_path / "case.txt"
-    path.write_text(" ".join(words))
-    out = subprocess.run([str(exe), str(path)], check=True, capture_output=True, text=True).stdout.split("\n")
-    rows = np.array([[float.fromhex(v) if "0x" in v else float(v) for v in line.split()] for line in out if line])
-    assert rows.shape == (B, 3 + P + 12)
-    return rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3:3 + P].T, rows[:, 3 + P:].T
-
-
-def check_gradient(g, g_fd, e_fd, loss, label=""):
-    """The fixture rule per candidate (column) over all P rows; the NaN pattern must be the fixture's, which is the
-    −Inf pattern."""
-    for b in range(g.shape[1]):
-        if np.isnan(g_fd[:, b]).any():
-            assert np.isneginf(loss[b]) and np.isnan(g[:, b]).all(), (label, b, loss[b], g[:, b])
-            continue
-        assert np.isfinite(loss[b]) and np.isfinite(g[:, b]).all(), (label, b, loss[b], g[:, b])
-        err = np.max(np.abs(g[:, b] - g_fd[:, b]))
-        bound = REL * np.max(np.abs(g_fd[:, b])) + e_fd[b]
-        print(f"{label} b={b}: max|g - g_fd| = {err:.3e}, bound {bound:.3e}, |g|inf = {np.max(np.abs(g_fd[:, b])):.3e}")
-        assert err <= bound, (label, b, err, bound)
-
-
-def same_bits(a, b):
-    return np.array_equal(np.asarray(a, dtype=np.float64).view(np.uint64), np.asarray(b, dtype=np.float64).view(np.uint64))
 
 
 @pytest.mark.parametrize("space", [0, 1])

@@ -6,27 +6,23 @@ max_i |g − g_fd| ≤ 1e-9·‖g_fd‖∞ + e_fd over the leading rows; the los
 bit; a −Inf loss comes with P NaNs, exactly where the fixture has them."""
 from __future__ import annotations
 
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from grad_rule import assert_candidate_rule as check_leading
+from gpu_scenarios import same_bits
+from host_check_io import build_host_check, run_fullgrad_host as run_host
 
 sys.path.insert(0, str(GOLDEN / "msedn_fullgrad"))
 import make_msedn_fullgrad as MF  # noqa: E402
 
-REL = 1e-9
-
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("msedn_fullgrad") / "msedn_fullgrad_host_check"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    str(ROOT / "tests" / "msedn_fullgrad_host_check.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_host_check(tmp_path_factory, "msedn_fullgrad_host_check", sanitize=True)
 
 
 @pytest.fixture(scope="module")
@@ -34,49 +30,8 @@ def cases():
     return MF.load_cases()
 
 
-def hexf(v) -> str:
-    return "nan" if v != v else float(v).hex()
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
-
-
-def run_host(exe, tmp_path, kind, Y, m, Th, tu, space):
-    """(loss[B], loss_and_grad's loss[B], unavailable[B], grad[P, B], loss_and_grad's grad[12, B])."""
-    N, T = Y.shape
-    P, B = Th.shape
-    words = [str(kind), str(N), str(T), str(B), str(space)]
-    words += [hexf(v) for v in m]
-    words += [hexf(v) for v in np.asarray(Y).reshape(-1, order="F")]
-    for b in range(B):
-        words.append(str(int(tu[b])))
-        words += [hexf(v) for v in Th[:, b]]
-    path = tmp_path / "case.txt"
-    path.write_text(" ".join(words))
-    out = subprocess.run([str(exe), str(path)], check=True, capture_output=True, text=True).stdout.split("\n")
-    rows = np.array([[float.fromhex(v) if "0x" in v else float(v) for v in line.split()] for line in out if line])
-    assert rows.shape == (B, 3 + P + 12)
-    return rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3:3 + P].T, rows[:, 3 + P:].T
-
-
 def kind_of(name: str) -> int:
     return int(name[1:name.index("_")])
-
-
-def check_leading(g, g_fd, e_fd, loss, label=""):
-    """The fixture rule per candidate over the leading rows; the NaN pattern is the fixture's −Inf pattern."""
-    nl = g_fd.shape[0]
-    for b in range(g.shape[1]):
-        if np.isnan(g_fd[:, b]).any():
-            assert np.isneginf(loss[b]) and np.isnan(g[:, b]).all(), (label, b, loss[b], g[:, b])
-            continue
-        assert np.isfinite(loss[b]) and np.isfinite(g[:, b]).all(), (label, b, loss[b], g[:, b])
-        err = np.max(np.abs(g[:nl, b] - g_fd[:, b]))
-        bound = REL * np.max(np.abs(g_fd[:, b])) + e_fd[b]
-        print(f"{label} b={b}: max|g - g_fd| = {err:.3e}, bound {bound:.3e}")
-        assert err <= bound, (label, b, err, bound)
 
 
 @pytest.mark.parametrize("name", MF.case_names())

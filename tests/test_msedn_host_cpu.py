@@ -9,13 +9,13 @@ cycling scalar / block_diag / diag) × N ∈ {4, 5, 30, 33} × a panel with a Na
 first column is NaN × both parameter spaces, three candidates each (T = 10)."""
 from __future__ import annotations
 
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
+from conftest import GOLDEN
+from host_check_io import build_host_check, run_loss_host as run_host
 
 sys.path.insert(0, str(GOLDEN / "msedn"))
 import make_msedn as MM  # noqa: E402
@@ -26,36 +26,12 @@ REL = 1e-12
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("msedn") / "msedn_host_check"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                    str(ROOT / "tests" / "msedn_host_check.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_host_check(tmp_path_factory, "msedn_host_check", sanitize=True)
 
 
 @pytest.fixture(scope="module")
 def cases():
     return MM.load_cases()
-
-
-def hexf(v) -> str:
-    return "nan" if v != v else float(v).hex()
-
-
-def run_host(exe, tmp_path, kind, Y, m, Th, tu, space):
-    N, T = Y.shape
-    B = Th.shape[1]
-    words = [str(kind), str(N), str(T), str(B), str(space)]
-    words += [hexf(v) for v in m]
-    words += [hexf(v) for v in np.asarray(Y).reshape(-1, order="F")]
-    for b in range(B):
-        words.append(str(int(tu[b])))
-        words += [hexf(v) for v in Th[:, b]]
-    path = tmp_path / "case.txt"
-    path.write_text(" ".join(words))
-    out = subprocess.run([str(exe), str(path)], check=True, capture_output=True, text=True).stdout.split()
-    assert len(out) == B
-    return np.array([float.fromhex(v) if "0x" in v else float(v) for v in out])
 
 
 def test_the_cases_cover_every_switch():

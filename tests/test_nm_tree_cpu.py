@@ -16,7 +16,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_check_io import build_host_check
 from oracle import optim_nm as NM
 
 R, N, ITER, MGI = 6, 20, 120, 3
@@ -45,10 +45,7 @@ def start(r):
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("nm") / "nm_tree_check"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                    str(ROOT / "tests" / "nm_tree_check.cpp"), "-o", str(exe)], check=True)
-    return exe
+    return build_host_check(tmp_path_factory, "nm_tree_check")
 
 
 def run(exe, budget):

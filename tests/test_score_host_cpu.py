@@ -9,28 +9,23 @@ the smallest case and on windows that end early.
 """
 from __future__ import annotations
 
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-from conftest import GOLDEN, ROOT
-from host_check_io import run_score_host as run_host
+from conftest import GOLDEN
+from host_check_io import build_host_check, run_score_host as run_host
 
 sys.path.insert(0, str(GOLDEN / "info"))
 import make_info as MI  # noqa: E402
 
 REL = 1e-9
-SRC = ROOT / "tests" / "score_host_check.cpp"
-FLAGS = ["-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas"]
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("score") / "score_host_check"
-    subprocess.run(["g++", "-O2", *FLAGS, str(SRC), "-o", str(exe)], check=True)
-    return exe
+    return build_host_check(tmp_path_factory, "score_host_check")
 
 
 def check_case(c, ll, g, Sc):
@@ -58,9 +53,7 @@ def test_host_scores_match_truth_differences(harness, tmp_path, name):
 def test_host_scores_under_the_sanitizers(tmp_path):
     """AddressSanitizer and UndefinedBehaviorSanitizer on the stand-alone program: the smallest case on its whole
     window and on windows of 1, 2 and 3 columns (no term, no term, one term)."""
-    exe = tmp_path / "score_host_check_san"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *FLAGS, str(SRC),
-                    "-o", str(exe)], check=True)
+    exe = build_host_check(tmp_path, "score_host_check", sanitize=True)
     c = MI.load_cases()["S-E"]
     T = c["Y"].shape[1]
     Th = np.repeat(c["Theta"][:, :1], 4, axis=1)

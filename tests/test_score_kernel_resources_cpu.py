@@ -4,20 +4,14 @@ dns_grad_kernel's recursion and stores a term per step, so it has no scratch and
 (DESIGN.md §3.11 states no allowance on top); opg_kernel has no scratch."""
 import pytest
 
-from test_kernel_resources_cpu import LIB, READELF, _kernel_metadata
+from test_kernel_resources_cpu import LIB, READELF, _kernel_metadata, only
 
 
 @pytest.mark.skipif(not LIB.exists() or not READELF.exists(), reason="in-tree library or llvm-readelf missing")
 def test_score_and_opg_kernels_within_budget(tmp_path):
     meta = _kernel_metadata(tmp_path)
 
-    def only(fragment):
-        hits = [(n, m) for n, m in meta.items() if fragment in n]
-        assert len(hits) == 1, sorted(meta)
-        print(*hits[0])
-        return hits[0][1]
-
-    grad, score, opg = only("dns_grad_kernel"), only("dns_score_kernel"), only("opg_kernel")
+    grad, score, opg = only(meta, "dns_grad_kernel"), only(meta, "dns_score_kernel"), only(meta, "opg_kernel")
     assert score["private_segment_fixed_size"] == 0 and score["vgpr_spill_count"] == 0, score
     assert score["vgpr_count"] <= grad["vgpr_count"] and score["agpr_count"] <= grad["agpr_count"], (score, grad)
     assert opg["private_segment_fixed_size"] == 0 and opg["vgpr_spill_count"] == 0, opg

@@ -10,37 +10,17 @@ the smallest case and on windows of 1, 2 and 3 columns.
 """
 from __future__ import annotations
 
-import subprocess
-
 import numpy as np
 import pytest
 
 import smooth_fixture as SF
-from conftest import ROOT
-from host_check_io import run_program
-
-SRC = ROOT / "tests" / "smooth_host_check.cpp"
-FLAGS = ["-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas"]
-
-
-def run_host(exe, tmp_path, M, Y, m, Th, tu, space=0):
-    """(beta_s[M, T, B], V_s[M, M, T, B], C_s[M, M, T − 1, B]) of smooth_host_check: T lines per candidate."""
-    T, B = Y.shape[1], Th.shape[1]
-    rows = np.array(run_program(exe, tmp_path, Y, m, Th, tu, space)).reshape(B, T, M + 2 * M * M)
-    bs = rows[:, :, :M].transpose(2, 1, 0)
-    V = rows[:, :, M:M + M * M].reshape(B, T, M, M).transpose(3, 2, 1, 0)  # column-major M × M per line
-    C = rows[:, :, M + M * M:].reshape(B, T, M, M).transpose(3, 2, 1, 0)[:, :, :T - 1]
-    return bs, V, C
+from host_check_io import build_host_check, run_smooth_host as run_host
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     d = tmp_path_factory.mktemp("smooth")
-    exes = {}
-    for M in (3, 5):
-        exes[M] = d / f"smooth_host_check_{M}"
-        subprocess.run(["g++", "-O2", *FLAGS, f"-DYFM_SMOOTH_M={M}", str(SRC), "-o", str(exes[M])], check=True)
-    return exes
+    return {M: build_host_check(d, "smooth_host_check", M=M) for M in (3, 5)}
 
 
 @pytest.mark.parametrize("space", (0, 1))
@@ -60,9 +40,7 @@ def test_host_smoother_under_the_sanitizers(tmp_path):
     """AddressSanitizer and UndefinedBehaviorSanitizer on the stand-alone program: the smallest case on its whole window
     and on windows of 1, 2 and 3 columns (one update and no C; one C; two), each against the dense checker on the
     same window."""
-    exe = tmp_path / "smooth_host_check_san"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *FLAGS,
-                    "-DYFM_SMOOTH_M=3", str(SRC), "-o", str(exe)], check=True)
+    exe = build_host_check(tmp_path, "smooth_host_check", sanitize=True, M=3)
     c = SF.cases()["S-E"]
     T = c["Y"].shape[1]
     Th = np.repeat(c["Theta"][:, :1], 4, axis=1)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import smooth_long_fixture as LF
+from gpu_scenarios import same_bits
 
 FIXED_CASES = LF.ML.CASES
 TVL_CASES = LF.MTL.CASES
@@ -31,7 +32,7 @@ def test_case_inputs_regenerate_the_stored_inputs_bit_for_bit(model, name):
         Y, m, Th, windows, unit, k = inp
         assert k == c["seed_step"]
     for got, stored in ((Y, c["Y"]), (m, c["maturities"]), (Th, c["Theta"])):
-        assert LF.same_bits(np.asarray(got, dtype=np.float64), stored)
+        assert same_bits(np.asarray(got, dtype=np.float64), stored)
     assert tuple(windows) == c["windows"] and unit == c["unit_root"]
     assert [(name, n) for n in windows] == [cw for cw in LF.case_windows(model) if cw[0] == name]
     N, T, B = LF.GENERATORS[model].SHAPES[name]

@@ -13,24 +13,17 @@ C 1.25e-9, 2.49e-10, 1.28e-9.  With a_{t|t} = a_t + P_ts_t, as the header had it
 """
 from __future__ import annotations
 
-import subprocess
-
 import numpy as np
 import pytest
 
 import smooth_long_fixture as LF
-from test_smooth_host_cpu import FLAGS, SRC, run_host
-
+from host_check_io import build_host_check, run_smooth_host as run_host
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
     d = tmp_path_factory.mktemp("smooth_long")
-    exes = {}
-    for M in (3, 5):
-        exes[M] = d / f"smooth_host_check_{M}"
-        subprocess.run(["g++", "-O2", *FLAGS, f"-DYFM_SMOOTH_M={M}", str(SRC), "-o", str(exes[M])], check=True)
-    return exes
+    return {M: build_host_check(d, "smooth_host_check", M=M) for M in (3, 5)}
 
 
 @pytest.mark.parametrize("name,n", LF.case_windows("fixed"))

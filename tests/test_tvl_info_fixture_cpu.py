@@ -11,14 +11,13 @@ program: no preloading) and run on the smallest case and on windows that end ear
 """
 from __future__ import annotations
 
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
-from host_check_io import run_score_host as run_host
+from host_check_io import build_host_check, run_score_host as run_host
 from yfm_amd import _lib
 
 sys.path.insert(0, str(GOLDEN / "tvl_info"))
@@ -28,12 +27,11 @@ import tvl_hessian_step_table as ST  # noqa: E402
 
 REL = 1e-9
 U = 2.0 ** -53
-SRC = ROOT / "tests" / "tvl_score_host_check.cpp"
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return ST.build(tmp_path_factory.mktemp("tvl_score"))
+    return build_host_check(tmp_path_factory, "tvl_score_host_check")
 
 
 @pytest.fixture(scope="module")
@@ -74,9 +72,7 @@ def test_host_hessian_at_the_default_step_is_as_close_as_the_fp64_reference(harn
 def test_host_scores_under_the_sanitizers(cases, tmp_path):
     """AddressSanitizer and UndefinedBehaviorSanitizer on the stand-alone program: the smallest case on its whole
     window and on windows of 1, 2 and 3 columns (no term, no term, one term)."""
-    exe = tmp_path / "tvl_score_host_check_san"
-    subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", *ST.FLAGS, str(SRC),
-                    "-o", str(exe)], check=True)
+    exe = build_host_check(tmp_path, "tvl_score_host_check", sanitize=True)
     c = cases["S-n4"]
     T = c["Y"].shape[1]
     Th = np.repeat(c["Theta"][:, :1], 4, axis=1)

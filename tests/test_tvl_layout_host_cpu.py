@@ -12,14 +12,11 @@ from __future__ import annotations
 
 import subprocess
 
-from conftest import ROOT
+from host_check_io import build_host_check
 
 
 def test_layout_structs_match_the_former_chains(tmp_path):
-    exe = tmp_path / "tvl_layout_host_check"
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", str(ROOT / "tests" / "tvl_layout_host_check.cpp"), "-o", str(exe)],
-                   check=True)
+    exe = build_host_check(tmp_path, "tvl_layout_host_check", sanitize=True)
     out = subprocess.run([str(exe)], capture_output=True, text=True)
     print(out.stdout, out.stderr)
     assert out.returncode == 0

@@ -5,20 +5,14 @@ which fills the 512 registers of a 256-thread block, and stores a term per step:
 the store, so it has no scratch and no spilled VGPR either.  opg31_kernel has opg_kernel's limits."""
 import pytest
 
-from test_kernel_resources_cpu import LIB, READELF, _kernel_metadata
+from test_kernel_resources_cpu import LIB, READELF, _kernel_metadata, only
 
 
 @pytest.mark.skipif(not LIB.exists() or not READELF.exists(), reason="in-tree library or llvm-readelf missing")
 def test_tvl_score_and_opg31_kernels_within_budget(tmp_path):
     meta = _kernel_metadata(tmp_path)
 
-    def only(fragment):
-        hits = [(n, m) for n, m in meta.items() if fragment in n]
-        assert len(hits) == 1, sorted(meta)
-        print(*hits[0])
-        return hits[0][1]
-
-    score, opg = only("tvl_score_kernel"), only("opg31_kernel")
+    score, opg = only(meta, "tvl_score_kernel"), only(meta, "opg31_kernel")
     assert score["private_segment_fixed_size"] == 0 and score["vgpr_spill_count"] == 0, score
     assert score["vgpr_count"] <= 512, score  # VGPRs and AGPRs together (gfx950's unified file)
     assert opg["private_segment_fixed_size"] == 0 and opg["vgpr_spill_count"] == 0, opg

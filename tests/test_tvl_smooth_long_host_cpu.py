@@ -11,27 +11,23 @@ C 1.13e-10, 5.42e-11, 1.03e-10.
 """
 from __future__ import annotations
 
-import subprocess
-
 import numpy as np
 import pytest
 
 import smooth_long_fixture as LF
-from test_tvl_smooth_host_cpu import FLAGS, SRC, run_host
+from host_check_io import build_host_check, run_smooth_host as run_host
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = tmp_path_factory.mktemp("tvl_smooth_long") / "tvl_smooth_host_check"
-    subprocess.run(["g++", "-O2", *FLAGS, str(SRC), "-o", str(out)], check=True)
-    return out
+    return build_host_check(tmp_path_factory, "tvl_smooth_host_check")
 
 
 @pytest.mark.parametrize("name,n", LF.case_windows("tvl"))
 def test_host_smoother_meets_the_rule(exe, tmp_path, name, n):
     c = LF.cases("tvl")[name]
     B = c["Theta"].shape[1]
-    bs, V, C = run_host(exe, tmp_path, c["Y"], c["maturities"], c["Theta"], np.full(B, n))
+    bs, V, C = run_host(exe, tmp_path, 4, c["Y"], c["maturities"], c["Theta"], np.full(B, n))
     for b in range(B):
         LF.assert_candidate("tvl", name, n, b, bs[..., b], V[..., b], C[..., b])
 
@@ -39,7 +35,7 @@ def test_host_smoother_meets_the_rule(exe, tmp_path, name, n):
 @pytest.mark.parametrize("name,n,b,what", LF.hard_params("tvl"))
 def test_hard_candidate_meets_the_rule(exe, tmp_path, name, n, b, what):
     c = LF.cases("tvl")[name]
-    bs, V, C = run_host(exe, tmp_path, c["Y"], c["maturities"], c["Theta"][:, b:b + 1], np.full(1, n))
+    bs, V, C = run_host(exe, tmp_path, 4, c["Y"], c["maturities"], c["Theta"][:, b:b + 1], np.full(1, n))
     LF.assert_hard_array("tvl", name, n, b, what, bs[..., 0], V[..., 0], C[..., 0])
 
 
@@ -49,6 +45,6 @@ def test_mixed_windows_in_one_call_are_the_solo_windows(exe, tmp_path):
     c = LF.cases("tvl")["TL-chunk"]
     tu = np.array(LF.MIXED_WINDOWS)
     Th = np.repeat(c["Theta"][:, :1], len(tu), axis=1)
-    bs, V, C = run_host(exe, tmp_path, c["Y"], c["maturities"], Th, tu)
+    bs, V, C = run_host(exe, tmp_path, 4, c["Y"], c["maturities"], Th, tu)
     for k, n in enumerate(tu):
         LF.assert_candidate("tvl", "TL-chunk", int(n), 0, bs[..., k], V[..., k], C[..., k])

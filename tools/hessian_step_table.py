@@ -9,7 +9,6 @@ case is the default (DESIGN.md §3.11 holds the table).
 
     python tools/hessian_step_table.py
 """
-import subprocess
 import sys
 import tempfile
 from pathlib import Path
@@ -22,7 +21,7 @@ sys.path.insert(0, str(ROOT / "tests" / "golden" / "info"))
 sys.path.insert(0, str(ROOT / "yieldfactormodels.jl_amd"))
 sys.path.insert(0, str(ROOT))
 import make_info as MI  # noqa: E402
-from host_check_io import run_grad_host as run_host  # noqa: E402
+from host_check_io import build_host_check, run_grad_host as run_host  # noqa: E402
 
 STEPS = (1e-2, 3e-3, 1e-3, 3e-4, 1e-4)
 
@@ -49,9 +48,7 @@ def main():
     cases = MI.load_cases()
     with tempfile.TemporaryDirectory() as d:
         tmp = Path(d)
-        exe = tmp / "grad_host_check"
-        subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas",
-                        str(ROOT / "tests" / "grad_host_check.cpp"), "-o", str(exe)], check=True)
+        exe = build_host_check(tmp, "grad_host_check")
         print("step     " + "  ".join(f"{n}[{b}]" for n in MI.HESS_CASES for b in range(cases[n]["Theta"].shape[1]))
               + "   worst")
         worst = {}

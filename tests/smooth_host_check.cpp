@@ -9,33 +9,14 @@
 // Output, per candidate, T lines: β̂_t (M), V_t (M², column-major), C_t (M², column-major), hex floats; NaN past the
 // window, in C of the window's last column, and everywhere for a candidate whose initial state is singular or that
 // has an output that is not finite.
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <vector>
-
 #include "../yieldfactormodels.jl_amd/csrc/yfm_smooth.hpp"
+#include "smooth_host_io.hpp"
 
 #ifndef YFM_SMOOTH_M
 #define YFM_SMOOTH_M 3
 #endif
 
-namespace sm = yfm::smooth;
 constexpr int M = YFM_SMOOTH_M;
-
-static double rd(FILE* f) {
-  char buf[128];
-  if (std::fscanf(f, "%127s", buf) != 1) {
-    std::fprintf(stderr, "short input\n");
-    std::exit(2);
-  }
-  return std::strtod(buf, nullptr);
-}
-
-struct Col {
-  double a[M], P[M][M];
-  sm::StepOps<M> o;
-};
 
 int main(int argc, char** argv) {
   if (argc != 2) return 2;
@@ -46,7 +27,6 @@ int main(int argc, char** argv) {
   std::vector<double> mats(N), Y((size_t)N * T);
   for (double& v : mats) v = rd(f);
   for (double& v : Y) v = rd(f);
-  constexpr int kRow = M + 2 * M * M;
   for (int b = 0; b < B; ++b) {
     int n = (int)rd(f);
     n = n < 1 ? 1 : (n > T ? T : n);
@@ -65,7 +45,7 @@ int main(int argc, char** argv) {
     }
     for (int j = 0; j < M; ++j)
       for (int k = j + 1; k < M; ++k) G[k][j] = G[j][k];
-    std::vector<Col> col(n);
+    std::vector<Col<M>> col(n);
     double lds[sm::InitCov<M>::kDoubles];
     bool ok = sm::init_mean<M>(m, col[0].a);
     ok = sm::InitCov<M>::solve(m, lds, 0, 1, [] {}, col[0].P) && ok;
@@ -81,38 +61,7 @@ int main(int argc, char** argv) {
       sm::step_operands<M>(m, G, col[t].a, col[t].P, zy, missing, col[t].o);
       if (t + 1 < n) sm::predict<M>(m, col[t].o.af, col[t].o.Pf, col[t + 1].a, col[t + 1].P);
     }
-    // backward
-    std::vector<double> out((size_t)T * kRow, std::nan(""));
-    double r[M] = {}, Nm[M][M] = {};
-    for (int t = n - 1; t >= 0; --t) {
-      const bool lag = t + 1 < n;
-      double Pn[M][M] = {}, bs[M], V[M][M], C[M][M];
-      if (lag)
-        for (int i = 0; i < M; ++i)
-          for (int j = 0; j < M; ++j) Pn[i][j] = col[t + 1].P[i][j];
-      ok = sm::step_outputs<M>(m, col[t].o.af, col[t].o.Pf, r, Nm, lag, Pn, bs, V, C) && ok;
-      double* o = &out[(size_t)t * kRow];
-      for (int i = 0; i < M; ++i) {
-        o[i] = bs[i];
-        for (int j = 0; j < M; ++j) {
-          o[M + j * M + i] = V[i][j];
-          if (lag) o[M + M * M + j * M + i] = C[i][j];
-        }
-      }
-      sm::chain_step<M>(col[t].o.s, col[t].o.W, col[t].o.L, r, Nm);
-    }
-    if (!ok)
-      for (double& v : out) v = std::nan("");
-    for (int t = 0; t < T; ++t) {
-      for (int k = 0; k < kRow; ++k) {
-        const double v = out[(size_t)t * kRow + k];
-        if (v != v)
-          std::printf("%snan", k ? " " : "");
-        else
-          std::printf("%s%a", k ? " " : "", v);
-      }
-      std::printf("\n");
-    }
+    print_rows(smooth_backward<M>(m, col, T, ok), M + 2 * M * M);
   }
   std::fclose(f);
   return 0;

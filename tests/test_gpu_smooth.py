@@ -78,7 +78,7 @@ def test_a_candidate_does_not_depend_on_its_batch_or_position(engine):
             assert same_bits(np.ascontiguousarray(g[..., pos]), np.ascontiguousarray(s[..., 0])), pos
 
 
-@pytest.mark.parametrize("n", (1, 3, 65))
+@pytest.mark.parametrize("n", (1, 3, 64, 65))  # one column, a partial chunk, a chunk exactly full, one column beyond it
 def test_a_window_is_the_panel_cut_to_it(engine, n):
     c = SF.cases()["S-n30"]
     engine.set_panel(c["Y"], c["maturities"])

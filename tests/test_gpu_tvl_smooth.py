@@ -82,7 +82,7 @@ def test_last_smoothed_state_propagates_to_predicts_forecast(engine):
         assert np.abs(got - want).max() <= 1e-9 * np.abs(want).max()
 
 
-@pytest.mark.parametrize("n", (1, 3, 65))
+@pytest.mark.parametrize("n", (1, 3, 64, 65))  # one column, a partial chunk, a chunk exactly full, one column beyond it
 def test_a_window_agrees_with_the_panel_cut_to_it(engine, n):
     """T_use = n against the panel cut to n columns: both meet the parity rule on that window, and they are within 1e-9
     of each other normwise per step.  Whether they are bitwise equal is printed, not asserted: the header promises the

@@ -5,50 +5,24 @@
 // The forward pass is the trajectory launch of yfm_filter_states: its record holds a_2 … a_n and P_2 … P_n, the
 // predicted moments the sweep needs; a_1 and P_1 are formed here (yfm_smooth.hpp init_mean, InitCov).
 //
-// smooth_kernel: one wave per candidate, the algebra of yfm_smooth.hpp.  The window is cut into chunks of 64 columns
-// (chunk c holds columns 64c + 1 … 64c + 64, whatever the window's end, so a column's lane and chunk do not depend on
-// n) that are taken from the last to the first.  Per chunk
-//   1. lane ℓ forms the operands of its column t = 64c + 1 + ℓ — Z'y_t over the N maturities (Z from LDS, broadcast),
-//      the solve with B_t, then s_t, W_t, L_t, a_{t|t}, P_{t|t} — from the recorded moments and the data alone, all 64
-//      columns at once, every load issued before the recursion, and writes s_t, W_t, L_t to LDS (operand-major, so
-//      the stores are conflict-free and the chain's reads are broadcasts);
-//   2. every lane runs the short serial chain r_{t−1} = s_t + L_t'r_t, N_{t−1} = W_t + L_t'N_tL_t over the chunk's
-//      columns on wave-uniform values (r and N stay in registers across chunks) and keeps r_t, N_t of its own column
-//      as the chain passes it;
-//   3. lane ℓ forms a_{t|t} = G⁻¹u_t (G⁻¹ from LDS; u_t = Z'y_t − σ²s_t kept from phase 1), then β̂_t, V_t and C_t of its
-//      column, and stores them.
-// Slots past a candidate's window are written as NaN by the same wave, and all of an unavailable candidate's slots:
-// a loglik that is not finite (−Inf, or NaN where initialize_filter throws), a candidate on the deferral list (`skip`),
-// an output that is not finite.  Those candidates raise flags[5].  No memset of the outputs is needed.
+// smooth_kernel: one wave per candidate, the chunked sweep of yfm_smooth_sweep.hpp (its phases 1 to 3 below), the
+// algebra of yfm_smooth.hpp.  What is this kernel's own:
+//   phase 1: Z'y_t over the N maturities (Z from LDS, broadcast), the solve with B_t, then s_t, W_t, L_t, P_{t|t}; of
+//     a_{t|t} only u_t = Z'y_t − σ²s_t (a_t at a missing column) is formed, and kept across the chain;
+//   phase 3: a_{t|t} = G⁻¹u_t (G⁻¹ from LDS), taken there because the chain's registers are free.
+// Unavailable, beside an output that is not finite: a loglik that is not finite (−Inf, or NaN where initialize_filter
+// throws) and a candidate on the deferral list (`skip`).
 #include <algorithm>
+#include <type_traits>
 
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
-#include "yfm_smooth.hpp"
+#include "yfm_smooth_sweep.hpp"
 
 namespace yfm {
 
-namespace {
-
-constexpr int kSmoothChunk = 64;  // columns per chunk: one per lane
-
-template <int M>
-constexpr int smooth_ops() {
-  return M + 2 * M * M;  // s, W, L per column
-}
-
-template <int M>
-__device__ __forceinline__ void fill_nan(double* __restrict__ beta_s, double* __restrict__ V_s, double* __restrict__ C_s,
-                                         int t_from, int T, int lane) {
-  const double nan = __builtin_nan("");
-  // slots t_from … T − 1 of β̂ and V (0-based), slots max(t_from − 1, 0) … T − 2 of C
-  for (size_t e = (size_t)t_from * M + lane; e < (size_t)T * M; e += 64) beta_s[e] = nan;
-  for (size_t e = (size_t)t_from * M * M + lane; e < (size_t)T * M * M; e += 64) V_s[e] = nan;
-  if (C_s)
-    for (size_t e = (size_t)max(t_from - 1, 0) * M * M + lane; e < (size_t)max(T - 1, 0) * M * M; e += 64) C_s[e] = nan;
-}
-
-}  // namespace
+using smooth::fill_nan;
+using smooth::kSmoothChunk;
 
 // theta: P × nb; ll: nb logliks of the forward launch; skip: nb marks (deferred candidates); rec_beta / rec_P: the
 // forward record, M (× M) × rec_len × nb, slot t − 2 = a_t, P_t; outputs M × T × nb, M × M × T × nb, M × M × (T − 1) × nb
@@ -63,11 +37,10 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
                                                     double* __restrict__ beta_s, double* __restrict__ V_s,
                                                     double* __restrict__ C_s, unsigned int* __restrict__ flags) {
   namespace sm = smooth;
-  constexpr int kOps = smooth_ops<M>();
-  __shared__ double zs[64 * M];                       // Z, row i at zs[i M …]
-  __shared__ double init_lds[sm::InitCov<M>::kDoubles];  // the P_1 system
-  __shared__ double ops[kOps * kSmoothChunk];          // operand k of column j at ops[64 k + j]
-  __shared__ double gis[M * M];                        // G⁻¹, row-major
+  __shared__ double zs[64 * M];                               // Z, row i at zs[i M …]
+  __shared__ double init_lds[sm::InitCov<M>::kDoubles];       // the P_1 system
+  __shared__ double ops[sm::smooth_ops<M>() * kSmoothChunk];  // the sweep's s, W, L
+  __shared__ double gis[M * M];                               // G⁻¹, row-major
 
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
@@ -148,14 +121,7 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
         for (int j = 0; j < M; ++j) Pm[i][j] = P1[i][j];
       }
     } else {
-      const double* pa = rec_beta + (rb + (size_t)(tt - 2)) * M;
-      const double* pp = rec_P + (rb + (size_t)(tt - 2)) * M * M;
-#pragma unroll
-      for (int i = 0; i < M; ++i) {
-        a[i] = pa[i];
-#pragma unroll
-        for (int j = 0; j < M; ++j) Pm[i][j] = pp[j * M + i];
-      }
+      sm::record_moments<M>(rec_beta, rec_P, rb + (size_t)(tt - 2), a, Pm);
     }
     double zy[M];
 #pragma unroll
@@ -168,24 +134,13 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
 #pragma unroll
       for (int k = 0; k < M; ++k) zy[k] = fma(zs[i * M + k], y, zy[k]);
     }
-    double af[M], Pf[M][M];
-    {
-      sm::StepOps<M> o;
-      sm::step_operands_core<M>(m, G, a, Pm, zy, missing, o);
+    sm::StepOps<M> o;
+    sm::step_operands_core<M>(m, G, a, Pm, zy, missing, o);
+    sm::store_operands<M>(ops, lane, o);
+    // a_{t|t} waits for phase 3, where the chain's registers are free: a (missing column) or G a_{t|t} until then
+    double af[M];
 #pragma unroll
-      for (int i = 0; i < M; ++i) {
-        ops[kSmoothChunk * i + lane] = o.s[i];
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-          Pf[i][j] = o.Pf[i][j];
-          ops[kSmoothChunk * (M + i * M + j) + lane] = o.W[i][j];
-          ops[kSmoothChunk * (M + M * M + i * M + j) + lane] = o.L[i][j];
-        }
-      }
-      // a_{t|t} waits for phase 3, where the chain's registers are free: a (missing column) or G a_{t|t} until then
-#pragma unroll
-      for (int i = 0; i < M; ++i) af[i] = missing ? a[i] : o.u[i];
-    }
+    for (int i = 0; i < M; ++i) af[i] = missing ? a[i] : o.u[i];
     wave_lds_sync();
     // 2. the chain over the chunk's columns, last to first; this lane keeps r_t, N_t of its own column
     double rt[M], Nt[M][M];
@@ -229,7 +184,7 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
       sm::filtered_mean<M>(gis, ga, ga, missing, af);
     }
     double bs[M], V[M][M], C[M][M];
-    const bool fin = sm::step_outputs<M>(m, af, Pf, rt, Nt, lag, Pn, bs, V, C);
+    const bool fin = sm::step_outputs<M>(m, af, o.Pf, rt, Nt, lag, Pn, bs, V, C);
     ok = ok && (fin || !act);
     if (act) {
 #pragma unroll
@@ -247,11 +202,7 @@ __global__ __launch_bounds__(64) void smooth_kernel(const double* __restrict__ t
     }
   }
   // an output that is not finite anywhere makes the candidate unavailable: all of it NaN
-  const bool bad = __ballot(!ok) != 0ull;
-  if (bad) {
-    __threadfence();
-    if (lane == 0) atomicAdd(flags + 5, 1u);
-  }
+  const bool bad = sm::raise_unavailable(ok, lane, flags);
   fill_nan<M>(bo, Vo, Co, bad ? 0 : n, T, lane);
 }
 
@@ -278,16 +229,15 @@ hipError_t launch_smooth(int kind, const LaunchArgs& a, const double* ll, unsign
                      a.defer_list, a.flags, a.B, skip);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  if (kind == YFM_MODEL_GNS5) {
-    hipLaunchKernelGGL(smooth_kernel<5>, dim3(a.B), dim3(64), 0, a.stream, a.theta, a.P, a.B, a.space, a.raw, a.N, a.T,
-                       a.mats, a.T_use, ll, skip, a.rec_beta, a.rec_P, a.rec_len, beta_s, V_s, C_s, a.flags);
-  } else if (kind == YFM_MODEL_DNS) {
-    hipLaunchKernelGGL(smooth_kernel<3>, dim3(a.B), dim3(64), 0, a.stream, a.theta, a.P, a.B, a.space, a.raw, a.N, a.T,
-                       a.mats, a.T_use, ll, skip, a.rec_beta, a.rec_P, a.rec_len, beta_s, V_s, C_s, a.flags);
-  } else {
-    return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
+  auto launch = [&](auto m) {
+    hipLaunchKernelGGL(smooth_kernel<decltype(m)::value>, dim3(a.B), dim3(64), 0, a.stream, a.theta, a.P, a.B, a.space,
+                       a.raw, a.N, a.T, a.mats, a.T_use, ll, skip, a.rec_beta, a.rec_P, a.rec_len, beta_s, V_s, C_s,
+                       a.flags);
+    return hipGetLastError();
+  };
+  if (kind == YFM_MODEL_GNS5) return launch(std::integral_constant<int, 5>{});
+  if (kind == YFM_MODEL_DNS) return launch(std::integral_constant<int, 3>{});
+  return hipErrorInvalidValue;
 }
 
 }  // namespace yfm

@@ -5,44 +5,23 @@
 // The forward pass is the TVλ trajectory launch of yfm_filter_states under the context's precision: its record holds
 // a_2 … a_n and P_2 … P_n; a_1 and P_1 are formed here (yfm_smooth.hpp init_mean, InitCov<4>).
 //
-// tvl_smooth_kernel: one wave per candidate, smooth_kernel's mapping, the algebra of yfm_tvl_smooth.hpp.  The window
-// is cut into chunks of 64 columns (chunk c holds columns 64c + 1 … 64c + 64, whatever the window's end), taken from
-// the last to the first.  Per chunk
-//   1. lane ℓ takes a_t, P_t of its column t = 64c + 1 + ℓ, forms the loadings' constants at λ_t = 0.01 + e^{a₄,t}
-//      with the forward's function (tvlgrad::step_consts, its λ-overflow branch tested on the smallest maturity), runs
-//      the maturity loop — one exp per maturity, (m, 1/m) broadcast from LDS, the panel column read through the cache —
-//      for G_t, u_t and the missing flag, then the 4×4 update in its symmetric form, and writes s_t, W_t, L_t to LDS
-//      (operand-major: conflict-free stores, broadcast reads);
-//   2. every lane runs the serial chain over the chunk's columns on wave-uniform values (smooth::chain_step; r and N
-//      stay in registers across chunks) and keeps r_t, N_t of its own column as the chain passes it;
-//   3. lane ℓ forms β̂_t, V_t and C_t of its column (smooth::step_outputs) and stores them.
-// Slots past a candidate's window are written as NaN by the same wave, and all of an unavailable candidate's slots: a
-// loglik that is not finite, a singular initial state, a data column whose det(σ²I + P_tG_t) is not usable
-// (tvlsmooth::det_usable: the gradient kernel's rule), an output that is not finite.  Those candidates raise flags[5].
-// No memset of the outputs is needed.
+// tvl_smooth_kernel: one wave per candidate, the chunked sweep of yfm_smooth_sweep.hpp (its phases 1 to 3 below) at
+// M = 4, the algebra of yfm_tvl_smooth.hpp.  What is this kernel's own is phase 1: from a_t, P_t of its column lane ℓ
+// forms the loadings' constants at λ_t = 0.01 + e^{a₄,t} with the forward's function (tvlgrad::step_consts, its
+// λ-overflow branch tested on the smallest maturity), runs the maturity loop — one exp per maturity, (m, 1/m) broadcast
+// from LDS, the panel column read through the cache — for G_t, u_t and the missing flag, then the 4×4 update in its
+// symmetric form for s_t, W_t, L_t, a_{t|t}, P_{t|t}.
+// Unavailable, beside an output that is not finite: a loglik that is not finite, a singular initial state, a data
+// column whose det(σ²I + P_tG_t) is not usable (tvlsmooth::det_usable: the gradient kernel's rule).
 #include "yfm_device.hpp"
 #include "yfm_internal.hpp"
+#include "yfm_smooth_sweep.hpp"
 #include "yfm_tvl_smooth.hpp"
 
 namespace yfm {
 
-namespace {
-
-constexpr int kTvlSmoothChunk = 64;                 // columns per chunk: one per lane
-constexpr int kTvlSmoothOps = 4 + 2 * 4 * 4;        // s, W, L per column
-
-__device__ __forceinline__ void tvl_fill_nan(double* __restrict__ beta_s, double* __restrict__ V_s,
-                                             double* __restrict__ C_s, int t_from, int T, int lane) {
-  constexpr int M = 4;
-  const double nan = __builtin_nan("");
-  // slots t_from … T − 1 of β̂ and V (0-based), slots max(t_from − 1, 0) … T − 2 of C
-  for (size_t e = (size_t)t_from * M + lane; e < (size_t)T * M; e += 64) beta_s[e] = nan;
-  for (size_t e = (size_t)t_from * M * M + lane; e < (size_t)T * M * M; e += 64) V_s[e] = nan;
-  if (C_s)
-    for (size_t e = (size_t)max(t_from - 1, 0) * M * M + lane; e < (size_t)max(T - 1, 0) * M * M; e += 64) C_s[e] = nan;
-}
-
-}  // namespace
+using smooth::fill_nan;
+using smooth::kSmoothChunk;
 
 // theta: 31 × nb; ll: nb logliks of the forward launch; rec_beta / rec_P: the forward record, 4 (× 4) × rec_len × nb,
 // slot t − 2 = a_t, P_t; outputs 4 × T × nb, 4 × 4 × T × nb, 4 × 4 × (T − 1) × nb.  Dynamic LDS: N × (m, 1/m).
@@ -61,7 +40,7 @@ __global__ __launch_bounds__(64) void tvl_smooth_kernel(const double* __restrict
   extern __shared__ __attribute__((aligned(16))) double tvl_smooth_dyn[];
   double2* const s_mr = reinterpret_cast<double2*>(tvl_smooth_dyn);  // (m_i, 1/m_i)
   __shared__ double init_lds[sm::InitCov<M>::kDoubles];               // the P_1 system
-  __shared__ double ops[kTvlSmoothOps * kTvlSmoothChunk];             // operand k of column j at ops[64 k + j]
+  __shared__ double ops[sm::smooth_ops<M>() * kSmoothChunk];          // the sweep's s, W, L
 
   const int lane = threadIdx.x;
   const int b = blockIdx.x;
@@ -72,7 +51,7 @@ __global__ __launch_bounds__(64) void tvl_smooth_kernel(const double* __restrict
   double* const Co = C_s ? C_s + (size_t)b * M * M * (size_t)max(T - 1, 0) : nullptr;
   const double llb = ll[b];
   if (!(llb - llb == 0.0)) {  // the whole wave
-    tvl_fill_nan(bo, Vo, Co, 0, T, lane);
+    fill_nan<M>(bo, Vo, Co, 0, T, lane);
     if (lane == 0) atomicAdd(flags + 5, 1u);
     return;
   }
@@ -103,8 +82,8 @@ __global__ __launch_bounds__(64) void tvl_smooth_kernel(const double* __restrict
   }
 
   const size_t rb = (size_t)b * (size_t)rec_len;
-  for (int c = (n - 1) / kTvlSmoothChunk; c >= 0; --c) {
-    const int t0 = kTvlSmoothChunk * c + 1;  // the chunk's first column (1-based)
+  for (int c = (n - 1) / kSmoothChunk; c >= 0; --c) {
+    const int t0 = kSmoothChunk * c + 1;  // the chunk's first column (1-based)
     const int t = t0 + lane;
     const bool act = t <= n;
     const int tt = act ? t : n;  // an idle lane repeats the window's last column and stores nothing
@@ -118,16 +97,9 @@ __global__ __launch_bounds__(64) void tvl_smooth_kernel(const double* __restrict
         for (int j = 0; j < M; ++j) Pm[i][j] = P1[i][j];
       }
     } else {
-      const double* pa = rec_beta + (rb + (size_t)(tt - 2)) * M;
-      const double* pp = rec_P + (rb + (size_t)(tt - 2)) * M * M;
-#pragma unroll
-      for (int i = 0; i < M; ++i) {
-        a[i] = pa[i];
-#pragma unroll
-        for (int j = 0; j < M; ++j) Pm[i][j] = pp[j * M + i];
-      }
+      sm::record_moments<M>(rec_beta, rec_P, rb + (size_t)(tt - 2), a, Pm);
     }
-    double af[M], Pf[M][M];
+    sm::StepOps<M> o;
     {
       tg::StepConst kc;
       tg::step_consts(a, minm, kc);
@@ -142,21 +114,10 @@ __global__ __launch_bounds__(64) void tvl_smooth_kernel(const double* __restrict
         missing = missing || (y != y);
         ts::accum(kc, a, mr.x, mr.y, exp(-(kc.lam * mr.x)), y, mo);
       }
-      sm::StepOps<M> o;
       const double det = ts::column_operands(gm, m, a, Pm, mo, N, missing, o);
       ok = ok && ts::det_usable(det, missing, tt);
-#pragma unroll
-      for (int i = 0; i < M; ++i) {
-        af[i] = o.af[i];
-        ops[kTvlSmoothChunk * i + lane] = o.s[i];
-#pragma unroll
-        for (int j = 0; j < M; ++j) {
-          Pf[i][j] = o.Pf[i][j];
-          ops[kTvlSmoothChunk * (M + i * M + j) + lane] = o.W[i][j];
-          ops[kTvlSmoothChunk * (M + M * M + i * M + j) + lane] = o.L[i][j];
-        }
-      }
     }
+    sm::store_operands<M>(ops, lane, o);
     wave_lds_sync();
     // 2. the chain over the chunk's columns, last to first; this lane keeps r_t, N_t of its own column
     double rt[M], Nt[M][M];
@@ -166,18 +127,18 @@ __global__ __launch_bounds__(64) void tvl_smooth_kernel(const double* __restrict
 #pragma unroll
       for (int j = 0; j < M; ++j) Nt[i][j] = 0.0;
     }
-    for (int j = min(n - t0, kTvlSmoothChunk - 1); j >= 0; --j) {
+    for (int j = min(n - t0, kSmoothChunk - 1); j >= 0; --j) {
       const bool mine = j == lane;
       double s[M], W[M][M], L[M][M];
 #pragma unroll
       for (int i = 0; i < M; ++i) {
         rt[i] = mine ? r[i] : rt[i];
-        s[i] = ops[kTvlSmoothChunk * i + j];
+        s[i] = ops[kSmoothChunk * i + j];
 #pragma unroll
         for (int k = 0; k < M; ++k) {
           Nt[i][k] = mine ? Nm[i][k] : Nt[i][k];
-          W[i][k] = ops[kTvlSmoothChunk * (M + i * M + k) + j];
-          L[i][k] = ops[kTvlSmoothChunk * (M + M * M + i * M + k) + j];
+          W[i][k] = ops[kSmoothChunk * (M + i * M + k) + j];
+          L[i][k] = ops[kSmoothChunk * (M + M * M + i * M + k) + j];
         }
       }
       sm::chain_step<M>(s, W, L, r, Nm);
@@ -194,7 +155,7 @@ __global__ __launch_bounds__(64) void tvl_smooth_kernel(const double* __restrict
         for (int j = 0; j < M; ++j) Pn[i][j] = lag ? pp[j * M + i] : 0.0;
     }
     double bs[M], V[M][M], C[M][M];
-    const bool fin = sm::step_outputs<M>(m, af, Pf, rt, Nt, lag, Pn, bs, V, C);
+    const bool fin = sm::step_outputs<M>(m, o.af, o.Pf, rt, Nt, lag, Pn, bs, V, C);
     ok = ok && (fin || !act);
     if (act) {
 #pragma unroll
@@ -212,12 +173,8 @@ __global__ __launch_bounds__(64) void tvl_smooth_kernel(const double* __restrict
     }
   }
   // a column without a usable determinant or an output that is not finite makes the candidate unavailable
-  const bool bad = __ballot(!ok) != 0ull;
-  if (bad) {
-    __threadfence();
-    if (lane == 0) atomicAdd(flags + 5, 1u);
-  }
-  tvl_fill_nan(bo, Vo, Co, bad ? 0 : n, T, lane);
+  const bool bad = sm::raise_unavailable(ok, lane, flags);
+  fill_nan<M>(bo, Vo, Co, bad ? 0 : n, T, lane);
 }
 
 int tvl_smooth_max_n() { return tvl_max_n(); }

@@ -8,7 +8,7 @@ import pytest
 from gpu_scenarios import assert_same_bits, same_bits
 from grad_rule import REL, assert_candidate_rule, assert_gradient_rule, chain_factor
 from yfm_amd import KIND_DNS, KIND_TVL
-from yfm_amd.params import n_params, transform_params
+from yfm_amd.params import n_params, state_dim, transform_params
 
 P, B = 4, 100
 
@@ -140,3 +140,110 @@ def test_bit_comparison():
             assert_same_bits(a, b)
     with pytest.raises(AssertionError):
         assert_same_bits([1.0], [2.0], nan_payloads=False)
+
+
+# ---- tests/call_steps.py: the comparer of the call sequences, and the table's constructed flags -----------------------
+def _result():
+    nan = np.array([0x7FF8000000000000], dtype=np.uint64).view(np.float64)[0]
+    out = {"ll": np.array([-3.5, nan, -np.inf, 0.0]), "grad": np.arange(8.0).reshape(2, 4)}
+    cnt = {"flags": (1, 1), "deferred": 2, "unavailable": 3, "steady": 0}
+    return out, cnt
+
+
+def _copy(r):
+    return {k: v.copy() for k, v in r[0].items()}, dict(r[1])
+
+
+def test_sequence_comparer_accepts_equal_runs_and_fails_on_one_counter_one_bit_or_one_key():
+    import call_steps as CS
+    ref = _result()
+    CS.assert_same_result(_copy(ref), ref)
+    for key, value in (("flags", (1, 2)), ("flags", (0, 1)), ("deferred", 3), ("unavailable", 2), ("steady", 1)):
+        got = _copy(ref)
+        got[1][key] = value  # one flipped counter
+        with pytest.raises(AssertionError):
+            CS.assert_same_result(got, ref)
+    got = _copy(ref)
+    got[0]["grad"][1, 2] = np.nextafter(got[0]["grad"][1, 2], np.inf)  # one differing bit
+    with pytest.raises(AssertionError):
+        CS.assert_same_result(got, ref)
+    got = _copy(ref)
+    got[0]["ll"][1] = np.array([0x7FF8000000000001], dtype=np.uint64).view(np.float64)[0]  # … in a NaN's payload
+    with pytest.raises(AssertionError):
+        CS.assert_same_result(got, ref)
+    got = _copy(ref)
+    got[0]["ll"][3] = -0.0
+    with pytest.raises(AssertionError):
+        CS.assert_same_result(got, ref)
+    got = _copy(ref)
+    del got[0]["grad"]  # a missing output
+    with pytest.raises(AssertionError):
+        CS.assert_same_result(got, ref)
+    got = _copy(ref)
+    got[0]["extra"] = np.zeros(1)
+    with pytest.raises(AssertionError):
+        CS.assert_same_result(got, ref)
+    with pytest.raises(AssertionError):  # counters where the reference defines none
+        CS.assert_same_result(_copy(ref), (ref[0], None))
+
+
+def test_sequence_constructed_counters_can_fail():
+    import call_steps as CS
+    step = CS.Step("s", lambda: None, lambda e: {}, flags=(1, 1), deferred=2, unavailable=3, value="ll")
+    ref = _result()
+    CS.assert_constructed(step, ref)
+    for key, value in (("flags", (1, 0)), ("deferred", 0), ("unavailable", 0), ("steady", 128)):
+        got = _copy(ref)
+        got[1][key] = value
+        with pytest.raises(AssertionError):
+            CS.assert_constructed(step, got)
+    got = _copy(ref)
+    got[0]["ll"][0] = -np.inf  # the values' own −Inf count no longer is the flag
+    with pytest.raises(AssertionError):
+        CS.assert_constructed(step, got)
+    free = CS.Step("d", lambda: None, lambda e: {}, flags=(1, 1), deferred=2, unavailable=3, steady=None, value="ll")
+    got = _copy(ref)
+    got[1]["steady"] = 128  # not constructible: any number passes, the other counters still count
+    CS.assert_constructed(free, got)
+    got[1]["deferred"] = 0
+    with pytest.raises(AssertionError):
+        CS.assert_constructed(free, got)
+    silent = CS.Step("r", lambda: None, lambda e: {}, flags=None)
+    CS.assert_constructed(silent, ({}, None))
+    with pytest.raises(AssertionError):
+        CS.assert_constructed(silent, ref)
+
+
+def test_sequence_table_flags_are_the_c_oracles_counts():
+    """Every Kalman-kind batch of the table, the dirtier and the victim: the NaN and −Inf counts the table constructs
+    are those of the dense FP64 restatement of the reference (oracle/yfm_oracle.c), and the steps' names, the pair
+    representatives and the batch sizes are what the sequences assume."""
+    import call_steps as CS
+    from oracle import kalman_oracle as O
+    from oracle.truth import loglik_oracle
+    table = CS.build_table()
+    assert set(CS.PAIR_STEPS) <= set(table) and len(CS.PAIR_STEPS) == 13
+    shapes = {table[n].panel()[0].shape for n in CS.PAIR_STEPS}
+    assert {s[0] for s in shapes} >= {4, 30, 64, 65, 67} and {s[1] for s in shapes} >= {8, 12, 16, 40}
+    steps = list(table.values()) + [CS.dirtier(), CS.victim()]
+    checked = 0
+    for s in steps:
+        if s.batch is None:
+            continue
+        Y, mats = s.panel()
+        Th = s.batch()
+        assert Th.shape[1] <= 16 or s.name == "D", s.name
+        ll = loglik_oracle(s.kind, Y, mats, Th, space=s.space)
+        if s.name.endswith("loss_array"):  # its −Inf count is of its own rows, which σ² = 0 leaves finite
+            Tc = Th if s.space == 1 else transform_params(s.kind, Th)
+            for b in np.flatnonzero(~np.isnan(ll)):
+                st = O.KalmanState.fresh(s.kind, mats, state_dim(s.kind))
+                O.set_params(st, Tc[:, b])
+                assert np.isfinite(O.get_loss_array(st, Y)).all(), (s.name, b)
+            assert tuple(s.flags) == (int(np.isnan(ll).sum()), 0), s.name
+            checked += 1
+            continue
+        assert (int(np.isnan(ll).sum()), int(np.isneginf(ll).sum())) == tuple(s.flags), (s.name, ll)
+        assert len({Th[:, b].tobytes() for b in range(Th.shape[1])}) == Th.shape[1], s.name  # no two candidates equal
+        checked += 1
+    assert checked >= 30

@@ -27,6 +27,7 @@ HOST_CHECKS = {
     "tvl_score_host_check": {False: PLAIN_BUILD, True: SAN_BUILD},
     "smooth_host_check": {False: PLAIN_BUILD, True: SAN_BUILD},
     "tvl_smooth_host_check": {False: PLAIN_BUILD, True: SAN_BUILD},
+    "kalman_map_host_check": {False: PLAIN_BUILD, True: SAN_BUILD},
     "msed_host_check": {True: SAN_BUILD},
     "msed_grad_host_check": {True: SAN_BUILD},
     "msed_fullgrad_host_check": {True: SAN_BUILD},

@@ -40,6 +40,10 @@ struct Params {
 constexpr int param_count(int M, int lead) { return lead + 1 + M * (M + 1) / 2 + M + M * M; }
 
 // transform_params (space == 0) + set_params!: θ layout [γ…, σ², U by column (i ≤ j), δ, Φ row-major].
+// The same mathematics as kalman::decode of yfm_kalman_map.hpp, which the tangent and smoother kernels call.  The texts
+// are two on purpose: this file is compiled with the default contraction and that header switches it off for whatever
+// follows it, and calling the shared text from here changed the code of the loglik kernels (the ISA rule of DESIGN.md
+// §3; §3.14b has the rows).  The same holds for gauss_solve and init_state below.
 template <int M, int LEAD>
 __device__ __forceinline__ void decode_params(const double* __restrict__ th, int space, Params<M, LEAD>& p) {
   int k = 0;
@@ -92,7 +96,8 @@ __device__ __forceinline__ void decode_params(const double* __restrict__ th, int
 
 // In-register Gaussian elimination with partial pivoting (LAPACK getf2 pivot rule:
 // first index of max |a|), n×n with R right-hand sides.  Returns false on an exact
-// zero pivot — where LAPACK's getrf reports info > 0 and Julia throws.
+// zero pivot — where LAPACK's getrf reports info > 0 and Julia throws.  (kalman::gauss_solve of yfm_kalman_map.hpp is
+// the same elimination; why this file keeps its own text is said at decode_params.)
 template <int n, int R>
 __device__ __forceinline__ bool gauss_solve(double (&A)[n][n], double (&X)[n][R]) {
   bool ok = true;
@@ -158,6 +163,9 @@ __device__ __forceinline__ bool gauss_solve(double (&A)[n][n], double (&X)[n][R]
 //   M(M+1)/2 unknowns P_ij (i ≤ j) of P − ΦPΦ' = Q.  That system is singular iff
 //   some λ_iλ_j = 1, exactly when the reference's M²×M² matrix is.
 // Returns false where the reference would throw (exact zero pivot).
+// (kalman::mean_solve and kalman::lyapunov_matrix of yfm_kalman_map.hpp are the same two systems; why this file keeps
+// its own text is said at decode_params.  Here the compiler may contract δ_rc − Φ_ik·Φ_jk (k = l) into one fma, there
+// it may not: the two P₀ can differ in the last bit.)
 template <int M, int LEAD>
 __device__ __forceinline__ bool init_state(const Params<M, LEAD>& p, double (&beta)[M], double (&P)[M][M]) {
   double A[M][M];

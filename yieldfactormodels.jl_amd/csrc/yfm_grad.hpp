@@ -28,6 +28,8 @@
 #define YFM_GHD inline
 #endif
 
+#include "yfm_kalman_map.hpp"  // the parameter map and the small solves, shared with the smoothers
+
 namespace yfm {
 namespace grad {
 
@@ -37,59 +39,7 @@ constexpr double kLog2Pi = 1.8378770664093454835606594728112;
 
 YFM_GHD double gfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
-// Gaussian elimination with partial pivoting (getf2's pivot rule, selects instead of row indexing), n×n
-// with R right-hand sides; A is left holding U (its diagonal gives |det|).
-template <int n, int R>
-YFM_GHD void gauss_solve(double (&A)[n][n], double (&X)[n][R]) {
-#pragma unroll
-  for (int k = 0; k < n; ++k) {
-    int p = k;
-    double amax = fabs(A[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < n; ++i) {
-      const double a = fabs(A[i][k]);
-      const bool gt = a > amax;
-      amax = gt ? a : amax;
-      p = gt ? i : p;
-    }
-#pragma unroll
-    for (int i = k + 1; i < n; ++i) {
-      const bool s = (p == i);
-#pragma unroll
-      for (int c = k; c < n; ++c) {
-        const double a = A[k][c], b = A[i][c];
-        A[k][c] = s ? b : a;
-        A[i][c] = s ? a : b;
-      }
-#pragma unroll
-      for (int c = 0; c < R; ++c) {
-        const double a = X[k][c], b = X[i][c];
-        X[k][c] = s ? b : a;
-        X[i][c] = s ? a : b;
-      }
-    }
-    const double r = 1.0 / A[k][k];
-#pragma unroll
-    for (int i = k + 1; i < n; ++i) {
-      const double l = A[i][k] * r;
-#pragma unroll
-      for (int c = k + 1; c < n; ++c) A[i][c] = gfma(-l, A[k][c], A[i][c]);
-#pragma unroll
-      for (int c = 0; c < R; ++c) X[i][c] = gfma(-l, X[k][c], X[i][c]);
-    }
-  }
-#pragma unroll
-  for (int k = n - 1; k >= 0; --k) {
-    const double r = 1.0 / A[k][k];
-#pragma unroll
-    for (int c = 0; c < R; ++c) {
-      double s = X[k][c];
-#pragma unroll
-      for (int j = k + 1; j < n; ++j) s = gfma(-A[k][j], X[j][c], s);
-      X[k][c] = s * r;
-    }
-  }
-}
+using kalman::gauss_solve;
 
 // LDLᵀ of a symmetric 3×3 (lower triangle read), as yfm_device.hpp's LDLT with IEEE reciprocals
 struct Ldlt3 {
@@ -140,64 +90,13 @@ struct Model {
   double U[3][3], Q[3][3], delta[3], Phi[3][3];
 };
 
-// transform_params (space == 0) + set_params! for DNS (yfm_device.hpp decode_params<3, 1>)
+// transform_params (space == 0) + set_params! for DNS
 YFM_GHD void decode(const double* th, int space, Model& m) {
-  int k = 0;
-  m.gam = th[k++];
-  const double es = exp(th[k]);
-  m.sigma2 = space == 0 ? es : th[k];
-  ++k;
-#pragma unroll
-  for (int j = 0; j < 3; ++j)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      if (i <= j) {
-        double x = th[k++];
-        if (i == j) {
-          const double e = exp(x);
-          x = space == 0 ? e : x;
-        }
-        m.U[i][j] = x;
-      } else {
-        m.U[i][j] = 0.0;
-      }
-    }
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      double s = 0.0;
-#pragma unroll
-      for (int l = 0; l < 3; ++l) s = gfma(m.U[l][i], m.U[l][j], s);
-      m.Q[i][j] = s;
-    }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) m.delta[i] = th[k++];
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      double x = th[k++];
-      if (i == j) {
-        const double y = exp(x);
-        const double e = 2.0 * y / (1.0 + y) - 1.0;
-        x = space == 0 ? e : x;
-      }
-      m.Phi[i][j] = x;
-    }
+  kalman::decode<3, 1>(th, space, &m.gam, m.sigma2, m.U, m.Q, m.delta, m.Phi);
 }
 
-// dθ_c[d]/dθ[d]: exp for the positive entries, d/dx (2y/(1+y) − 1) = 2y/(1+y)² (y = eˣ) for the Φ diagonal
-// (transformations.jl:2-4, :21-26), 1 elsewhere and in the constrained space
-YFM_GHD double chain_factor(const double* th, int space, int d) {
-  const int dc = d < kNP ? d : kNP - 1;
-  const double y = exp(th[dc]);
-  const bool pos = d == 1 || d == 2 || d == 4 || d == 7;
-  const bool r11 = d == 11 || d == 15 || d == 19;
-  const double dr = 2.0 * y / ((1.0 + y) * (1.0 + y));
-  const double f = pos ? y : (r11 ? dr : 1.0);
-  return space == 0 ? f : 1.0;
-}
+// dθ_c[d]/dθ[d] (the exp rows 1, 2, 4, 7, the Φ-diagonal rows 11, 15, 19)
+YFM_GHD double chain_factor(const double* th, int space, int d) { return kalman::chain_factor<kM, 1>(th, space, d); }
 
 // DNS loadings of one maturity (dns.jl:51-65) and their γ-derivatives: with κ = e^γ/λ (dτ/dγ = τκ),
 // dZ₁ = −Z₂κ, dZ₂ = κ(zτ − Z₂)
@@ -341,43 +240,15 @@ YFM_GHD void seed(const Model& m, int d, Tangent& t) {
   }
 }
 
-// the symmetric-subspace Lyapunov operator of init_state (yfm_device.hpp): row (i, j), column (k, l), i ≤ j, k ≤ l
-YFM_GHD void lyapunov_matrix(const double (&Phi)[3][3], double (&L)[6][6]) {
-  int r = 0;
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-#pragma unroll
-    for (int j = i; j < 3; ++j) {
-      int c = 0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int l = k; l < 3; ++l) {
-          double s = Phi[i][k] * Phi[j][l];
-          if (k != l) s = gfma(Phi[i][l], Phi[j][k], s);
-          L[r][c] = (r == c ? 1.0 : 0.0) - s;
-          ++c;
-        }
-      ++r;
-    }
-}
+using kalman::lyapunov_matrix;  // the symmetric-subspace operator of P − ΦPΦ' = Q
 
 // initialize_filter (filter.jl:1-10) and its tangents through both solves:
 //   (I − Φ) dβ₀ = dδ + dΦ β₀,    dP₀ − Φ dP₀ Φ' = dQ + dΦ P₀ Φ' + Φ P₀ dΦ'
 template <int ND>
 YFM_GHD void init_state(const Common& c, State& s, Tangent (&t)[ND]) {
   const Model& m = c.m;
-  double A[3][3], X[3][4];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      A[i][j] = (i == j ? 1.0 : 0.0) - m.Phi[i][j];
-      X[i][1 + j] = (i == j) ? 1.0 : 0.0;
-    }
-    X[i][0] = m.delta[i];
-  }
-  gauss_solve<3, 4>(A, X);  // β₀ and (I − Φ)⁻¹
+  double X[3][4];
+  kalman::mean_solve<3, 4>(m.Phi, m.delta, X);  // β₀ and (I − Φ)⁻¹
 #pragma unroll
   for (int i = 0; i < 3; ++i) s.beta[i] = X[i][0];
 #pragma unroll

@@ -29,6 +29,8 @@
 #define YFM_SHD inline
 #endif
 
+#include "yfm_kalman_map.hpp"  // the parameter map and the small solves, shared with the tangent kernels
+
 namespace yfm {
 namespace smooth {
 
@@ -45,54 +47,11 @@ struct Model {
   double Q[M][M], delta[M], Phi[M][M];
 };
 
-// transform_params (space == 0) + set_params! (yfm_device.hpp decode_params)
+// transform_params (space == 0) + set_params!; the smoother has no use for U beyond Q = U'U
 template <int M>
 YFM_SHD void decode(const double* th, int space, Model<M>& m) {
-  int k = 0;
-#pragma unroll
-  for (int l = 0; l < Model<M>::kLead; ++l) m.gam[l] = th[k++];
-  const double es = exp(th[k]);
-  m.sigma2 = space == 0 ? es : th[k];
-  ++k;
   double U[M][M];
-#pragma unroll
-  for (int j = 0; j < M; ++j)
-#pragma unroll
-    for (int i = 0; i < M; ++i) {
-      if (i <= j) {
-        double x = th[k++];
-        if (i == j) {
-          const double e = exp(x);
-          x = space == 0 ? e : x;
-        }
-        U[i][j] = x;
-      } else {
-        U[i][j] = 0.0;
-      }
-    }
-#pragma unroll
-  for (int i = 0; i < M; ++i)
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      double s = 0.0;
-#pragma unroll
-      for (int l = 0; l < M; ++l) s = sfma(U[l][i], U[l][j], s);
-      m.Q[i][j] = s;
-    }
-#pragma unroll
-  for (int i = 0; i < M; ++i) m.delta[i] = th[k++];
-#pragma unroll
-  for (int i = 0; i < M; ++i)
-#pragma unroll
-    for (int j = 0; j < M; ++j) {
-      double x = th[k++];
-      if (i == j) {
-        const double y = exp(x);
-        const double e = 2.0 * y / (1.0 + y) - 1.0;
-        x = space == 0 ? e : x;
-      }
-      m.Phi[i][j] = x;
-    }
+  kalman::decode<M, Model<M>::kLead>(th, space, m.gam, m.sigma2, U, m.Q, m.delta, m.Phi);
 }
 
 // row i of Z: [1, S(λ₁), C(λ₁) (, S(λ₂), C(λ₂))], λ = 0.01 + e^γ (dns.jl:51-65; the GNS5 extension takes two γ)
@@ -110,80 +69,19 @@ YFM_SHD void loading_row(const Model<M>& m, double mat, double (&z)[M]) {
   }
 }
 
-// Gaussian elimination with partial pivoting (getf2's pivot rule, selects instead of row indexing), n×n with R
-// right-hand sides; false on an exact zero pivot, where the reference's solve throws
-template <int n, int R>
-YFM_SHD bool gauss_solve(double (&A)[n][n], double (&X)[n][R]) {
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < n; ++k) {
-    int p = k;
-    double amax = fabs(A[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < n; ++i) {
-      const double a = fabs(A[i][k]);
-      const bool gt = a > amax;
-      amax = gt ? a : amax;
-      p = gt ? i : p;
-    }
-#pragma unroll
-    for (int i = k + 1; i < n; ++i) {
-      const bool s = (p == i);
-#pragma unroll
-      for (int c = k; c < n; ++c) {
-        const double a = A[k][c], b = A[i][c];
-        A[k][c] = s ? b : a;
-        A[i][c] = s ? a : b;
-      }
-#pragma unroll
-      for (int c = 0; c < R; ++c) {
-        const double a = X[k][c], b = X[i][c];
-        X[k][c] = s ? b : a;
-        X[i][c] = s ? a : b;
-      }
-    }
-    ok = ok && (A[k][k] != 0.0);
-    const double r = 1.0 / A[k][k];
-#pragma unroll
-    for (int i = k + 1; i < n; ++i) {
-      const double l = A[i][k] * r;
-#pragma unroll
-      for (int c = k + 1; c < n; ++c) A[i][c] = sfma(-l, A[k][c], A[i][c]);
-#pragma unroll
-      for (int c = 0; c < R; ++c) X[i][c] = sfma(-l, X[k][c], X[i][c]);
-    }
-  }
-#pragma unroll
-  for (int k = n - 1; k >= 0; --k) {
-    const double r = 1.0 / A[k][k];
-#pragma unroll
-    for (int c = 0; c < R; ++c) {
-      double s = X[k][c];
-#pragma unroll
-      for (int j = k + 1; j < n; ++j) s = sfma(-A[k][j], X[j][c], s);
-      X[k][c] = s * r;
-    }
-  }
-  return ok;
-}
+using kalman::gauss_solve;
 
 // a_1 = (I − Φ) \ δ (filter.jl:4)
 template <int M>
 YFM_SHD bool init_mean(const Model<M>& m, double (&a)[M]) {
-  double A[M][M], x[M][1];
-#pragma unroll
-  for (int i = 0; i < M; ++i) {
-#pragma unroll
-    for (int j = 0; j < M; ++j) A[i][j] = (i == j ? 1.0 : 0.0) - m.Phi[i][j];
-    x[i][0] = m.delta[i];
-  }
-  const bool ok = gauss_solve<M, 1>(A, x);
+  double x[M][1];
+  const bool ok = kalman::mean_solve<M, 1>(m.Phi, m.delta, x);
 #pragma unroll
   for (int i = 0; i < M; ++i) a[i] = x[i][0];
   return ok;
 }
 
-// P_1 (filter.jl:7) on the symmetric subspace, as yfm_device.hpp init_state states it: the S = M(M+1)/2 unknowns P_ij
+// P_1 (filter.jl:7) on the symmetric subspace (kalman::lyapunov_coefficient): the S = M(M+1)/2 unknowns P_ij
 // (i ≤ j) of P − ΦPΦ' = Q.  The S × (S + 1) augmented system lives in memory the caller provides (LDS on the device):
 // a wave's lanes share the elimination, element e of a row update going to lane e mod nl, with `sync` between the
 // phases; the host runs it with lane = 0, nl = 1.  Every lane returns the same verdict and reads the same P.
@@ -208,8 +106,7 @@ struct InitCov {
           for (int k = 0; k < M; ++k)
 #pragma unroll
             for (int l = k; l < M; ++l) {
-              double s = m.Phi[i][k] * m.Phi[j][l];
-              if (k != l) s = sfma(m.Phi[i][l], m.Phi[j][k], s);
+              const double s = kalman::lyapunov_coefficient<M>(m.Phi, i, j, k, l);
               if ((r * LD + c) % nl == lane) A[r * LD + c] = (r == c ? 1.0 : 0.0) - s;
               ++c;
             }

@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kTvlGradBlock) void tvl_grad_kernel(const double* _
   wave_lds_sync();
   g::State s;
   g::Tangent t[ND];
-  tvl_for_slots<ND>([&](auto sl) { g::seed(g::slot_direction(L, sl(), j), t[sl()]); });
+  for_slots<ND>([&](auto sl) { g::seed(g::slot_direction(L, sl(), j), t[sl()]); });
   g::init_state<ND>(m, Linv, s, t);
 
   double l_minm = __builtin_inf();  // this lane's smallest maturity (the λ-overflow test of step_consts)
@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kTvlGradBlock) void tvl_grad_kernel(const double* _
     g::primal_update(mk, s, mo, N, u);
     g::Filtered f;
     g::filtered_state(mk, s, u, nan_col, f);
-    tvl_for_slots<ND>(
+    for_slots<ND>(
         [&](auto sl) { g::tangent_step<tvl_slot_mask<L, sl()>()>(mk, s, u, mo, N, f, nan_col, t[sl()], acc); });
     g::primal_step(mk, u, f, nan_col, s, acc);
   }

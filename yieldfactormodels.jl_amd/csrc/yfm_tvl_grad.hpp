@@ -32,7 +32,7 @@
 // Gradients are taken with respect to the constrained parameters and multiplied by dθ_c/dθ at the end.
 // Every fused multiply-add is an explicit fma; contraction is off.
 #pragma once
-#include "yfm_grad.hpp"  // gfma, gauss_solve, YFM_GHD
+#include "yfm_grad.hpp"  // gfma, YFM_GHD, and yfm_kalman_map.hpp through it
 #include "yfm_tvl_step.hpp"  // the statistics of a step, shared with tvl_loglik_kernel
 
 namespace yfm {
@@ -56,64 +56,16 @@ struct Model {
   double U[4][4], Q[4][4], delta[4], Phi[4][4];
 };
 
-// transform_params (space == 0) + set_params! for TVλ (yfm_device.hpp decode_params<4, 0>)
+// transform_params (space == 0) + set_params! for TVλ.  (1/σ² is formed before the shared call, from the same select:
+// formed after it, from m.sigma2, it moved tvl_grad_kernel<32, 1> by three instructions.)
 YFM_GHD void decode(const double* th, int space, Model& m) {
-  int k = 0;
-  const double es = exp(th[k]);
-  m.sigma2 = space == 0 ? es : th[k];
-  m.rsig2 = 1.0 / m.sigma2;
-  ++k;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      if (i <= j) {
-        double x = th[k++];
-        if (i == j) {
-          const double e = exp(x);
-          x = space == 0 ? e : x;
-        }
-        m.U[i][j] = x;
-      } else {
-        m.U[i][j] = 0.0;
-      }
-    }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double s = 0.0;
-#pragma unroll
-      for (int l = 0; l < 4; ++l) s = gfma(m.U[l][i], m.U[l][j], s);
-      m.Q[i][j] = s;
-    }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) m.delta[i] = th[k++];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      double x = th[k++];
-      if (i == j) {
-        const double y = exp(x);
-        const double e = 2.0 * y / (1.0 + y) - 1.0;
-        x = space == 0 ? e : x;
-      }
-      m.Phi[i][j] = x;
-    }
+  const double es = exp(th[0]);
+  m.rsig2 = 1.0 / (space == 0 ? es : th[0]);
+  kalman::decode<4, 0>(th, space, nullptr, m.sigma2, m.U, m.Q, m.delta, m.Phi);
 }
 
-// dθ_c[d]/dθ[d]: exp for σ² and the diagonal of U, 2y/(1+y)² (y = eˣ) for the Φ diagonal
-// (transformations.jl:2-4, :21-26), 1 elsewhere and in the constrained space
-YFM_GHD double chain_factor(const double* th, int space, int d) {
-  const int dc = d < kNP ? d : kNP - 1;
-  const double y = exp(th[dc]);
-  const bool pos = d == 0 || d == 1 || d == 3 || d == 6 || d == 10;
-  const bool r11 = d == 15 || d == 20 || d == 25 || d == 30;
-  const double dr = 2.0 * y / ((1.0 + y) * (1.0 + y));
-  const double f = pos ? y : (r11 ? dr : 1.0);
-  return space == 0 ? f : 1.0;
-}
+// dθ_c[d]/dθ[d] (the exp rows 0, 1, 3, 6, 10, the Φ-diagonal rows 15, 20, 25, 30)
+YFM_GHD double chain_factor(const double* th, int space, int d) { return kalman::chain_factor<kM, 0>(th, space, d); }
 
 // ---- filter state and one tangent direction ----------------------------------------------------------
 struct State {
@@ -174,26 +126,7 @@ YFM_GHD int slot_direction(int L, int slot, int j) {
 // direction d (θ_c index; d ≥ kNP: a padding direction, every seed zero)
 YFM_GHD void seed(int d, Tangent& t) { t.d = d; }
 
-// the symmetric-subspace Lyapunov operator of init_state (yfm_device.hpp): row (i, j), column (k, l), i ≤ j, k ≤ l
-YFM_GHD void lyapunov_matrix(const double (&Phi)[4][4], double (&L)[10][10]) {
-  int r = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = i; j < 4; ++j) {
-      int c = 0;
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int l = k; l < 4; ++l) {
-          double s = Phi[i][k] * Phi[j][l];
-          if (k != l) s = gfma(Phi[i][l], Phi[j][k], s);
-          L[r][c] = (r == c ? 1.0 : 0.0) - s;
-          ++c;
-        }
-      ++r;
-    }
-}
+using kalman::lyapunov_matrix;  // the symmetric-subspace operator of P − ΦPΦ' = Q
 
 // column c of the inverse of that operator (the same pivots whichever column: every caller factors the same matrix)
 YFM_GHD void lyapunov_inverse_column(const double (&Phi)[4][4], int c, double (&col)[10]) {
@@ -228,17 +161,8 @@ YFM_GHD void lyapunov_apply(const double* Linv, const double (&rhs)[10], double 
 // a column per lane, and shares; every direction then costs one 10×10 product.
 template <int ND>
 YFM_GHD void init_state(const Model& m, const double* Linv, State& s, Tangent (&t)[ND]) {
-  double A[4][4], X[4][5];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      A[i][j] = (i == j ? 1.0 : 0.0) - m.Phi[i][j];
-      X[i][1 + j] = (i == j) ? 1.0 : 0.0;
-    }
-    X[i][0] = m.delta[i];
-  }
-  gauss_solve<4, 5>(A, X);  // β₀ and (I − Φ)⁻¹
+  double X[4][5];
+  kalman::mean_solve<4, 5>(m.Phi, m.delta, X);  // β₀ and (I − Φ)⁻¹
 #pragma unroll
   for (int i = 0; i < 4; ++i) s.beta[i] = X[i][0];
 #pragma unroll

@@ -1,8 +1,7 @@
 // yfm_tvl_grad_map.hpp — the lane mapping that the TVλ tangent kernels share (yfm_tvl_grad.hip, yfm_tvl_score.hip):
 // one candidate per group of L lanes, ND directions per lane (tvlgrad::slot_direction).  Device only.
 #pragma once
-#include <type_traits>
-
+#include "yfm_grad_map.hpp"  // for_slots
 #include "yfm_tvl_grad.hpp"
 
 namespace yfm {
@@ -20,12 +19,6 @@ constexpr int tvl_slot_mask() {
   constexpr int lo = S * L, hi = S * L + L - 1;
   return (lo <= 0 ? g::kSeedS : 0) | ((lo < g::kOffD && hi >= g::kOffU) ? g::kSeedQ : 0) |
          ((lo < g::kOffF && hi >= g::kOffD) ? g::kSeedD : 0);
-}
-// f(integral_constant<int, S>) for S = 0 … ND − 1
-template <int ND, int S = 0, class F>
-__device__ __forceinline__ void tvl_for_slots(F&& f) {
-  f(std::integral_constant<int, S>{});
-  if constexpr (S + 1 < ND) tvl_for_slots<ND, S + 1>(f);
 }
 
 // This lane's index in its group, formed afresh (the wave's lane count through an operand the compiler cannot fold):
